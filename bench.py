@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the Flood-complex coverage sweep on MI355X (BASELINE.json metric).
 
-    python bench.py                       # 1 GPU, cfg 2, 50 steps
+    python bench.py                       # 1 GPU, cfg 2, 50 steps: the headline line only
+    python bench.py --full                # + CPU baseline, parity, roofline, cold / index-ready / e2e, cfg 3-5 lines
+    python bench.py --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N ...          # starts its own N ranks (torch.distributed.run child, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # what the driver runs for N > 1
+
+A plain run sets up, warms up, times --steps steps and prints the headline (metric, value, ms_per_step, ...).
+Everything else the script measures or checks runs only with --full.
 
 A "step" is one full coverage sweep of the workload from the RAW cloud and the simplices resident in HBM to the
 per-face filtration values in HBM: index build (bounding box, Hilbert codes, radix argsort, gather, box tree - the
@@ -33,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: peak fp32 vector
 
@@ -138,17 +144,46 @@ def parse_args():
                     help="draw the synthetic cloud on the GPU (flooder_amd.synthetic with device=: SURVEY.md 8 f-4) instead "
                          "of on the host; the timed step starts from the cloud in HBM either way")
     ap.add_argument("--extra-workloads", default=None, metavar="cfg3,cfg5",
-                    help="further workloads timed by child runs and attached to the line as extra_workloads "
-                         "(default: cfg3,cfg5 on the default single-GPU cfg2 run; 'none' to skip)")
+                    help="--full: further workloads timed by child runs and attached to the line as extra_workloads "
+                         "(default: cfg3,cfg4,cfg5 on the default single-GPU cfg2 run; 'none' to skip)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=INT",
                     help="flooder_set_option switch (include/flooder_hip.h), e.g. --option cell_grid=512")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: landmark-selection timings, streamed H2D (cfg5), candidate "
+                         "pairs and roofline, index-ready / host / cold steps, end-to-end flood_complex, work counters, "
+                         "CPU baseline + parity, per-rank spans, and the cfg3 / cfg4 / cfg5 child runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """``arrays``: name -> float32 / float64 numpy array.  An array larger than its even share of DUMP_LIMIT_BYTES is
+    replaced by a fixed, seeded sample of its rows (ascending), whose row numbers go beside it as ``<name>_rows.npy``
+    (float64)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 0:
+            row_bytes = a.nbytes // a.shape[0] + 8
+            keep = max(1, min(a.shape[0], share // row_bytes))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def run_extra_workload(wl: str) -> dict:
     """One bench line of another workload from a CHILD process (this one keeps its GPU context), reduced to what the
     judge reads: step time, the dominant kernel's roofline fractions, per-kernel times, parity."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "5" if wl == "cfg4" else "10", "--warmup",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", wl, "--steps", "5" if wl == "cfg4" else "10", "--warmup",
            "1" if wl == "cfg4" else "2", "--no-cold", "--no-e2e", "--no-all-cores", "--cpu-sample",
            {"cfg5": "150", "cfg4": "200"}.get(wl, "300"), "--extra-workloads", "none"]
     t0 = time.perf_counter()
@@ -277,7 +312,7 @@ def main():
     # from pinned memory on a copy stream, every chunk's bounding-box reduction overlapped with the next copy; the
     # streamed index is then checked to be the resident one (same rows, same tree)
     h2d_stream = None
-    if args.workload == "cfg5" and world == 1:
+    if args.full and args.workload == "cfg5" and world == 1:
         pinned = pts_cpu.pin_memory()
         core.index_from_host(pinned[:1 << 20], dev)            # warm-up (allocator, streams)
         torch.cuda.synchronize()
@@ -305,20 +340,21 @@ def main():
         return out_, time.perf_counter() - t0_
 
     lms, t_fps_cold = timed_fps()
-    lms, t_fps = timed_fps()
-    # the brute-force sweep (one full pass over the cloud per landmark: fps_fast_kernel) on a bounded number of
-    # landmarks: the one genuinely bandwidth-bound kernel of the path, priced at its own bytes
-    n_brute = min(w["n_lms"], 128)
-    core.fps_indices(pts_full, n_brute, 0, method="brute")
-    torch.cuda.synchronize()
-    t0_b = time.perf_counter()
-    core.fps_indices(pts_full, n_brute, 0, method="brute")
-    torch.cuda.synchronize()
-    t_brute = time.perf_counter() - t0_b
-    fps_bucketed = w["dim"] <= core.FPS_BUCKET_MAX_DIM and w["n"] >= core.FPS_BUCKET_MIN_POINTS and w["n_lms"] > 64
-    t_fps_ready = None
-    if fps_bucketed:
-        _, t_fps_ready = timed_fps(index=core.PointIndex(pts_full))
+    if args.full:
+        lms, t_fps = timed_fps()
+        # the brute-force sweep (one full pass over the cloud per landmark: fps_fast_kernel) on a bounded number of
+        # landmarks: the one genuinely bandwidth-bound kernel of the path, priced at its own bytes
+        n_brute = min(w["n_lms"], 128)
+        core.fps_indices(pts_full, n_brute, 0, method="brute")
+        torch.cuda.synchronize()
+        t0_b = time.perf_counter()
+        core.fps_indices(pts_full, n_brute, 0, method="brute")
+        torch.cuda.synchronize()
+        t_brute = time.perf_counter() - t0_b
+        fps_bucketed = w["dim"] <= core.FPS_BUCKET_MAX_DIM and w["n"] >= core.FPS_BUCKET_MIN_POINTS and w["n_lms"] > 64
+        t_fps_ready = None
+        if fps_bucketed:
+            _, t_fps_ready = timed_fps(index=core.PointIndex(pts_full))
     d = w.get("max_dim", w["dim"])                   # dimension of the swept simplices (grid mode: the top one)
     t_cx = time.perf_counter()
     stree, simplices = core._build_complex(lms, d)
@@ -340,28 +376,31 @@ def main():
 
     # reference-defined work of this input (untimed): candidate pairs per simplex |X n ball_s| (core.py:156-217);
     # workloads with "p_sample" count them on that many random simplices and scale (cfg 4: 1.2 M triangles whose
-    # slabs hold half the cloud each - the full count is ~1e12 ball tests)
-    pts_pad0 = core._pad_rows(pts_full[torch.argsort(pts_full[:, axis])], dp)
-    search0 = pts_pad0[:, axis].contiguous()
-    p_sample = w.get("p_sample")
-    if p_sample and p_sample < S_all:
-        pick0 = torch.randperm(S_all, generator=torch.Generator().manual_seed(0))[:p_sample].to(dev)
-        c0, r0 = centers[pick0].contiguous(), radii[pick0].contiguous()
+    # slabs hold half the cloud each - the full count is ~1e12 ball tests).  Only --full reports it, and --order ball
+    # sorts by it; a plain run leaves it out
+    count_pairs = args.full or args.order == "ball"
+    p_sample = w.get("p_sample") if count_pairs else None
+    if count_pairs:
+        pts_pad0 = core._pad_rows(pts_full[torch.argsort(pts_full[:, axis])], dp)
+        search0 = pts_pad0[:, axis].contiguous()
+        if p_sample and p_sample < S_all:
+            pick0 = torch.randperm(S_all, generator=torch.Generator().manual_seed(0))[:p_sample].to(dev)
+            c0, r0 = centers[pick0].contiguous(), radii[pick0].contiguous()
+        else:
+            p_sample, c0, r0 = None, centers.contiguous(), radii.contiguous()
+        lo0 = torch.searchsorted(search0, (c0[:, axis] - r0).contiguous(), right=False)
+        hi0 = torch.searchsorted(search0, (c0[:, axis] + r0).contiguous(), right=True)
+        cnt0 = torch.zeros(c0.shape[0], dtype=torch.int32, device=dev)
+        _native.check(lib.flooder_ball_count_f32(_native.ptr(pts_pad0), pts_pad0.shape[0], w["dim"], dp,
+                                                 _native.ptr(c0), _native.ptr(r0), _native.ptr(lo0), _native.ptr(hi0),
+                                                 c0.shape[0], _native.ptr(cnt0), _native.current_stream_ptr(dev)),
+                      "ball_count")
+        if p_sample:
+            cnt_mean = float(cnt0.to(torch.float64).mean().item())
+            cnt0 = torch.full((S_all,), 0, dtype=torch.int32, device=dev)   # (per-simplex counts unknown: orders below unused)
+        del pts_pad0, search0, lo0, hi0
     else:
-        p_sample, c0, r0 = None, centers.contiguous(), radii.contiguous()
-    lo0 = torch.searchsorted(search0, (c0[:, axis] - r0).contiguous(), right=False)
-    hi0 = torch.searchsorted(search0, (c0[:, axis] + r0).contiguous(), right=True)
-    cnt0 = torch.zeros(c0.shape[0], dtype=torch.int32, device=dev)
-    _native.check(lib.flooder_ball_count_f32(_native.ptr(pts_pad0), pts_pad0.shape[0], w["dim"], dp,
-                                             _native.ptr(c0), _native.ptr(r0), _native.ptr(lo0), _native.ptr(hi0),
-                                             c0.shape[0], _native.ptr(cnt0), _native.current_stream_ptr(dev)),
-                  "ball_count")
-    P_scale = 1.0
-    if p_sample:
-        P_scale = S_all / float(p_sample)
-        cnt_mean = float(cnt0.to(torch.float64).mean().item())
-        cnt0 = torch.full((S_all,), 0, dtype=torch.int32, device=dev)   # (per-simplex counts unknown: orders below unused)
-    del pts_pad0, search0, lo0, hi0
+        cnt0 = torch.zeros(S_all, dtype=torch.int32, device=dev)       # (not counted: only the orders below read it)
     if args.order == "ball":  # experiment: heaviest simplices (by the reference's candidate count) first
         perm = torch.argsort(cnt0, descending=True)
         verts, centers, radii, simp, cnt0 = verts[perm], centers[perm], radii[perm], simp[perm], cnt0[perm]
@@ -531,7 +570,59 @@ def main():
     elapsed, step_ms, out_timed = timed_loop(args.steps, timer)   # (out_timed: the LAST TIMED step's values - parity below)
     ms_per_step = elapsed / args.steps * 1e3
     value = w["n"] * S_all / (elapsed / args.steps) / 1e6
+    k_ms = {k: v / args.steps for k, v in timer.totals_ms().items()}   # HIP events on the launch stream
+    if args.method != "cell" and "sweep" in k_ms:
+        k_ms["sweep_bvh" if args.method == "bvh" else "sweep_ball"] = k_ms.pop("sweep")
+    ms_index = k_ms.get("index", 0.0)
+    ms_sweep_only = ms_per_step - ms_index
 
+    # what a caller of the timed path receives from its last step: one value per distinct face of the complex (or per
+    # (simplex, face) where faces are not shared), and the same values per top simplex x face of the sample lattice,
+    # the simplices in the step's queue order
+    if args.dump_outputs and rank == 0:
+        arrays = {"face_values": out_timed}
+        if slots is not None:
+            arrays["simplex_face_values"] = out_timed[slots_all[0].long()]
+        dump_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in arrays.items()})
+
+    result = {
+        "metric": "M points×simplices/s (coverage sweep)",
+        "value": round(value, 3),
+        "unit": "M points×simplices/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "ms_per_step_mean": round(float(step_ms.mean()), 4),
+        "ms_per_step_std": round(float(step_ms.std()), 4),
+        "ms_per_step_min": round(float(step_ms.min()), 4),
+        "ms_index_build": round(ms_index, 4),
+        "value_sweep_only": round(w["n"] * S_all / (ms_sweep_only * 1e-3) / 1e6, 3),
+        "step_definition": "raw cloud + simplices in HBM -> index build (Hilbert sort + box tree) -> sweep -> exact "
+                           "finish -> [all_reduce] -> per-face values in HBM (value, ms_per_step: back-to-back steps, "
+                           "caches warm); value_sweep_only = value with the index span subtracted",
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic" if not args.device_cloud else f"synthetic, drawn on the device in {gen_ms:.1f} ms (flooder_amd.synthetic)",
+        "config": {
+            "workload": w["desc"], "points": w["n"], "landmarks": w["n_lms"], "top_simplices": S_all,
+            "top_simplices_rank0": S, "swept_dimension": d, "samples_per_simplex": R, "method": args.method,
+            "parallelism": (f"{args.shard}-shard x{world} ({backend})"
+                            + (" - kept for correctness: the culled sweeps walk every sample on every rank, only the "
+                               "reference's exhaustive formulation (--method ball) scales this way" if args.shard == "points" else "")
+                            if world > 1 else "single GPU"),
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result, ensure_ascii=False))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ------------------------------------------------------------------ --full: everything beyond the headline
     # the same step with a ready index (flood_complex(..., index=...) / the index generate_landmarks built): what a
     # caller pays who sweeps one cloud more than once - and each rank of a multi-GPU run, where the index build is
     # the part that does not divide
@@ -632,12 +723,7 @@ def main():
         out = out[slots_all[0].long()]     # (n_slots,) values per distinct face -> (S_all, F) for the parity check below
 
     # ------------------------------------------------------------------ per-kernel numbers (rank 0's share)
-    k_ms = {k: v / args.steps for k, v in timer.totals_ms().items()}   # HIP events on the launch stream
-    if args.method != "cell" and "sweep" in k_ms:
-        k_ms["sweep_bvh" if args.method == "bvh" else "sweep_ball"] = k_ms.pop("sweep")
     sweep_span = {"cell": "sweep", "bvh": "sweep_bvh", "ball": "sweep_ball"}[args.method]
-    ms_index = k_ms.get("index", 0.0)
-    ms_sweep_only = ms_per_step - ms_index
     # algorithmic bytes of one step on this rank: every candidate row read once per simplex
     # (P x 4 x dim), vertices, weights, and the result written once - the (S, F) face values on the fused path,
     # the (S, R) minima where they are materialised (unfused / tree / ball sweeps, point-sharded reduction)
@@ -736,19 +822,7 @@ def main():
     except Exception:
         pass
     dom_bytes = int(alg_bytes * dom_rec["unit_share"])
-    result = {
-        "metric": "M points×simplices/s (coverage sweep)",
-        "value": round(value, 3),
-        "unit": "M points×simplices/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "ms_per_step_mean": round(float(step_ms.mean()), 4),
-        "ms_per_step_std": round(float(step_ms.std()), 4),
-        "ms_per_step_min": round(float(step_ms.min()), 4),
-        "ms_index_build": round(ms_index, 4),
-        "value_sweep_only": round(w["n"] * S_all / (ms_sweep_only * 1e-3) / 1e6, 3),
+    result.update({
         "ms_per_step_index_ready": round(ms_cached, 4),
         "host": host_rec,
         "value_index_ready": round(w["n"] * S_all / (ms_cached * 1e-3) / 1e6, 3),
@@ -759,22 +833,11 @@ def main():
                            "(median of 5); ms_per_step_index_ready / value_index_ready: the step with a PointIndex "
                            "of the cloud passed in (flood_complex(..., index=...)), timed over the same number of "
                            "steps; value_sweep_only = value with the index span subtracted",
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic" if not args.device_cloud else f"synthetic, drawn on the device in {gen_ms:.1f} ms (flooder_amd.synthetic)",
         "config": {
-            "workload": w["desc"], "points": w["n"], "landmarks": w["n_lms"], "top_simplices": S_all, "complex": complex_rec,
-            "top_simplices_rank0": S, "swept_dimension": d,
-            "samples_per_simplex": R, "candidate_pairs_rank0": P_local,
+            **result["config"],
+            "complex": complex_rec, "candidate_pairs_rank0": P_local,
             "candidate_pairs_note": (f"mean of {p_sample} random simplices x S" if p_sample else "counted on every simplex"),
-            "pair_evals_rank0": pair_evals,
-            "parallelism": (f"{args.shard}-shard x{world} ({backend})"
-                            + (" - kept for correctness: the culled sweeps walk every sample on every rank, only the "
-                               "reference's exhaustive formulation (--method ball) scales this way" if args.shard == "points" else "")
-                            if world > 1 else "single GPU"),
-            "method": args.method, "pair_evals_done_rank0": int(done_evals),
+            "pair_evals_rank0": pair_evals, "pair_evals_done_rank0": int(done_evals),
             "sub_cloud_rows_rank0": (sub_rows[-1] if sub_rows else None),
             "sweep_stats_rank0": st_h,
             "sweep_stats_note": "work counters come from one extra untimed step (the timed steps run without them, as flood_complex does)",
@@ -849,7 +912,7 @@ def main():
                                         "and landmark (SURVEY.md 8d); wall clock incl. launches; a working set below "
                                         "256 MB is served by the Infinity Cache, not HBM"},
                 "hbm_peak_GBs": HBM_PEAK_GBS},
-    }
+    })
 
     # ------------------------------------------------------------------ CPU baseline + parity (rank 0, N=1)
     if world == 1 and not args.no_cpu_baseline:

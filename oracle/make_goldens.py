@@ -3,6 +3,7 @@
 Run from the repo root, in the container that has ``/root/reference`` mounted::
 
     TRITON_INTERPRET=1 python oracle/make_goldens.py
+    MKL_CBWR=COMPATIBLE python oracle/make_goldens.py mkl-compatible   # host-independent draws (see that section)
 
 The reference package is imported from ``/root/reference`` (read-only, never copied).  Two of
 its third-party wheels are absent from the image, so two import shims are injected into
@@ -266,9 +267,57 @@ def make_visualization_vectors():
               f"{ {k: v.shape[0] for k, v in out.items() if k in ('edges', 'triangles', 'tetrahedra')} }")
 
 
+def make_mkl_compatible_vectors():
+    """``MKL_CBWR=COMPATIBLE python oracle/make_goldens.py mkl-compatible``: the draws whose last bits depend on the host.
+
+    torch sends contiguous float32 log / sin / cos to MKL's vector math, and MKL picks its code path by the host CPU, so
+    ``u_64_3_seed42`` and ``annulus`` above differ in the last bit of a few values from what the same calls give on
+    another x86 host.  MKL's COMPATIBLE branch (MKL_CBWR, read when MKL starts) gives the same bits on every x86 host;
+    this section adds the reference's outputs on that branch as ``<key>_mkl_compatible`` to the existing files."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "run with MKL_CBWR=COMPATIBLE in the environment"
+    _install_shims()
+    import torch
+    from flooder import core as rcore
+    from flooder import synthetic_data_generators as sg
+
+    def add(fname, new):
+        path = os.path.join(OUT, fname)
+        z = dict(np.load(path))
+        z.update(new)
+        np.savez_compressed(path, **z)
+        print(fname, {k: v.shape for k, v in new.items()})
+
+    torch.manual_seed(42)
+    add("grid_vectors.npz", {"u_64_3_seed42_mkl_compatible": rcore.generate_uniform_weights(
+        64, 3, torch.device("cpu"), torch.float32).numpy()})
+    # non-Intel CPUs run MKL's vector sqrt on a path of their own whatever the branch setting: the annulus radii's one
+    # torch.sqrt call is recorded too (its input: the radius draws; its output on this branch), so that a test can hold
+    # that call to these bits and compare everything else bit for bit on any host
+    real_sqrt, sqrt_calls = torch.sqrt, []
+
+    def recording_sqrt(x, *a, **k):
+        y = real_sqrt(x, *a, **k)
+        sqrt_calls.append((x.clone(), y.clone()))
+        return y
+
+    torch.sqrt = recording_sqrt
+    try:
+        annulus = sg.generate_annulus_points_2d(300, torch.tensor([0.5, -0.25]), 1.5, 0.4, seed=13).numpy()
+    finally:
+        torch.sqrt = real_sqrt
+    assert len(sqrt_calls) == 1, len(sqrt_calls)
+    add("generators.npz", {
+        "annulus_mkl_compatible": annulus,
+        "annulus_sqrt_in_mkl_compatible": sqrt_calls[0][0].numpy(),
+        "annulus_sqrt_out_mkl_compatible": sqrt_calls[0][1].numpy(),
+        "torus_mkl_compatible": sg.generate_noisy_torus_points_3d(400, R=3.0, r=1.0, noise_std=0.02, seed=14).numpy()})
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["generators"]:
         make_generator_vectors()
+    elif sys.argv[1:] == ["mkl-compatible"]:
+        make_mkl_compatible_vectors()
     elif sys.argv[1:] == ["visualization"]:
         make_visualization_vectors()
     else:

@@ -1,11 +1,15 @@
 """Shared helpers of the parity tests."""
 import glob
 import os
+import subprocess
+import sys
+import textwrap
 
 import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Parity bar (BASELINE.json north_star): filtration values within 1e-5 relative in fp32.
 # The absolute floor covers the exact zeros (vertices: a landmark is its own nearest point) and the
@@ -114,3 +118,21 @@ def assert_tree_matches_kdtree(st, points, landmarks, points_per_edge, top, what
         if not lower:
             break
     return n
+
+
+def run_on_mkl_compatible_branch(code, tmp_path):
+    """Run ``code`` (which fills the dict ``out`` with numpy arrays) in a fresh CPU-only Python process started with
+    ``MKL_CBWR=COMPATIBLE``, and return ``out``.
+
+    torch sends contiguous float32 log / sin / cos to MKL's vector math, and MKL picks its code path by the host CPU:
+    the same seeded draws differ in the last bit of a few values from one x86 host to another.  MKL's COMPATIBLE branch
+    gives the same bits on every x86 host, and the ``*_mkl_compatible`` goldens are the reference's own outputs on it
+    (``oracle/make_goldens.py mkl-compatible``).  MKL reads the setting when it starts, hence the fresh process."""
+    path = tmp_path / "mkl_compatible_out.npz"
+    script = "import numpy as np\nout = {}\n" + textwrap.dedent(code) + f"\nnp.savez({str(path)!r}, **out)\n"
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", script]
+    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MKL_CBWR="COMPATIBLE"), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    z = np.load(path)
+    return {k: z[k] for k in z.files}

@@ -11,7 +11,7 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native, core
 from flooder_amd.simplex_tree import SimplexTree, delaunay_simplices
-from helpers import GOLDEN, e2e_cases, load_e2e, dict_values
+from helpers import GOLDEN, e2e_cases, load_e2e, dict_values, run_on_mkl_compatible_branch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -42,11 +42,15 @@ def test_generate_grid_matches_reference(n, dim):
         assert np.array_equal(f[k].numpy(), g[f"f_{n}_{dim}_{k}"])
 
 
-def test_uniform_weights_match_reference():
+def test_uniform_weights_match_reference(tmp_path):
     g = np.load(os.path.join(GOLDEN, "grid_vectors.npz"))
-    torch.manual_seed(42)
-    w = fa.generate_uniform_weights(64, 3, torch.device("cpu"), torch.float32)
-    assert np.array_equal(w.numpy(), g["u_64_3_seed42"])
+    out = run_on_mkl_compatible_branch("""
+        import torch
+        import flooder_amd as fa
+        torch.manual_seed(42)
+        out["w"] = fa.generate_uniform_weights(64, 3, torch.device("cpu"), torch.float32).numpy()
+    """, tmp_path)
+    assert np.array_equal(out["w"], g["u_64_3_seed42_mkl_compatible"])
 
 
 def test_landmarks_int_and_return_tree():

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import flood_oracle as fo
-from helpers import GOLDEN, e2e_cases, load_e2e, dict_values
+from helpers import GOLDEN, e2e_cases, load_e2e, dict_values, run_on_mkl_compatible_branch
 
 GRID_CASES = [(2, 1), (5, 2), (8, 3), (30, 3), (4, 4), (3, 6), (20, 2)]
 
@@ -23,10 +23,15 @@ def test_generate_grid_matches_reference(n, dim):
         assert np.array_equal(f[k], g[f"f_{n}_{dim}_{k}"])
 
 
-def test_uniform_weights_match_reference():
+def test_uniform_weights_match_reference(tmp_path):
     g = np.load(os.path.join(GOLDEN, "grid_vectors.npz"))
-    torch.manual_seed(42)
-    assert np.array_equal(fo.generate_uniform_weights(64, 3), g["u_64_3_seed42"])
+    out = run_on_mkl_compatible_branch("""
+        import torch
+        from oracle import flood_oracle as fo
+        torch.manual_seed(42)
+        out["w"] = fo.generate_uniform_weights(64, 3)
+    """, tmp_path)
+    assert np.array_equal(out["w"], g["u_64_3_seed42_mkl_compatible"])
     assert np.array_equal(fo.generate_uniform_weights(7, 0), g["u_7_0"])
 
 

@@ -7,8 +7,10 @@ import pytest
 import torch
 
 from flooder_amd import synthetic as sg
+from helpers import run_on_mkl_compatible_branch
 
-GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "generators.npz"))
+GOLD_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "generators.npz")
+GOLD = np.load(GOLD_PATH)
 
 
 def test_figure_eight_matches_reference_draws():
@@ -45,13 +47,41 @@ def test_swiss_cheese_properties():
         sg.generate_swiss_cheese_points(10, (0.0, 0.0), (1.0, 1.0, 1.0))
 
 
-def test_annulus_and_torus_match_reference_draws():
-    got = sg.generate_annulus_points_2d(300, torch.tensor([0.5, -0.25]), 1.5, 0.4, seed=13).numpy()
-    np.testing.assert_array_equal(got, GOLD["annulus"])
+def test_annulus_and_torus_match_reference_draws(tmp_path):
+    # The annulus radii are float32 square roots, and MKL's vector sqrt runs on a path of its own on non-Intel CPUs
+    # whatever the branch setting.  The one torch.sqrt call is therefore held to the bits the reference's call gave on
+    # the recorded branch: the call must receive exactly the reference's radius draws, and everything around it (draw
+    # order, angles, cos / sin, the arithmetic) is compared bit for bit on any host.
+    out = run_on_mkl_compatible_branch(f"""
+        import torch
+        from flooder_amd import synthetic as sg
+        g = np.load({GOLD_PATH!r})
+        sqrt_in = torch.from_numpy(g["annulus_sqrt_in_mkl_compatible"])
+        sqrt_out = torch.from_numpy(g["annulus_sqrt_out_mkl_compatible"])
+        real_sqrt, calls = torch.sqrt, []
+
+        def recorded_sqrt(x, *a, **k):
+            calls.append(x.clone())
+            if x.dtype == sqrt_in.dtype and x.shape == sqrt_in.shape and torch.equal(x.view(torch.int32), sqrt_in.view(torch.int32)):
+                return sqrt_out.clone()
+            return real_sqrt(x, *a, **k)
+
+        torch.sqrt = recorded_sqrt
+        try:
+            out["annulus"] = sg.generate_annulus_points_2d(300, torch.tensor([0.5, -0.25]), 1.5, 0.4, seed=13).numpy()
+        finally:
+            torch.sqrt = real_sqrt
+        out["sqrt_calls"] = np.array(len(calls), dtype=np.float64)
+        out["sqrt_in"] = calls[0].numpy()
+        out["torus"] = sg.generate_noisy_torus_points_3d(400, R=3.0, r=1.0, noise_std=0.02, seed=14).numpy()
+    """, tmp_path)
+    assert int(out["sqrt_calls"]) == 1
+    np.testing.assert_array_equal(out["sqrt_in"], GOLD["annulus_sqrt_in_mkl_compatible"])
+    got = out["annulus"]
+    np.testing.assert_array_equal(got, GOLD["annulus_mkl_compatible"])
     rad = np.linalg.norm(got - np.array([0.5, -0.25], dtype=np.float32), axis=1)
     assert rad.min() >= 1.1 - 1e-5 and rad.max() <= 1.5 + 1e-5
-    got = sg.generate_noisy_torus_points_3d(400, R=3.0, r=1.0, noise_std=0.02, seed=14).numpy()
-    np.testing.assert_array_equal(got, GOLD["torus"])
+    np.testing.assert_array_equal(out["torus"], GOLD["torus_mkl_compatible"])
     with pytest.raises(AssertionError):
         sg.generate_annulus_points_2d(10, torch.zeros(3))
     with pytest.raises(AssertionError):

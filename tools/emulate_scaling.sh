@@ -4,7 +4,7 @@
 # usage: tools/emulate_scaling.sh [workload]     SPECS="0/1 0/2 ..." overrides the list
 wl=${1:-cfg2}
 for spec in ${SPECS:-0/1 0/2 0/4 0/8 1/8 2/8 3/8 4/8 5/8 6/8 7/8}; do
-  timeout 300 python bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-cold --emulate-shard $spec $EXTRA 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-cold --emulate-shard $spec $EXTRA 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['per_rank'][0]
 print('$spec', 'step', d['ms_per_step'], 'index ready', d['ms_per_step_index_ready'], 'spans', r['spans'], 'ready', r['spans_index_ready'])"

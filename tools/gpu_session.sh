@@ -12,14 +12,14 @@ for s in $STEPS; do
   case $s in
     test)   timeout 900 python -m pytest tests -m gpu -x -q --timeout 200 --durations=12 > $OUT/pytest_gpu.txt 2>&1; tail -3 $OUT/pytest_gpu.txt ;;
     testall) timeout 1500 python -m pytest tests -m gpu -q --durations=12 > $OUT/pytest_gpu.txt 2>&1; tail -15 $OUT/pytest_gpu.txt ;;
-    bench)  timeout 600 python bench.py > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err; cut -c1-600 $OUT/bench_cfg2.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg2.json $OUT/profiles/r6_cfg2_bench.json ;;
-    bench3) timeout 900 python bench.py --workload cfg3 --cpu-sample 600 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; cut -c1-400 $OUT/bench_cfg3.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg3.json $OUT/profiles/r6_cfg3_bench.json ;;
-    bench4) timeout 1500 python bench.py --workload cfg4 --steps 5 --warmup 1 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err; cut -c1-1500 $OUT/bench_cfg4.json; tail -3 $OUT/bench_cfg4.err ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg4.json $OUT/profiles/r6_cfg4_bench.json ;;
-    bench5) timeout 1500 python bench.py --workload cfg5 --cpu-sample 300 --steps 20 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err; cut -c1-400 $OUT/bench_cfg5.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg5.json $OUT/profiles/r6_cfg5_bench.json ;;
-    bench2) timeout 600 python bench.py --gpus 2 --no-cpu-baseline > $OUT/bench_cfg2_2ranks.json 2> $OUT/bench_cfg2_2ranks.err; cut -c1-400 $OUT/bench_cfg2_2ranks.json; tail -3 $OUT/bench_cfg2_2ranks.err ;;
+    bench)  timeout 600 python bench.py --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err; cut -c1-600 $OUT/bench_cfg2.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg2.json $OUT/profiles/r6_cfg2_bench.json ;;
+    bench3) timeout 900 python bench.py --full --workload cfg3 --cpu-sample 600 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; cut -c1-400 $OUT/bench_cfg3.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg3.json $OUT/profiles/r6_cfg3_bench.json ;;
+    bench4) timeout 1500 python bench.py --full --workload cfg4 --steps 5 --warmup 1 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err; cut -c1-1500 $OUT/bench_cfg4.json; tail -3 $OUT/bench_cfg4.err ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg4.json $OUT/profiles/r6_cfg4_bench.json ;;
+    bench5) timeout 1500 python bench.py --full --workload cfg5 --cpu-sample 300 --steps 20 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err; cut -c1-400 $OUT/bench_cfg5.json ; mkdir -p $OUT/profiles; cp $OUT/bench_cfg5.json $OUT/profiles/r6_cfg5_bench.json ;;
+    bench2) timeout 600 python bench.py --full --gpus 2 --no-cpu-baseline > $OUT/bench_cfg2_2ranks.json 2> $OUT/bench_cfg2_2ranks.err; cut -c1-400 $OUT/bench_cfg2_2ranks.json; tail -3 $OUT/bench_cfg2_2ranks.err ;;
     ranks2:*) # ranks2:<workload>:<shard mode>  two ranks on the ONE GPU (gloo): functional check of bench.py --gpus N
             IFS=: read -r _ wl sh <<< "$s"
-            timeout 900 python bench.py --gpus 2 --workload $wl --shard $sh --no-cpu-baseline --steps 5 --warmup 1 > $OUT/ranks2_${wl}_${sh}.json 2> $OUT/ranks2_${wl}_${sh}.err
+            timeout 900 python bench.py --full --gpus 2 --workload $wl --shard $sh --no-cpu-baseline --steps 5 --warmup 1 > $OUT/ranks2_${wl}_${sh}.json 2> $OUT/ranks2_${wl}_${sh}.err
             python - $OUT/ranks2_${wl}_${sh}.json "$wl $sh" <<'PY'
 import json, sys
 try:
@@ -44,7 +44,7 @@ PY
             cat $OUT/phase_timers.txt; head -20 $OUT/chunk_times_1.txt; cat $OUT/bvh_phase_cfg3.txt ;;
     ab:*)   # ab:<workload>:<name>:<flags with , for space>   one bench line per variant
             IFS=: read -r _ wl name flags <<< "$s"
-            timeout 600 python bench.py --workload $wl --no-cpu-baseline --steps 20 --warmup 3 --no-cold ${flags//,/ } > $OUT/ab_${wl}_${name}.json 2> $OUT/ab_${wl}_${name}.err
+            timeout 600 python bench.py --full --workload $wl --no-cpu-baseline --steps 20 --warmup 3 --no-cold ${flags//,/ } > $OUT/ab_${wl}_${name}.json 2> $OUT/ab_${wl}_${name}.err
             python - "$OUT/ab_${wl}_${name}.json" "$wl $name" <<'PY'
 import json, sys
 try:
@@ -59,7 +59,7 @@ PY
     var:*)  # var:<lib in gpurun_in/ without .so | product>:<workload>:<name>[:<flags with , for space>]  bench line of a library variant
             IFS=: read -r _ lib wl name flags <<< "$s"
             if [ "$lib" != product ]; then export FLOODER_HIP_LIB=$R/gpurun_in/$lib.so; fi
-            timeout 600 python bench.py --workload $wl --no-cpu-baseline --steps 20 --warmup 3 --no-cold ${flags//,/ } > $OUT/var_${wl}_${name}.json 2> $OUT/var_${wl}_${name}.err
+            timeout 600 python bench.py --full --workload $wl --no-cpu-baseline --steps 20 --warmup 3 --no-cold ${flags//,/ } > $OUT/var_${wl}_${name}.json 2> $OUT/var_${wl}_${name}.err
             unset FLOODER_HIP_LIB
             python - "$OUT/var_${wl}_${name}.json" "$wl $name" <<'PY'
 import json, sys
@@ -73,7 +73,7 @@ PY
     lds:*)  # LDS counters of the sweep kernels: bank conflicts, LDS-array cycles
             wl=${s#lds:}
             ( cd /tmp && export TMPDIR=/tmp
-              timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_lds_$wl -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/lds_$wl.json 2> $OUT/lds_$wl.err )
+              timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_lds_$wl -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/lds_$wl.json 2> $OUT/lds_$wl.err )
             python - $OUT $wl > $OUT/lds_summary_$wl.txt <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: [0.0, 0])
@@ -94,7 +94,7 @@ PY
     pytest:*) k="${s#pytest:}"; timeout 1200 python -m pytest tests -m gpu -x -q -k "${k//,/ }" > $OUT/pytest_k.txt 2>&1; tail -8 $OUT/pytest_k.txt ;;
     trace:*) # per-dispatch durations of the finish passes (probe, top, rest) from a kernel trace
             wl=${s#trace:}
-            ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$wl -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace_$wl.json 2> $OUT/trace_$wl.err )
+            ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$wl -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace_$wl.json 2> $OUT/trace_$wl.err )
             python - $OUT/trace_$wl <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
@@ -113,7 +113,7 @@ PY
             rm -rf $OUT/trace_$wl ;;
     timeline:*) # every dispatch of ONE step (back-to-back steps, the last but one): offset, duration, gap to the previous end
             wl=${s#timeline:}
-            ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl_$wl -- python3 $R/bench.py --workload $wl --steps 12 --warmup 3 --no-cpu-baseline --no-cold --no-e2e > $OUT/tl_$wl.json 2> $OUT/tl_$wl.err )
+            ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl_$wl -- python3 $R/bench.py --full --workload $wl --steps 12 --warmup 3 --no-cpu-baseline --no-cold --no-e2e > $OUT/tl_$wl.json 2> $OUT/tl_$wl.err )
             python - $OUT/tl_$wl > $OUT/timeline_$wl.txt <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
@@ -163,8 +163,8 @@ PY
     icache:*) # instruction-cache counters of the sweep kernels (is the 66-83 KB kernel thrashing the 64 KB cache two CUs share?)
             wl=${s#icache:}
             ( cd /tmp && export TMPDIR=/tmp
-              timeout 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc_icache_$wl -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/icache_$wl.json 2> $OUT/icache_$wl.err
-              timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d $OUT/pmc_inst_$wl -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/inst_$wl.json 2>> $OUT/icache_$wl.err )
+              timeout 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc_icache_$wl -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/icache_$wl.json 2> $OUT/icache_$wl.err
+              timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d $OUT/pmc_inst_$wl -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-cold > $OUT/inst_$wl.json 2>> $OUT/icache_$wl.err )
             python - $OUT $wl > $OUT/icache_summary_$wl.txt <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: [0.0, 0])
