@@ -10,6 +10,7 @@ from .core import (flood_complex, generate_landmarks, generate_grid, generate_un
                    index_from_host, forget_index)
 from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
+from .grad import FloodFiltration, flood_filtration
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -21,6 +22,8 @@ __version__ = "0.1"
 
 __all__ = [
     "flood_complex",
+    "flood_filtration",
+    "FloodFiltration",
     "generate_landmarks",
     "generate_grid",
     "generate_uniform_weights",

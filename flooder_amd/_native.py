@@ -75,6 +75,13 @@ class FpsBatched(_Block):
         p launches_out""")
 
 
+class WitnessSearch(_Block):
+    """``flooder_witness_search_t``: the exact witness point of every distinct face (flooder_amd.grad)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p order; p verts; p weights;
+        i32 R; i32 reserved; i64 n_simplices; i64 n_queries; p q_simplex; p q_row; p q_d2; p out_point; p not_found""")
+
+
 _lib = None
 _load_error: Exception | None = None
 _load_missing = False  # the last failure was "file not found" (worth another look after a build)
@@ -158,6 +165,11 @@ SIGNATURES = {
     "flooder_sorted_faces": (c_int, [ctypes.POINTER(SortedSweep), c_void_p]),
     "flooder_sorted_minima": (c_int, [ctypes.POINTER(SortedSweep), c_void_p]),
     "flooder_fps_batched": (c_int, [ctypes.POINTER(FpsBatched), c_void_p]),
+    # witnesses of the filtration values and the scatter of their gradients (flooder_amd.grad)
+    "flooder_face_argmax_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p]),
+    "flooder_witness_search": (c_int, [ctypes.POINTER(WitnessSearch), c_void_p]),
+    "flooder_segment_sum_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -1,0 +1,508 @@
+"""Differentiable Flood filtration: exact witnesses of every filtration value and their gradients.
+
+For a simplex tau with landmark vertices L_0..L_k the Flood filtration value is
+
+    f(tau) = |p* - x*|,   p* = sum_i w*_i L_i   (the sample on tau whose nearest-point distance is largest)
+                          x* = points[j*]      (the point of the cloud nearest to p*)
+
+so, for f > 0 and u = (p* - x*) / f,  df/dpoints[j*] = -u  and  df/dL_i = w*_i u  (0 for f = 0).  ``flood_filtration``
+runs the sweep of ``flood_complex`` and recovers (w*, j*) exactly: on ROCm tensors from the per-sample minimum d2 bits
+of the unfused sweep (``csrc/flood_grad.hip``: face argmax, witness search in the box tree of the cloud), on CPU tensors
+from the indices of the kd-tree query.  The values themselves are the ones ``flood_complex`` returns.  See DESIGN.md,
+"Witnesses and gradients".
+"""
+
+from __future__ import annotations
+
+import ctypes
+import itertools
+from numbers import Integral
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _native
+from . import core
+from .persistence import persistence_pairs_simplices
+from .simplex_tree import SimplexTree, delaunay_cells
+
+__all__ = ["FloodFiltration", "flood_filtration"]
+
+
+class FloodFiltration:
+    """Result of ``flood_filtration``: per dimension d (lists indexed by d)
+
+    ``simplices[d]``        (n_d, d+1) int64 CPU: the rows of ``tree.simplices_of_dimension(d)`` (vertex ids ascending)
+    ``values[d]``           (n_d,) on the points' device and dtype, differentiable w.r.t. points and landmarks
+    ``witness_point[d]``    (n_d,) int64: j*, the row of ``points`` nearest to the witness sample (-1: none)
+    ``witness_weights[d]``  (n_d, d+1): barycentric weights w* of the witness sample over the simplex's OWN vertices
+    ``tree``                the ``flooder_amd.SimplexTree`` with the (detached) values
+    """
+
+    def __init__(self, tree: SimplexTree, simplices, values, witness_point, witness_weights, landmark_ids,
+                 faces_not_found: int = 0):
+        self.tree = tree
+        self.simplices: List[torch.Tensor] = simplices
+        self.values: List[torch.Tensor] = values
+        self.witness_point: List[torch.Tensor] = witness_point
+        self.witness_weights: List[torch.Tensor] = witness_weights
+        self.landmark_ids = landmark_ids   # int64 rows of `points` the landmarks were taken from (integer landmarks)
+        self.faces_not_found = faces_not_found   # faces the device witness search found no point for (0; else it raises)
+
+    def to_dict(self) -> Dict[tuple, float]:
+        """``{simplex: value}``, what ``flood_complex`` returns for the same arguments."""
+        return self.tree.to_dict()
+
+    def diagrams(self, min_persistence: float = 0.0, persistence_dim_max: bool = False) -> Dict[int, torch.Tensor]:
+        """``{dim: (m, 2) tensor}`` of persistence intervals, rows sorted as ``tree.persistence_intervals_in_dimension``
+        sorts them; births and finite deaths are entries of ``values`` (differentiable), essential classes die at inf."""
+        top = self.tree.dimension()
+        if top >= len(self.values):
+            raise ValueError(f"diagrams() needs every dimension of the complex: the filtration covers dimensions "
+                             f"0..{len(self.values) - 1}, the complex has dimension {top} (pass max_dimension={top})")
+        pairs = persistence_pairs_simplices(self.tree, min_persistence=min_persistence,
+                                            persistence_dim_max=persistence_dim_max)
+        flat = torch.cat(self.values)
+        offs = np.concatenate([[0], np.cumsum([v.shape[0] for v in self.values])]).astype(np.int64)
+        inf = flat.new_tensor(float("inf"))
+        out: Dict[int, torch.Tensor] = {}
+        for dim, pr in pairs.items():
+            birth = flat[torch.as_tensor(offs[pr[:, 0]] + pr[:, 1], device=flat.device)]
+            ess = pr[:, 2] < 0
+            dpos = np.where(ess, 0, offs[np.maximum(pr[:, 2], 0)] + pr[:, 3])
+            death = torch.where(torch.as_tensor(ess, device=flat.device), inf,
+                                flat[torch.as_tensor(dpos, device=flat.device)])
+            iv = torch.stack((birth, death), dim=1)
+            key = iv.detach().cpu().double().numpy()
+            order = np.lexsort((key[:, 1], key[:, 0]))
+            out[dim] = iv[torch.as_tensor(order, device=iv.device)]
+        return out
+
+
+def _check_args(points: torch.Tensor, method: Optional[str]):
+    if points.dim() != 2 or points.shape[0] == 0:
+        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {tuple(points.shape)}")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"dtype ({points.dtype}) not supported")
+    if method == "ball":
+        raise ValueError("flood_filtration: method 'ball' has no exact witnesses (use 'cell' or 'bvh')")
+    if method not in (None, "auto", "cell", "bvh"):
+        raise ValueError(f"method must be 'cell' or 'bvh', got {method!r}")
+    dim = points.shape[1]
+    if points.is_cuda:
+        if points.dtype is torch.float64:
+            raise TypeError("flood_filtration: ROCm float64 tensors are not supported (pass float32)")
+        if not 2 <= dim <= 8:
+            raise ValueError("flood_filtration: ROCm tensors need ambient dimension 2 to 8")
+        if method in (None, "auto"):
+            method = "cell" if dim in (2, 3) and points.shape[0] < (1 << 28) - 64 else "bvh"
+        if method == "cell" and dim not in (2, 3):
+            raise ValueError("method 'cell' supports ambient dimension 2 and 3 only")
+    elif points.device.type != "cpu":
+        raise RuntimeError("Device not supported.")
+    return method
+
+
+def _check_index(index: "core.PointIndex", points: torch.Tensor) -> None:
+    """The checks ``flood_complex(index=...)`` makes: a PointIndex of these very points, not written to since."""
+    if not points.is_cuda:
+        raise ValueError("index= applies to ROCm tensors")
+    if (not isinstance(index, core.PointIndex) or (index.n, index.dim) != tuple(points.shape)
+            or index.pts.device != points.device):
+        raise ValueError("index= is not a PointIndex of these points (shape or device differ)")
+    src = getattr(index, "source", None)
+    ver = core._tensor_version(points)
+    if src is not None and src[0] == points.data_ptr() and src[1] is not None and ver is not None and src[1] != ver:
+        raise ValueError("index= was built from an earlier state of `points` (the tensor has been modified in "
+                         "place since): rebuild the PointIndex")
+
+
+def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[int] = None, points_per_edge: int = 30,
+                     num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, method: Optional[str] = None,
+                     index: Optional["core.PointIndex"] = None) -> FloodFiltration:
+    """Flood filtration with exact witnesses: the values of ``flood_complex(points, landmarks, max_dimension,
+    points_per_edge, num_rand, start_idx=start_idx, method=method, index=index)``, differentiable w.r.t. ``points`` and
+    ``landmarks``.  Integer ``landmarks``: farthest-point sampling as ``flood_complex`` does it, the landmarks are
+    ``points.index_select(0, idx)`` (their gradient flows into ``points``).  CPU tensors (float32, float64) and ROCm
+    float32 in ambient dimension 2 to 8, methods ``"cell"`` / ``"bvh"``."""
+    method = _check_args(points, method)
+    if index is not None:
+        _check_index(index, points)
+    dim = points.shape[1]
+    if max_dimension is None:
+        max_dimension = dim
+    landmark_ids = None
+    if isinstance(landmarks, Integral):
+        n_l = int(landmarks)
+        if n_l <= 0:
+            raise RuntimeError(f"Number of landmarks ({n_l}) must be positive")
+        if start_idx is None:
+            start_idx = int(torch.randint(points.shape[0], (1,)).item())
+        if not (0 <= start_idx < points.shape[0]):
+            raise RuntimeError(f"start_idx ({start_idx}) out of range for {points.shape[0]} points")
+        with torch.no_grad():
+            if points.is_cuda and index is None:
+                index = core.PointIndex(points.detach().to(torch.float32))
+            landmark_ids = core.fps_indices(points.detach(), min(n_l, points.shape[0]), start_idx, index=index)
+        landmarks = points.index_select(0, landmark_ids)
+    if landmarks.device != points.device:
+        raise RuntimeError(f"landmarks.device ({landmarks.device}) != points.device ({points.device})")
+    if landmarks.dtype != points.dtype:
+        raise RuntimeError(f"landmarks.dtype ({landmarks.dtype}) != points.dtype ({points.dtype})")
+
+    with torch.no_grad():
+        pts = points.detach()
+        lms = landmarks.detach()
+        lm_np = lms.cpu().numpy()
+        tree = SimplexTree.from_cells(delaunay_cells(lm_np), lm_np.shape[0], eager=max_dimension, trusted=True)
+        simplices = [tree.simplices_of_dimension(d) for d in range(max_dimension + 1)]
+        n_dims = max_dimension + 1
+        own_val = [np.full(s.shape[0], np.nan) for s in simplices]
+        own_pt = [np.full(s.shape[0], -1, dtype=np.int64) for s in simplices]
+        own_w = [np.zeros((s.shape[0], d + 1)) for d, s in enumerate(simplices)]
+        not_found = 0
+        if points.is_cuda:
+            not_found = _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index,
+                                   own_val, own_pt, own_w)
+        else:
+            _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w)
+        for d in range(n_dims):
+            vals = tree.filtrations_of_dimension(d)
+            if vals.shape[0]:
+                vals[:] = own_val[d]
+        tree._persistence = None
+        tree.make_filtration_non_decreasing()
+        wp, ww = _inherit(tree, own_val, own_pt, own_w, n_dims)
+
+    dev, dt = points.device, points.dtype
+    vals_t = [torch.as_tensor(tree.filtrations_of_dimension(d), dtype=dt).to(dev) for d in range(n_dims)]
+    F = FloodFiltration(tree, [torch.as_tensor(s) for s in simplices], None,
+                        [torch.as_tensor(p).to(dev) for p in wp], [torch.as_tensor(w, dtype=dt).to(dev) for w in ww],
+                        landmark_ids, not_found)
+    # (the context keeps the witness tensors, not F: F holds the outputs of this very node - a cycle through autograd's
+    # C++ graph that the garbage collector cannot break)
+    flat = _FloodValues.apply(points, landmarks, torch.cat(vals_t), (F.simplices, F.witness_point, F.witness_weights))
+    F.values = list(torch.split(flat, [v.shape[0] for v in vals_t]))
+    return F
+
+
+# ---------------------------------------------------------------------------------------------------- the sweeps
+def _table_rows(tree: SimplexTree, d: int, order_np: np.ndarray, simp_h: np.ndarray, v_idx: np.ndarray) -> np.ndarray:
+    """(S, nf) rows of the dimension k-1 table holding face j (vertex positions ``v_idx[j]``) of queue simplex s."""
+    nf, k = v_idx.shape
+    top = tree._cells is not None and tree._cells.shape[1] == d + 1
+    index = tree.cell_face_index(k - 1) if top else None
+    if index is not None:
+        combos = list(itertools.combinations(range(d + 1), k))
+        pick = [combos.index(tuple(int(x) for x in row)) for row in v_idx]
+        return index[order_np][:, pick]
+    if k == d + 1 and nf == 1:
+        return order_np.reshape(-1, 1)
+    rows = tree._locate(k - 1, simp_h[:, v_idx].reshape(-1, k))
+    return rows.reshape(-1, nf)
+
+
+def _face_groups(v_idx_np):
+    """[(first column of the group in the face table, v_idx)] of a grid table; None = random samples (one face)."""
+    if v_idx_np is None:
+        return None
+    out, col = [], 0
+    for v_idx in v_idx_np:
+        out.append((col, v_idx))
+        col += v_idx.shape[0]
+    return out
+
+
+def _pick_copies(key: torch.Tensor, rows: torch.Tensor, n_rows: int):
+    """Per table row: among its copies (entries of ``rows``), the largest d2 bits (high word of ``key``), then the
+    smallest flat (queue position, face) index - the smallest queue position, a simplex has a face once; inside the
+    copy, ``key`` already names its smallest sample row.  Returns (covered rows, winning flat positions)."""
+    dev = key.device
+    bits = key >> 32
+    bmax = torch.full((n_rows,), -1, dtype=torch.int64, device=dev)
+    bmax.scatter_reduce_(0, rows, bits, reduce="amax")
+    pos = torch.arange(key.shape[0], device=dev, dtype=torch.int64)
+    big = torch.iinfo(torch.int64).max
+    cand = torch.where(bits == bmax[rows], pos, torch.full_like(pos, big))
+    win = torch.full((n_rows,), big, dtype=torch.int64, device=dev)
+    win.scatter_reduce_(0, rows, cand, reduce="amin")
+    covered = torch.nonzero(win != big).reshape(-1)
+    return covered, win[covered]
+
+
+def _grad_face_rows(plan: "core.SamplePlan"):
+    """(face CSR in swept columns (``rows_perm``) with every face's segment ascending - a face that spans the row is read
+    coalesced -, the weight-table row of every swept column), kept on the plan: a grid plan is cached per
+    points_per_edge."""
+    got = getattr(plan, "_grad_rows", None)
+    if got is None:
+        ptr = plan.faces.ptr.cpu().numpy()
+        rp = plan.rows_perm.cpu().numpy().copy()
+        for f in range(plan.faces.n_faces):
+            rp[ptr[f]:ptr[f + 1]].sort()
+        dev = plan.rows_perm.device
+        got = plan._grad_rows = (torch.as_tensor(rp, device=dev),
+                                 torch.as_tensor(np.asarray(plan._perm, dtype=np.int32), device=dev))
+    return got
+
+
+def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index, own_val, own_pt, own_w):
+    lib = _native.load()
+    dev = pts.device
+    torch.cuda.set_device(dev)
+    pts32 = pts.to(torch.float32).contiguous()
+    if index is None:
+        index = core.PointIndex(pts32)
+    box = index.box.cpu()
+    dim = pts.shape[1]
+    axis = int(torch.argmax(box[8:8 + dim] - box[:dim]).item())
+    lm_np = lms.to(torch.float32).cpu().numpy()
+    st = _native.current_stream_ptr(dev)
+    not_found = torch.zeros(1, dtype=torch.int32, device=dev)
+    for d in range(max_dimension + 1):
+        if num_rand is None and d < max_dimension:
+            continue
+        S = simplices[d].shape[0]
+        if S == 0:
+            continue
+        v_np = lm_np[simplices[d]]
+        order_np = np.argsort(v_np[:, :, axis].sum(axis=1), kind="stable")
+        simp_h = simplices[d][order_np]
+        sv = torch.as_tensor(np.ascontiguousarray(v_np[order_np]), device=dev)
+        if num_rand is None:
+            weights, _, _, faces, plan, v_idx_np = core._grid_tables(points_per_edge, max_dimension, dev, torch.float32)
+        else:
+            weights = core.generate_uniform_weights(num_rand, d, dev, torch.float32)
+            faces = core._FaceTable(None, weights.shape[0], dev)
+            plan, v_idx_np = core.SamplePlan(weights, faces), None
+        R = weights.shape[0]
+        got = []
+        sweep = core._sweep_dimension_cell if method == "cell" else core._sweep_dimension_bvh
+        face_dev, _ = sweep(index, sv, weights, faces, got.append, plan=plan)
+        d2 = got[0]
+        F = faces.n_faces
+        keys = torch.empty((S, F), dtype=torch.int64, device=dev)
+        face_rows, row_id = _grad_face_rows(plan)
+        _native.check(lib.flooder_face_argmax_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr), _native.ptr(face_rows),
+                                                  _native.ptr(row_id), F, _native.ptr(keys), st),
+                      "flooder_face_argmax_f32")
+        groups = _face_groups(v_idx_np) or [(0, np.arange(d + 1, dtype=np.int64).reshape(1, -1))]
+        for col, v_idx in groups:
+            nf, k = v_idx.shape
+            rows_np = _table_rows(tree, d, order_np, simp_h, v_idx)
+            n_rows = simplices[k - 1].shape[0]
+            rows = torch.as_tensor(np.ascontiguousarray(rows_np, dtype=np.int64), device=dev).reshape(-1)
+            key = keys[:, col:col + nf].reshape(-1)
+            val = face_dev[:, col:col + nf].reshape(-1)
+            ok = rows >= 0
+            if not bool(ok.all()):
+                sel = torch.nonzero(ok).reshape(-1)
+                rows, key, val = rows[sel], key[sel], val[sel]
+            else:
+                sel = None
+            covered, win = _pick_copies(key, rows, n_rows)
+            flat = win if sel is None else sel[win]         # position in the (S, nf) block
+            s_q = torch.div(flat, nf, rounding_mode="floor")
+            j_q = flat - s_q * nf
+            kw = key[win]
+            r_w = 0xFFFFFFFF - (kw & 0xFFFFFFFF)              # the winning row of the weight table
+            ok_r = r_w < R
+            r_q = torch.where(ok_r, plan.inv[torch.where(ok_r, r_w, 0)], -1)   # ... and its swept column (-1: none)
+            bits = (kw >> 32)
+            n_q = int(covered.shape[0])
+            out_pt = torch.empty(n_q, dtype=torch.int64, device=dev)
+            q_s = s_q.to(torch.int32).contiguous()
+            q_r = r_q.to(torch.int32).contiguous()
+            q_b = bits.to(torch.int32).contiguous()
+            blk = _native.WitnessSearch(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=d + 1, nodes=index.nodes,
+                                        order=index.order32, verts=sv, weights=plan.w_perm, R=R, n_simplices=S, n_queries=n_q,
+                                        q_simplex=q_s, q_row=q_r, q_d2=q_b, out_point=out_pt, not_found=not_found)
+            _native.check(lib.flooder_witness_search(ctypes.byref(blk), st), "flooder_witness_search")
+            cov = covered.cpu().numpy()
+            own_val[k - 1][cov] = val[win].cpu().numpy().astype(np.float64)
+            own_pt[k - 1][cov] = out_pt.cpu().numpy()
+            w_full = plan.w_perm[r_q.clamp(min=0)]           # (n_q, d+1) over the swept simplex's vertices
+            vi = torch.as_tensor(v_idx, device=dev)[j_q]     # (n_q, k) the face's vertex positions
+            own_w[k - 1][cov] = torch.gather(w_full, 1, vi).cpu().numpy().astype(np.float64)
+    missing = int(not_found.item())
+    if missing:
+        raise RuntimeError(f"flood_filtration: the witness search found no point at the exact distance for "
+                           f"{missing} faces")
+    return missing
+
+
+def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w):
+    from scipy.spatial import KDTree
+
+    kdtree = KDTree(np.asarray(pts))
+    axis = int(torch.argmax(pts.max(dim=0).values - pts.min(dim=0).values).item())
+    dtype = pts.dtype
+    for d in range(max_dimension + 1):
+        if num_rand is None and d < max_dimension:
+            continue
+        S = simplices[d].shape[0]
+        if S == 0:
+            continue
+        # the queue of flood_complex's CPU branch (same samples, bit for bit)
+        sv = lms[torch.as_tensor(simplices[d])]
+        centers, _ = core._ball_prep(sv, d)
+        splx_idx = torch.argsort(centers[:, axis])
+        sv = sv[splx_idx]
+        order_np = splx_idx.numpy()
+        simp_h = simplices[d][order_np]
+        if num_rand is None:
+            weights, _, _, faces, _, v_idx_np = core._grid_tables(points_per_edge, max_dimension, pts.device, dtype)
+        else:
+            weights = core.generate_uniform_weights(num_rand, d, pts.device, dtype)
+            faces = core._FaceTable(None, weights.shape[0], pts.device)
+            v_idx_np = None
+        samples = weights.unsqueeze(0) @ sv
+        dist, idx = kdtree.query(np.asarray(samples), workers=core.CPU_WORKERS)
+        fptr = faces.ptr.numpy()
+        frows = faces.rows.numpy()
+        w_np = weights.numpy()
+        groups = _face_groups(v_idx_np) or [(0, np.arange(d + 1, dtype=np.int64).reshape(1, -1))]
+        for col, v_idx in groups:
+            nf, k = v_idx.shape
+            rows = _table_rows(tree, d, order_np, simp_h, v_idx).reshape(-1)
+            arg = np.empty((S, nf), dtype=np.int64)
+            val = np.empty((S, nf))
+            for j in range(nf):
+                fr = frows[fptr[col + j]:fptr[col + j + 1]]
+                a = np.argmax(dist[:, fr], axis=1)           # first maximum: the smallest sample row
+                arg[:, j] = fr[a]
+                val[:, j] = dist[np.arange(S), fr[a]]
+            ok = rows >= 0
+            pos = np.nonzero(ok)[0]
+            # per table row: the largest value, then the smallest (queue position, face) copy
+            order = np.lexsort((pos, -val.reshape(-1)[pos], rows[pos]))
+            srt = pos[order]
+            first = np.ones(srt.shape[0], dtype=bool)
+            first[1:] = rows[srt[1:]] != rows[srt[:-1]]
+            win = srt[first]
+            s_q, j_q = win // nf, win % nf
+            r_q = arg.reshape(-1)[win]
+            tr = rows[win]
+            own_val[k - 1][tr] = val.reshape(-1)[win]
+            own_pt[k - 1][tr] = idx[s_q, r_q]
+            own_w[k - 1][tr] = w_np[r_q[:, None], v_idx[j_q]]
+
+
+def _facet_rows(tree: SimplexTree, d: int) -> np.ndarray:
+    fr = tree._facet_rows(d)
+    if fr is not None:
+        return fr
+    rows = tree.simplices_of_dimension(d)
+    return np.stack([tree._locate(d - 1, np.delete(rows, j, axis=1)) for j in range(d + 1)], axis=1)
+
+
+def _inherit(tree: SimplexTree, own_val, own_pt, own_w, n_dims: int):
+    """Witnesses of the final (monotone) values: a simplex that ``make_filtration_non_decreasing`` raised to a facet's
+    value takes that facet's witness (the first facet, omitting vertex j, that holds the value), its weights
+    re-expressed over the simplex's own vertices (0 at the omitted one)."""
+    wp = [p.copy() for p in own_pt]
+    ww = [w.copy() for w in own_w]
+    for d in range(1, n_dims):
+        n = wp[d].shape[0]
+        if n == 0 or wp[d - 1].shape[0] == 0:
+            continue
+        fin = tree.filtrations_of_dimension(d)
+        own = own_val[d]
+        raised = np.isnan(own) | (fin > own)
+        if not raised.any():
+            continue
+        sel = np.nonzero(raised)[0]
+        facets = _facet_rows(tree, d)[sel]
+        fv = tree.filtrations_of_dimension(d - 1)[np.maximum(facets, 0)]
+        hit = (facets >= 0) & (fv == fin[sel, None])
+        has = hit.any(axis=1)
+        j = np.argmax(hit, axis=1)
+        sel, j = sel[has], j[has]
+        src = facets[np.nonzero(has)[0], j]
+        wp[d][sel] = wp[d - 1][src]
+        w = np.zeros((sel.shape[0], d + 1))
+        for m in range(d + 1):
+            take = np.nonzero(j != m)[0]
+            col = np.where(m < j[take], m, m - 1)
+            w[take, m] = ww[d - 1][src[take], col]
+        ww[d][sel] = w
+    return wp, ww
+
+
+# ---------------------------------------------------------------------------------------------------- autograd
+class _FloodValues(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, landmarks, values, witnesses):
+        ctx.witnesses = witnesses
+        ctx.save_for_backward(points, landmarks)
+        return values.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        points, landmarks = ctx.saved_tensors
+        gp, gl = witness_backward(*ctx.witnesses, points.detach(), landmarks.detach(), grad)
+        return (gp if ctx.needs_input_grad[0] else None), (gl if ctx.needs_input_grad[1] else None), None, None
+
+
+def witness_backward(simplices, witness_point, witness_weights, points: torch.Tensor, landmarks: torch.Tensor,
+                     grad: torch.Tensor):
+    """(grad_points (n, dim), grad_landmarks (L, dim)) of sum(grad * values), in the input dtype.  ROCm tensors: the
+    contributions are summed per target row in a fixed order (``flooder_segment_sum_f32``): bit-identical run to run."""
+    dev, dt = points.device, points.dtype
+    dim = points.shape[1]
+    tg_p, vl_p, tg_l, vl_l = [], [], [], []
+    off = 0
+    for d, simp in enumerate(simplices):
+        n = simp.shape[0]
+        g = grad[off:off + n].to(dt)
+        off += n
+        if n == 0:
+            continue
+        jp = witness_point[d]
+        keep = torch.nonzero((g != 0) & (jp >= 0)).reshape(-1)
+        if keep.numel() == 0:
+            continue
+        g = g[keep]
+        jp = jp[keep]
+        V = simp.to(dev)[keep]                                 # (m, d+1) landmark ids
+        W = witness_weights[d][keep]                           # (m, d+1)
+        p = (W.unsqueeze(2) * landmarks[V]).sum(dim=1)         # p* (m, dim)
+        diff = p - points[jp]
+        f = diff.norm(dim=1, keepdim=True)
+        u = torch.where(f > 0, diff / torch.where(f > 0, f, torch.ones_like(f)), torch.zeros_like(diff))
+        gu = g.unsqueeze(1) * u
+        tg_p.append(jp)
+        vl_p.append(-gu)
+        nz = W != 0
+        rows_i, cols_i = torch.nonzero(nz, as_tuple=True)
+        tg_l.append(V[rows_i, cols_i])
+        vl_l.append(W[rows_i, cols_i].unsqueeze(1) * gu[rows_i])
+    gp = _scatter_rows(tg_p, vl_p, points.shape[0], dim, dev, dt)
+    gl = _scatter_rows(tg_l, vl_l, landmarks.shape[0], dim, dev, dt)
+    return gp, gl
+
+
+def _scatter_rows(targets, vals, n_out: int, dim: int, dev, dt) -> torch.Tensor:
+    out = torch.zeros((n_out, dim), dtype=dt, device=dev)
+    if not targets:
+        return out
+    tg = torch.cat(targets)
+    vl = torch.cat(vals).contiguous()
+    if tg.numel() == 0:
+        return out
+    if dev.type != "cuda":
+        out.index_add_(0, tg, vl)    # (sequential on the host: deterministic)
+        return out
+    lib = _native.load()
+    srt, order = torch.sort(tg, stable=True)
+    uniq, counts = torch.unique_consecutive(srt, return_counts=True)
+    seg_ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=seg_ptr[1:])
+    vl32 = vl.to(torch.float32).contiguous()
+    _native.check(lib.flooder_segment_sum_f32(_native.ptr(vl32), dim, _native.ptr(order.contiguous()), _native.ptr(seg_ptr),
+                                              _native.ptr(uniq.contiguous()), uniq.shape[0], _native.ptr(out),
+                                              _native.current_stream_ptr(dev)), "flooder_segment_sum_f32")
+    return out

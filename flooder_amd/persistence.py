@@ -130,6 +130,39 @@ def _filtration_order_native(st, top: int, counts):
     return dims, filt, bptr, bidx[:nb], order
 
 
+def persistence_pairs_simplices(st, min_persistence: float = 0.0,
+                                persistence_dim_max: bool = False) -> Dict[int, np.ndarray]:
+    """The intervals of ``persistence_pairs`` as simplices: ``{dim: (m, 4) int64}`` rows ``(birth dim, birth row,
+    death dim, death row)`` - rows of ``st.simplices_of_dimension`` - in the order ``persistence_pairs`` lists the
+    intervals; an essential class has death ``(-1, -1)``."""
+    st._flush()
+    st._materialise_all()
+    dims, filt, bptr, bidx, order = filtration_order(st)
+    if dims.size == 0:
+        return {}
+    pair = reduce_pairs(dims, bptr, bidx)
+    top = int(dims.max())
+    counts = [st._rows[d].shape[0] if d in st._rows else 0 for d in range(top + 1)]
+    offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    gid = np.asarray(order, dtype=np.int64)                 # position in filtration order -> offs[d] + row
+    sdim = np.searchsorted(offs, gid, side="right") - 1
+    srow = gid - offs[sdim]
+    idx = np.arange(dims.shape[0])
+    births = (pair == -1) | (pair > idx)
+    death = np.where(pair == -1, np.inf, filt[np.where(pair >= 0, pair, 0)])
+    keep = births & (death - filt > min_persistence)
+    if not persistence_dim_max:
+        keep &= dims != top
+    out: Dict[int, np.ndarray] = {}
+    for d in np.unique(dims[keep]).tolist():
+        sel = np.nonzero(keep & (dims == d))[0]
+        p = pair[sel]
+        dd = np.where(p >= 0, sdim[np.maximum(p, 0)], -1)
+        dr = np.where(p >= 0, srow[np.maximum(p, 0)], -1)
+        out[int(d)] = np.stack((sdim[sel], srow[sel], dd, dr), axis=1).astype(np.int64)
+    return out
+
+
 def reduce_pairs(dims: np.ndarray, bptr: np.ndarray, bidx: np.ndarray) -> np.ndarray:
     lib = _host_lib()
     n = dims.shape[0]

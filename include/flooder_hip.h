@@ -696,6 +696,48 @@ typedef struct flooder_fps_batched_s {    /* flooder_fps_batched_f32 */
 } flooder_fps_batched_t;
 int flooder_fps_batched(const flooder_fps_batched_t* p, void* stream);
 
+/*
+ * ---- Witnesses of the filtration values (csrc/flood_grad.hip; flooder_amd.grad) ---------------------------------
+ * flooder_face_argmax_f32: over the (n_simplices x R) minimum d2 bits of an unfused sweep and the face CSR (face_rows:
+ * columns of d2, each face's segment ascending), out_key[s * n_faces + f] = (max d2 bits << 32) | (0xffffffff - r)
+ * with r the smallest sample row attaining it: r = row_id[c] for column c (the caller's weight-table row of a swept
+ * column; NULL: r = c).
+ * flooder_witness_search: per query q, p* = sum_j weights[q_row[q], j] * verts[q_simplex[q], j, :] (fma in vertex
+ * order, as the sweeps), then out_point[q] = the smallest original id (order[row]) of the points at squared distance
+ * with exactly the bits q_d2[q] (t0*t0, then fma(t, t, d2) over the remaining axes), -1 if none; every query without
+ * a point adds 1 to *not_found (one zeroed word).
+ * flooder_segment_sum_f32: out[seg_target[g], k] = sum over i in [seg_ptr[g], seg_ptr[g+1]) of vals[order[i], k], in
+ * that order (deterministic; rows of out no segment targets are left as they are).
+ */
+int flooder_face_argmax_f32(const uint32_t* d2, int64_t n_simplices, int R, const int32_t* face_ptr,
+                            const int32_t* face_rows, const int32_t* row_id, int n_faces, uint64_t* out_key,
+                            void* stream);
+
+typedef struct flooder_witness_search_s {   /* flooder_witness_search */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const int32_t* order;       /* PointIndex.order32: tree row -> original id */
+  const float* verts;         /* (n_simplices, k1, dim) vertex rows of the swept simplices */
+  const float* weights;       /* (R, k1) the swept weight rows */
+  int32_t R;
+  int32_t reserved;
+  int64_t n_simplices;        /* rows of verts */
+  int64_t n_queries;
+  const int32_t* q_simplex;   /* (n_queries,) queue position of the simplex */
+  const int32_t* q_row;       /* (n_queries,) weight row */
+  const uint32_t* q_d2;       /* (n_queries,) target d2 bits */
+  int64_t* out_point;         /* (n_queries,) */
+  int32_t* not_found;         /* one zeroed word */
+} flooder_witness_search_t;
+int flooder_witness_search(const flooder_witness_search_t* p, void* stream);
+
+int flooder_segment_sum_f32(const float* vals, int dim, const int64_t* order, const int64_t* seg_ptr,
+                            const int64_t* seg_target, int64_t n_seg, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
