@@ -56,7 +56,7 @@ class FusedSweep(_Block):
         p face_bits; p face_slot; p d2_scratch; p flag_list; p flag_count; p flag_key; p flag_hist; p flag_sorted; p top;
         p top_list; p top_count; p simplex_weight; p plane_scratch; p wit_queue; p wit_item_list; p wit_stats;
         p cell_queue; p defer_list; p defer_c; p defer_ctl; p light_list; p heavy_list; p cell_stats; p finish_ctl;
-        p hard_scratch; i32 hard_cap; i32 probed; p finish_stats""")
+        p hard_scratch; i32 hard_cap; i32 probed; p finish_stats; p wit_runs; i32 wit_run_len; i32 wit_n_runs""")
 
 
 class SortedSweep(_Block):

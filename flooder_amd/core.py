@@ -1003,6 +1003,54 @@ def witness_plan(weights: torch.Tensor, perm: np.ndarray) -> Optional[Tuple[np.n
     return out
 
 
+WIT_RUN_LEN = 8          # rows per run of the witness sweep's run test (tools/wit_run_bound.py: 8 leaves less work than 16)
+WIT_RUN_SUM_TOL = 2.0 ** -21   # the weight rows and the run centres must sum to the same value within this (8 ulp)
+
+
+def witness_runs(w_perm: np.ndarray, memb: np.ndarray, parents: np.ndarray,
+                 run_len: Optional[int] = None) -> Optional[np.ndarray]:
+    """Run table of the witness sweep's run test (csrc/flood_wit.hip, phase 4a; ``flooder_fused_sweep_t.wit_runs``):
+    one row of 8 uint32 words per aligned run of ``run_len`` rows of the float32 weight table IN SWEEP ORDER
+    (``w_perm``, with the face masks ``memb`` and the parent words ``parents`` of ``witness_plan`` in the same order):
+    four float32 centre weights (a convex combination of the members: non-negative, zero beyond k1), the OR of the
+    members' face masks, the parent word of the member nearest the centre, and ``rho``: the largest 2-norm of
+    (member's weights - centre weights), in float64 on the float32 values, rounded UP to float32; the last word is 0.
+    For rows that sum to one the 2-norm of a weight difference IS the distance in the regular-simplex embedding of
+    ``witness_plan`` (its corners e_j - 1/k1 project a zero-sum vector onto itself), and a sample moves by at most
+    that distance times the spectral norm of the centred vertex matrix: the kernel bounds a whole run with one
+    evaluation.  The centre is an approximate 1-centre (Badoiu - Clarkson steps from the mean), which keeps ``rho``
+    within a few percent of the smallest possible.  A last partial run gets no row (its samples are looked at one by
+    one).  None: more than four vertices, negative weights, or rows whose sums differ by more than 8 ulp - the kernel's
+    error analysis assumes none of these."""
+    run_len = WIT_RUN_LEN if run_len is None else int(run_len)
+    w32 = np.ascontiguousarray(w_perm, dtype=np.float32)
+    R, k1 = w32.shape
+    n = R // run_len
+    if k1 > 4 or n == 0 or run_len < 8 or run_len & (run_len - 1) or (w32 < 0).any():
+        return None
+    w = w32.astype(np.float64)[:n * run_len].reshape(n, run_len, k1)
+    c = w.mean(axis=1)
+    rows = np.arange(n)
+    for it in range(1, 65):
+        far = ((w - c[:, None, :]) ** 2).sum(axis=2).argmax(axis=1)
+        c += (w[rows, far] - c) / (it + 1)
+    c32 = np.maximum(c, 0.0).astype(np.float32)
+    c64 = c32.astype(np.float64)
+    d = np.sqrt(((w - c64[:, None, :]) ** 2).sum(axis=2))
+    rho = d.max(axis=1) * (1.0 + 1e-12)
+    rho32 = rho.astype(np.float32)
+    rho32 = np.where(rho32.astype(np.float64) < rho, np.nextafter(rho32, np.float32(np.inf)), rho32).astype(np.float32)
+    sums = w32.astype(np.float64).sum(axis=1)
+    if max(np.abs(sums - 1.0).max(), np.abs(c64.sum(axis=1) - 1.0).max()) > 0.5 * WIT_RUN_SUM_TOL:
+        return None
+    out = np.zeros((n, 8), dtype=np.uint32)
+    out[:, :k1] = c32.view(np.uint32)
+    out[:, 4] = np.bitwise_or.reduce(np.asarray(memb).view(np.uint32)[:n * run_len].reshape(n, run_len), axis=1)
+    out[:, 5] = np.asarray(parents).view(np.uint32)[:n * run_len].reshape(n, run_len)[rows, d.argmin(axis=1)]
+    out[:, 6] = rho32.view(np.uint32)
+    return out
+
+
 class SamplePlan:
     """Device-resident sample weights in sweep order (``sample_order``) plus the face table remapped to that order
     and, per row, the bit mask of the faces it lies on (the fused face maxima); built once per dimension pass,
@@ -1031,6 +1079,7 @@ class SamplePlan:
         self._perm, self._weights, self._face_rows = perm, weights, (f_ptr, f_rows, inv)
         self._late_rows = self._wit = None
         self._late_built = self._wit_built = False
+        self._wit_runs, self._wit_runs_built = None, False
 
     # The two tables below cost host work (a device sync for the weights, a cKDTree / farthest-point pass, one loop
     # per face) and only one sweep each reads them: they are built when that sweep first asks - a ``num_rand`` call,
@@ -1065,6 +1114,21 @@ class SamplePlan:
                 dev = self._weights.device
                 self._wit = (torch.as_tensor(wp[0], device=dev), torch.as_tensor(wp[1].view(np.int32), device=dev), wp[2])
         return self._wit
+
+
+    @property
+    def wit_runs(self):
+        """run table of the witness sweep (``witness_runs``) on the device: (table, run length, number of runs), or
+        None.  Like the plan it depends on the weight table and the sweep order only."""
+        if not self._wit_runs_built:
+            self._wit_runs_built = True
+            if self.wit is not None:
+                run_len = WIT_RUN_LEN
+                tab = witness_runs(self.w_perm.cpu().numpy(), self.memb_all.cpu().numpy(), self.wit[1].cpu().numpy(), run_len)
+                if tab is not None:
+                    self._wit_runs = (torch.as_tensor(tab.view(np.int32), device=self._weights.device), run_len,
+                                      int(tab.shape[0]))
+        return self._wit_runs
 
 
 def _sweep_dimension_f64(index: PointIndex, pts64_sorted: torch.Tensor, verts: torch.Tensor, weights: torch.Tensor,
@@ -1260,6 +1324,7 @@ WIT_MIN_SIMPLICES = 1536   # fewer simplices than this in a sweep: no witness sw
 # 6052 handled; cfg 3: 181).  Results do not depend on it (witness on / off: bit-identical, tested).
 WIT_MAX_POINTS_PER_SIMPLEX = 400
 CELL_WITNESS = True  # sparse simplices go to the witness sweep first (whole simplex per wave, coarse samples + bounds)
+WIT_RUNS = True      # ... and it gets the run table of the plan (witness_runs): whole runs of samples dropped with one bound
 
 
 def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
@@ -1371,6 +1436,8 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         if use_wit:   # (split[0]: the witness sweep's item list - scratch until the cell sweep's entry fills it)
             blk.n_coarse, blk.coarse_rows, blk.parents = plan.wit[2], plan.wit[0].data_ptr(), plan.wit[1].data_ptr()
             blk.wit_queue, blk.wit_item_list, blk.wit_stats = qwit.data_ptr(), split[0].data_ptr(), _native.ptr(wst) or None
+            if WIT_RUNS and plan.wit_runs is not None:   # (run test of its pass over all samples)
+                blk.wit_runs, blk.wit_run_len, blk.wit_n_runs = plan.wit_runs[0].data_ptr(), plan.wit_runs[1], plan.wit_runs[2]
         with _span(timer, "sweep"):
             try:
                 if use_wit:

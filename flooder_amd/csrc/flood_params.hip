@@ -29,7 +29,7 @@ extern "C" int flooder_fused_witness(const flooder_fused_sweep_t* p, void* strea
                                 a.coarse_rows, a.n_coarse, a.parents, a.wit_queue, a.d2_scratch, a.memb, a.n_faces,
                                 a.face_bits, a.face_slot, a.flag_list, a.flag_count, a.flag_key, a.flag_hist, a.top,
                                 a.top_list, a.top_count, a.simplex_weight, a.wit_item_list, a.plane_scratch, a.wit_stats,
-                                a.density_grid, stream);
+                                a.density_grid, a.wit_runs, a.wit_run_len, a.wit_n_runs, stream);
 }
 
 extern "C" int flooder_fused_cell(const flooder_fused_sweep_t* p, void* stream) {

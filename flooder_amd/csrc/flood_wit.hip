@@ -46,6 +46,7 @@ int g_wit_max_live_pct = 12; // ... and the share of all samples that may surviv
 int g_wit_adaptive = 0;     // 1: once half of the simplices tried had to be abandoned, only every 16th is still tried
 int g_wit_flags = 0;        // test switches: 1 = no exact pass for the open samples, 2 = rounds not shared between waves
 int g_wit_cmax_ext_pct = 60;  // ... and at most this share of the simplex's extent
+int g_wit_runs = 1;        // 1: the run test of the pass over all samples (phase 4a) where the caller hands in a run table
 int g_wit_surface_pct = 60;   // no attempt at all on a cloud that lies on a surface (the statistic of flood_common.hpp's cloud_kind_block,
 //    // same threshold as the cell sweep's "cell_surface_pct"): every box that meets the sheet is too dense for one stage
 //    // (cfg 3: 5581 simplices tried, none handled, 52 us); 0 = always try
@@ -92,6 +93,10 @@ struct WitPlan {
   const int32_t* coarse_rows;  // WCOARSE entries: row of coarse sample c, -1 beyond n_coarse
   const uint32_t* parents;     // per row: four coarse slots, 8 bits each (a coarse row's first parent is itself)
   int n_coarse;
+  // run table (flooder_fused_sweep_t::wit_runs): per aligned run of 1 << run_shift rows two uint4 - {centre weights},
+  // {OR of the members' face masks, parent word, radius in weight space (float), 0}; n_runs == 0: no run test
+  const uint4* runs;
+  int run_shift, n_runs;
 };
 
 struct WitOut {
@@ -220,6 +225,11 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
   __shared__ float s_rg[Region<DIM>::WORDS];
   __shared__ long long s_item;
   __shared__ int s_off;            // the sweep has switched itself off (see below)
+  __shared__ float s_run[2];       // run test: [0] sigma (norm bound of the weights -> space map), [1] absolute rounding term
+  __shared__ int s_nrun;           // ... runs that survive it
+  // (their list lives in the leaf list: dead between the focus rounds of phase 3b and those of phase 5b)
+  uint16_t* s_runs = reinterpret_cast<uint16_t*>(s_leaf);
+  static_assert(WLEAF * sizeof(int) >= (WROWS / 8) * sizeof(uint16_t), "the run list fits the leaf list (runs of 8 rows or more)");
   uint32_t* s_qub = s_qbuf;
   uint16_t* s_qrow = reinterpret_cast<uint16_t*>(s_qbuf + WQ);
   // (the focus rounds run while the queue is empty - before the pass over all samples, after the rounds - and stream
@@ -239,7 +249,7 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
   if (__builtin_amdgcn_readfirstlane(item_count[0]) == 0) return;
   __shared__ unsigned long long s_stat[24];
   enum { ST_HANDLED = 0, ST_HEAVY = 1, ST_OVER = 2, ST_DENSE = 3, ST_STAGED = 4, ST_CCERT = 5, ST_LIVE = 6, ST_ROUNDS = 7,
-         ST_UNRES = 8, ST_FLAGGED = 9, ST_PAIRS = 10, ST_BINS = 11, ST_EXACT = 22, ST_EXACT_OVER = 23 };
+         ST_UNRES = 8, ST_FLAGGED = 9, ST_PAIRS = 10, ST_BINS = 11, ST_RUNS = 21, ST_EXACT = 22, ST_EXACT_OVER = 23 };
   if (threadIdx.x < 24) s_stat[threadIdx.x] = 0ull;
   auto count = [&](int what, unsigned long long n) {  // (call from one lane per event)
     if (stats) atomicAdd(&s_stat[what], n);
@@ -268,6 +278,7 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     }
     if (tid < MAXL + 2) s_gn[tid] = 0;
     if (tid < 4) s_ctr[tid] = 0;
+    if (tid == 4) s_nrun = 0;
     if (tid < NBIN) s_hist[tid] = 0;
     for (int i = tid; i < WROWS / 32; i += WTHREADS) s_unres[i] = 0u;
     for (int i = tid; i < WROWS / 64; i += WTHREADS) s_tkey[i] = 0u;
@@ -346,6 +357,50 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       const float h = DIM == 3 ? cbrtf(vol / n0) : __builtin_sqrtf(vol / n0);
       c_max = __builtin_fminf(cmax_mult * h, cmax_ext * ext);
       if (tid == 0) rg.store(s_rg);
+      if (tid == 0 && plan.n_runs > 0) {
+        // Run test (phase 4a), per simplex: a sample is p = sum_j w_j v_j, so two samples with weight rows w, w' differ by
+        // p - p' = d^T V = d^T W + (sum d) c^T, d = w - w', W = V - 1 c^T for ANY c, and |d^T W| <= |d|_2 ||W||_2.
+        // sigma >= ||W||_2 for c ~ the centroid: W scaled by its largest entry s (no under- / overflow in the products),
+        // Gershgorin's row-sum bound of the DIM x DIM Gram matrix W^T W, square root.  Rounding: the entries of W carry
+        // 1 ulp each, the scaling 2, a Gram entry 4 fma roundings of products <= the largest diagonal entry, a row
+        // sum 2 more: the computed bound is short of the true one by < 16 u in the square (u = 2^-24), 8 u in the root,
+        // + 2 u for sqrt and the product with s - the factor 1.00001 (168 u) covers it seven times over.
+        // s_run[1]: 2 epsb = 32 u amax covers the rounding of the run's centre and of its members (four fma each:
+        // 4 u amax per coordinate, sqrt(3) of that in the norm, for both: 13.9 u amax) plus the weight rows' sums
+        // differing from one another by <= 8 u (checked by the host; term <= 8 u sqrt(3) amax = 13.9 u amax).
+        float c[DIM], wn[4][DIM], sc = 0.f;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+          c[k] = 0.f;
+          for (int j = 0; j < k1; ++j) c[k] += vs[j * DIM + k];
+          c[k] /= (float)k1;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int k = 0; k < DIM; ++k) {
+            wn[j][k] = j < k1 ? vs[j * DIM + k] - c[k] : 0.f;
+            sc = __builtin_fmaxf(sc, __builtin_fabsf(wn[j][k]));
+          }
+        }
+        const float inv = 1.f / sc;
+        float sig2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+          float row = 0.f;
+#pragma unroll
+          for (int l = 0; l < DIM; ++l) {
+            float g = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g = __builtin_fmaf(wn[j][k] * inv, wn[j][l] * inv, g);
+            row += __builtin_fabsf(g);
+          }
+          sig2 = __builtin_fmaxf(sig2, row);
+        }
+        // (all vertices in one point: 0 is exact; an extent too small to scale: no run is dropped)
+        s_run[0] = sc >= 1e-30f ? __builtin_sqrtf(sig2) * sc * 1.00001f : (sc == 0.f ? 0.f : __builtin_inff());
+        s_run[1] = 2.f * rg.epsb;
+      }
     }
     if (!(c_max > 0.f) || !(c_max < 3.0e38f)) WIT_ABANDON(ST_OVER)
     __syncthreads();
@@ -825,6 +880,7 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     }
     if (tid == 0) s_ctr[3] = 0;
     __syncthreads();
+    WPHASE(4);  // (the focus rounds of 3b count as coarse work)
 
     // ---- 4. all samples: bound from the witnesses of the nearest coarse samples; the live ones are queued.
     // (the table rows of the next step are in flight while this one is worked on)
@@ -834,12 +890,88 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       int rr[UNRF];
       bool valid[UNRF];
     };
+    // ---- 4a. run test: the rows are stored in patches (core.sample_order), and a whole aligned run of them is dropped
+    // with ONE bound.  g: the run's centre (built from its centre weights as a sample is), x: the witness of one of
+    // the run's four parents - a real point of the cloud -, rho: the largest |w - w_centre|_2 among the members.  Every
+    // member p has |p - x| <= |g - x| + rho sigma + A in exact arithmetic on the ROUNDED p and g (sigma, A: phase 1).
+    // In float: d2(g, x) comes out >= (1 - 5.1 u) of its value (two roundings per squared difference, three sums),
+    // its root >= (1 - 3.6 u), t below >= (1 - 5 u) T, t t >= (1 - 11 u) T^2; a member's evaluated d2(p, x) is
+    // <= (1 + 5.1 u) T^2.  The factor 1.000004 (67 u) covers the 17 u four times.  Below 1e-30 the relative bounds
+    // no longer hold (subnormal products): no drop.  B is NaN or inf where the arithmetic overflowed: no drop.
+    // B <= every running maximum of the faces any member lies on: no member can raise one - the maxima only rise, so
+    // the drop stays valid - and none is looked at.  The other runs go through the per-sample pass below unchanged.
+    const int run_shift = plan.run_shift;
+    int n_run_rows = 0, tail0 = 0;   // rows of the surviving runs; first row behind the last whole run
+    if (plan.n_runs > 0) {
+      const float sigma = s_run[0], a_abs = s_run[1];
+      // (as below: the table rows of the next step are in flight while this one is worked on)
+      auto load_run = [&](int i0, uint4& ra, uint4& rb) {
+        const int i = i0 + tid < plan.n_runs ? i0 + tid : 0;
+        ra = plan.runs[2 * i];
+        rb = plan.runs[2 * i + 1];
+      };
+      uint4 ra_next, rb_next;
+      load_run(0, ra_next, rb_next);
+      for (int i0 = 0; i0 < plan.n_runs; i0 += WTHREADS) {
+        if (i0 + (wv << 6) >= plan.n_runs) break;  // (wave-uniform: no run left for this wave; no barrier inside the loop)
+        const int i = i0 + tid;
+        const bool valid = i < plan.n_runs;
+        const uint4 ra = ra_next, rb = rb_next;
+        if (i0 + WTHREADS < plan.n_runs) load_run(i0 + WTHREADS, ra_next, rb_next);
+        const float cw[4] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z), __uint_as_float(ra.w)};
+        float g[DIM];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) g[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < k1) {
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) g[k] = __builtin_fmaf(cw[j], vs[j * DIM + k], g[k]);
+          }
+        }
+        float dg2 = __builtin_inff();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = (int)((rb.y >> (8 * j)) & 0xffu);
+          float t0 = g[0] - s_wit[3 * c + 0];
+          float d2 = t0 * t0;
+          t0 = g[1] - s_wit[3 * c + 1];
+          d2 = __builtin_fmaf(t0, t0, d2);
+          if constexpr (DIM == 3) {
+            t0 = g[2] - s_wit[3 * c + 2];
+            d2 = __builtin_fmaf(t0, t0, d2);
+          }
+          dg2 = __builtin_fminf(dg2, d2);
+        }
+        const float t = __builtin_sqrtf(dg2) + __builtin_fmaf(__uint_as_float(rb.z), sigma, a_abs);
+        float bnd = (t * t) * 1.000004f;
+        if (bnd < 1e-30f) bnd = __builtin_inff();
+        const uint32_t thr = threshold(valid ? rb.x : 0u);  // (every lane of the wave takes part: reductions inside)
+        const bool keep = valid && !(__float_as_uint(bnd) <= thr);
+        const unsigned long long m = __ballot(keep);
+        if (m != 0ull) {
+          int base = 0;
+          if (lane == 0) base = atomicAdd(&s_nrun, __popcll(m));
+          base = wave_uniform(base);
+          if (keep) s_runs[base + lane_rank(m)] = (uint16_t)i;
+        }
+        if (stats) { const unsigned long long md = __ballot(valid && !keep); if (lane == 0) count(ST_RUNS, (unsigned long long)__popcll(md)); }
+      }
+      __syncthreads();
+      n_run_rows = s_nrun << run_shift;
+      tail0 = plan.n_runs << run_shift;
+    }
+    // ---- 4b. the samples of the surviving runs (and the rows behind the last whole run), one by one
+    const int n_fine = n_run_rows + (R - tail0);
     auto load_rows = [&](int g0, FineRows& fr) {
 #pragma unroll
       for (int u = 0; u < UNRF; ++u) {
-        const int r = g0 + u * WTHREADS + tid;
-        fr.valid[u] = r < R;
-        fr.rr[u] = fr.valid[u] ? r : R - 1;
+        const int idx = g0 + u * WTHREADS + tid;
+        fr.valid[u] = idx < n_fine;
+        const int r = !fr.valid[u] ? R - 1
+                      : idx < n_run_rows ? ((int)s_runs[idx >> run_shift] << run_shift) + (idx & ((1 << run_shift) - 1))
+                                         : tail0 + (idx - n_run_rows);
+        fr.rr[u] = r;
         if (k1 == 4) fr.w4[u] = *reinterpret_cast<const float4*>(weights + (int64_t)fr.rr[u] * 4);
         fr.par[u] = plan.parents[fr.rr[u]];
         fr.mb[u] = fr.valid[u] ? acc.memb[fr.rr[u]] : 0u;
@@ -849,15 +981,15 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     FineRows ring[FDEPTH];
 #pragma unroll
     for (int a = 0; a < FDEPTH; ++a)
-      if (a * WTHREADS * UNRF < R) load_rows(a * WTHREADS * UNRF, ring[a]);
-    for (int g0 = 0; g0 < R; g0 += WTHREADS * UNRF) {
+      if (a * WTHREADS * UNRF < n_fine) load_rows(a * WTHREADS * UNRF, ring[a]);
+    for (int g0 = 0; g0 < n_fine; g0 += WTHREADS * UNRF) {
       const FineRows cur = ring[0];
 #pragma unroll
       for (int a = 0; a + 1 < FDEPTH; ++a) ring[a] = ring[a + 1];
-      if (g0 + FDEPTH * WTHREADS * UNRF < R) load_rows(g0 + FDEPTH * WTHREADS * UNRF, ring[FDEPTH - 1]);
+      if (g0 + FDEPTH * WTHREADS * UNRF < n_fine) load_rows(g0 + FDEPTH * WTHREADS * UNRF, ring[FDEPTH - 1]);
 #pragma unroll
       for (int u = 0; u < UNRF; ++u) {
-        if (g0 + u * WTHREADS >= R) break;  // (block-uniform)
+        if (g0 + u * WTHREADS >= n_fine) break;  // (block-uniform)
         float p[DIM];
         if (k1 == 4) {
           const float wj[4] = {cur.w4[u].x, cur.w4[u].y, cur.w4[u].z, cur.w4[u].w};
@@ -1051,7 +1183,13 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     if (tid == 0)
       for (int i = 0; i < 10; ++i) atomicAdd(&stats[12 + i], t_ph[i]);
 #endif
-    if (tid < 24 && (tid < 12 || tid >= 22) && s_stat[tid] != 0ull) atomicAdd(&stats[tid], s_stat[tid]);
+    // (ST_RUNS shares its word with the last phase timer: counted in builds without the timers only)
+#ifdef FLOODER_WIT_TIMERS
+    const bool flush = tid < 12 || tid >= 22;
+#else
+    const bool flush = tid < 12 || tid >= ST_RUNS;
+#endif
+    if (tid < 24 && flush && s_stat[tid] != 0ull) atomicAdd(&stats[tid], s_stat[tid]);
   }
 }
 
@@ -1175,7 +1313,7 @@ int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* 
                   uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count,
                   uint32_t* flag_key, int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count,
                   float* simplex_weight, int32_t* item_list, float* plane_scratch, uint64_t* stats,
-                  const int32_t* density_grid, void* stream) {
+                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, void* stream) {
   if (n_simplices == 0 || R == 0) return FLOODER_OK;
   if (!pts_sorted || !nodes || !verts || !weights || !coarse_rows || !parents || !queue || !d2_scratch || !memb ||
       !face_bits || !flag_list || !flag_count || !simplex_weight || !item_list || !plane_scratch || n_pts < 1 || k1 < 1 ||
@@ -1191,8 +1329,18 @@ int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* 
     return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: cloud too large");
   FaceAcc acc{memb, face_bits, n_faces, reinterpret_cast<unsigned long long*>(top), top_list, top_count, face_slot,
               flag_key, flag_hist};
+  // run table: whole runs of a power of two >= 8 rows (the run list is 16 bit and shares the leaf list's storage),
+  // centre weights for at most four vertices; anything else is a bad argument, no table is no run test
+  int run_shift = 0;
+  if (runs && n_runs > 0) {
+    if (run_len < 8 || run_len > R || (run_len & (run_len - 1)) != 0 || (int64_t)n_runs * run_len > R || k1 > 4)
+      return fail(FLOODER_E_ARG, "flooder_fused_witness: bad run table");
+    while ((1 << run_shift) < run_len) ++run_shift;
+  }
+  const bool use_runs = runs && n_runs > 0 && g_wit_runs != 0;
   return dispatch_dim<WitOp>(dim, pts_sorted, nodes, lv, verts, plane_scratch, weights, k1, R, n_simplices,
-                             WitPlan{coarse_rows, parents, n_coarse}, queue, item_list, queue + FLOODER_QUEUE_WORDS - 1,
+                             WitPlan{coarse_rows, parents, n_coarse, use_runs ? reinterpret_cast<const uint4*>(runs) : nullptr,
+                                     run_shift, use_runs ? n_runs : 0}, queue, item_list, queue + FLOODER_QUEUE_WORDS - 1,
                              WitOut{d2_scratch, flag_list, flag_count, simplex_weight}, acc,
                              reinterpret_cast<unsigned long long*>(stats),
                              density_grid ? density_grid + (flooder_density_grid_words(dim) - KIND_WORDS) : nullptr,
@@ -1215,7 +1363,8 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
                               int32_t* item_list, float* plane_scratch, uint64_t* stats, void* stream) {
   return sweep_witness(pts_sorted, n_pts, dim, nodes, verts, weights, k1, R, n_simplices, coarse_rows, n_coarse, parents,
                        queue, d2_scratch, memb, n_faces, face_bits, face_slot, flag_list, flag_count, flag_key, flag_hist,
-                       top, top_list, top_count, simplex_weight, item_list, plane_scratch, stats, nullptr, stream);
+                       top, top_list, top_count, simplex_weight, item_list, plane_scratch, stats, nullptr, nullptr, 0, 0,
+                       stream);
 }
 
 }  // extern "C"

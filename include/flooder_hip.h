@@ -425,7 +425,9 @@ int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim
  * weight -1, which flooder_sweep_cell_faces_f32 skips.  R <= FLOODER_WIT_MAX_ROWS.  queue: FLOODER_QUEUE_WORDS zeroed
  * int32.  item_list: n_simplices int32 of scratch (the simplices light enough, heaviest class first).  stats: NULL or 24 zeroed uint64 {simplices handled, too heavy, gather overflow, too dense for the stage,
  * points staged, coarse samples certified, samples live after the bound, evaluation rounds, samples handed to the
- * finish, tiles flagged, pairs evaluated, excess bins kept; [12:22] cycles per phase in builds with -DFLOODER_PHASE_TIMERS}.  Options: "wit_cmax_pct" (250: gather radius in percent of
+ * finish, tiles flagged, pairs evaluated, excess bins kept; [12:22] cycles per phase in builds with -DFLOODER_WIT_TIMERS -
+ * without them [21] = runs of samples dropped by the run test (flooder_fused_witness with a run table only); [22], [23]
+ * focus rounds, gather overflows in them}.  Options: "wit_cmax_pct" (250: gather radius in percent of
  * the local point spacing), "wit_min_bins" (6), "wit_grid".
  */
 int flooder_wit_max_rows(void);
@@ -638,12 +640,24 @@ typedef struct flooder_fused_sweep_s {
   int32_t hard_cap;
   int32_t probed;
   uint64_t* finish_stats;
+  /* witness sweep, run test (fields added behind the first release of the struct: a caller that does not have them
+   * gets no run test).  wit_runs: NULL, or wit_n_runs rows of 8 words, one per aligned run of wit_run_len (a power of
+   * two >= 8) consecutive rows of `weights`: {4 float centre weights (non-negative, sum 1, zero beyond k1), uint32 OR
+   * of the members' words of `memb`, uint32 parent word (as `parents`), float radius: the largest 2-norm of
+   * (member's weight row - centre weights), rounded up, 0}.  wit_n_runs * wit_run_len <= R (rows behind the last whole
+   * run are always looked at one by one); 32-byte aligned; k1 <= 4.  Every weight row and the centre weights must sum
+   * to the same value within 2^-21.  Option "wit_runs" 0 switches the test off. */
+  const uint32_t* wit_runs;
+  int32_t wit_run_len;
+  int32_t wit_n_runs;
 } flooder_fused_sweep_t;
 
 /* flooder_sweep_witness_f32, flooder_sweep_cell_faces_f32, flooder_finish_faces_f32 on the fields of *p (host memory;
  * read during the call only).  flooder_fused_witness also hands `density_grid` (may be NULL) to the witness sweep, which
- * then stands back on a cloud that lies on a surface (option "wit_surface_pct"); the positional function has no such
- * argument and always tries. */
+ * then stands back on a cloud that lies on a surface (option "wit_surface_pct"), and the run table (wit_runs): a
+ * whole run of samples is dropped with one bound - the distance of the run's centre to a parent's witness plus the
+ * run's radius - where that bound cannot raise a face value; the positional function has neither argument: it always
+ * tries and looks at every sample.  Face values are the same bit for bit either way. */
 int flooder_fused_witness(const flooder_fused_sweep_t* p, void* stream);
 int flooder_fused_cell(const flooder_fused_sweep_t* p, void* stream);
 int flooder_fused_finish(const flooder_fused_sweep_t* p, void* stream);

@@ -71,7 +71,10 @@ for shared in (True, False):
     if w[0] > 0:
         print(f"  per handled simplex: staged {w[4] / w[0]:.0f} coarse_cert {w[5] / w[0]:.0f} live {w[6] / w[0]:.0f} rounds {w[7] / w[0]:.2f} "
               f"unresolved {w[8] / w[0]:.1f} tiles {w[9] / w[0]:.2f} bins {w[11] / w[0]:.1f}")
-    if st[28:38].sum() > 0:
+    if st[28:37].sum() == 0:   # (no phase timers in this build: the last timer word counts the runs the run test dropped)
+        n_runs = (R // core.WIT_RUN_LEN) * int(w[0])
+        print(f"  runs dropped by the run test: {int(st[37])} of {n_runs} ({100.0 * st[37] / max(n_runs, 1):.1f} %)")
+    if st[28:37].sum() > 0:
         ph = st[28:38].astype(float)
         print("  wit phases % (setup, gather, hist, stage, coarse, fine, rounds, flag, pop, -):", [round(100 * v / ph.sum(), 1) for v in ph], "Mcycles/item", round(ph.sum() / max(w[0], 1) / 1e6, 3))
     print("  cell:", [int(v) for v in st[:9]], "finish:", [int(v) for v in st[9:16]])
