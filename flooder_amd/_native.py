@@ -82,6 +82,13 @@ class WitnessSearch(_Block):
         i32 R; i32 reserved; i64 n_simplices; i64 n_queries; p q_simplex; p q_row; p q_d2; p out_point; p not_found""")
 
 
+class KnnSweep(_Block):
+    """``flooder_knn_sweep_t``: the tree sweep that keeps the k nearest points of every sample (robust filtration)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
+        i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats""")
+
+
 _lib = None
 _load_error: Exception | None = None
 _load_missing = False  # the last failure was "file not found" (worth another look after a build)
@@ -170,6 +177,8 @@ SIGNATURES = {
                                         c_void_p]),
     "flooder_witness_search": (c_int, [ctypes.POINTER(WitnessSearch), c_void_p]),
     "flooder_segment_sum_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    # the k nearest points of every sample (flood_complex(neighbors=k))
+    "flooder_sweep_knn_f32": (c_int, [ctypes.POINTER(KnnSweep), c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

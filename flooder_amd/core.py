@@ -1300,6 +1300,45 @@ def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.
     return out_face, out_dist
 
 
+# Most neighbours per sample of the robust filtration (``flood_complex(neighbors=k)``; FLOODER_KNN_MAX).  A register-budget
+# limit of the kernel, not a tuning knob: every lane of csrc/flood_knn.hip keeps its best squared distances in K vector
+# registers, K = k rounded up to 2, 4, 8, 16 or 32 (k = 17 costs what k = 32 costs), and at 32 the sweep still runs four
+# waves per SIMD.
+KNN_MAX = 32
+NEIGHBOR_STATS = ("kth", "dtm")
+
+
+def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                         k: int, stat: str, plan: Optional["SamplePlan"] = None,
+                         stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None):
+    """All simplices of one dimension against an indexed point set, ``k`` nearest points per sample -> (S, F) face
+    maxima of the k-distance (``stat="kth"``) or of the distance to the empirical measure (``"dtm"``).
+
+    sweep_knn (plain stores of the SQUARED statistic's bits into the (S, R) buffer, samples in the order of
+    ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, k1, _ = verts.shape
+    R = weights.shape[0]
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
+    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
+    blk = _native.KnnSweep(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
+                           weights=plan.w_perm, R=R, k=int(k), n_simplices=S, stat=NEIGHBOR_STATS.index(stat),
+                           queue=queue, out_bits=d2, stats=stats)
+    with _span(timer, "sweep"):
+        _native.check(lib.flooder_sweep_knn_f32(ctypes.byref(blk), st), "flooder_sweep_knn_f32")
+    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
+    with _span(timer, "face_max"):
+        _native.check(lib.flooder_face_max_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr),
+                                               _native.ptr(plan.rows_perm), faces.n_faces,
+                                               _native.ptr(out_face), None, st),
+                      "flooder_face_max_f32")
+    return out_face, None
+
+
 # tree sweep over spatially sorted samples (csrc/flood_sorted.hip): None = above 3 dimensions, True / False = always / never
 BVH_SORTED_SAMPLES: Optional[bool] = None
 SORTED_WORKSPACE_BYTES = 16 << 30   # scratch the sorted-sample sweep may take (288 GB of HBM per GPU)
@@ -1522,6 +1561,8 @@ def flood_complex(
     index: Optional["PointIndex"] = None,
     shard_blocks: bool = False,
     landmarks_in_cloud: Optional[bool] = None,
+    neighbors: int = 1,
+    neighbor_stat: str = "kth",
 ):
     """Flood complex of ``points`` over the Delaunay triangulation of ``landmarks``.
 
@@ -1566,7 +1607,47 @@ def flood_complex(
     order instead: this rank's (S, F) values are the maxima over ITS samples (0 where it has none), and
     ``face_reduce_hook`` - an in-place elementwise MIN over the ranks, whatever it is given - receives the NEGATED
     matrix, so that its MIN is the MAX of the values.
+
+    ``neighbors=k`` with ``neighbor_stat`` (keyword-only): the ROBUST filtration.  With d_(1) <= d_(2) <= ... the
+    distances from a sample to the points of the cloud (a point that occurs twice counts twice), a sample's value is
+    d_(k) (``"kth"``, the k-distance) or sqrt(mean of d_(1)^2 .. d_(k)^2) (``"dtm"``, the distance to the empirical
+    measure) instead of d_(1); a simplex still gets the maximum over its samples.  A few stray points inside a void then
+    no longer fill it (README, "Robust filtration").  1 <= k <= ``KNN_MAX`` (32: what a lane of the kernel keeps in
+    registers; the kernel rounds k up to 2, 4, 8, 16 or 32 slots, so k = 17 costs what k = 32 costs) and k <= number of
+    points; ``neighbors=1`` IS the plain filtration - the code path of a call without the
+    argument, bit for bit, whichever statistic is named.  For k > 1: ROCm float32 tensors in 2 to 8 dimensions run the
+    k-nearest tree sweep (``method`` ``None`` / ``"auto"`` / ``"bvh"``; ``"cell"`` and ``"ball"`` evaluate the
+    nearest point only and are refused), CPU tensors query the kd-tree with ``k=neighbors``; ``reduce_hook`` (a MIN
+    over point shards is not the k-th of their union), ``shard_blocks=True`` (the bounding balls of a block bound the
+    NEAREST point only) and ROCm float64 tensors are refused; ``simplex_shard`` without blocks works as before.
     """
+    # ---- the robust filtration's arguments, before any work is done
+    if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
+        raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
+    neighbors = int(neighbors)
+    if not 1 <= neighbors <= KNN_MAX:
+        raise ValueError(f"neighbors must be in 1..{KNN_MAX} (KNN_MAX: the k best of a sample live in registers of the "
+                         f"kernel), got {neighbors}")
+    if neighbor_stat not in NEIGHBOR_STATS:
+        raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
+    if points.dim() == 2 and neighbors > max(points.shape[0], 1):
+        raise ValueError(f"neighbors={neighbors} exceeds the number of points ({points.shape[0]})")
+    if neighbors > 1:
+        if method in ("cell", "ball"):
+            raise ValueError(f"neighbors > 1 needs the tree sweep: method {method!r} evaluates the nearest point only "
+                             "(use method=None, 'auto' or 'bvh')")
+        if reduce_hook is not None:
+            raise ValueError("neighbors > 1 cannot be combined with reduce_hook: a MIN over point shards is not the "
+                             "k-th nearest of their union")
+        if shard_blocks:
+            raise ValueError("neighbors > 1 cannot be combined with shard_blocks=True: a block's sub-cloud holds the "
+                             "points inside its simplices' bounding balls, which bound the nearest point only")
+        if points.is_cuda and points.dtype is torch.float64:
+            raise ValueError("neighbors > 1 on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
+        if points.is_cuda and points.dim() == 2 and not 2 <= points.shape[1] <= 8:
+            raise ValueError("neighbors > 1 on ROCm tensors needs ambient dimension 2 to 8")
+        if method is None or method == "auto":
+            method = "bvh"   # (the tree sweep in every dimension; any other name is judged below as always)
     if use_triton is None:
         use_triton = HAS_HIP_KERNELS
     if use_triton and not _has_hip_kernels():
@@ -1741,7 +1822,7 @@ def flood_complex(
             if blocks:   # a contiguous block of the queue (the simplices are ordered along the widest axis)
                 mine = torch.arange(num_simplices * sh_rank // sh_world, num_simplices * (sh_rank + 1) // sh_world,
                                     device=device)
-            elif (on_gpu and not use_f64 and reduce_hook is None
+            elif (on_gpu and not use_f64 and reduce_hook is None and neighbors == 1
                   and shards_sorted_tiles(dim, num_simplices, weights.shape[0], method)):
                 mine = None          # all simplices, a contiguous run of the TILES of the sorted sample order
                 tile_shard = (sh_rank, sh_world)
@@ -1764,6 +1845,8 @@ def flood_complex(
         if on_gpu and sv.shape[0] == 0 and (blocks or slots is not None):   # (more ranks than simplices)
             face_dev = (torch.full((slots[1],), float("inf"), dtype=torch.float32, device=device) if slots is not None
                         else torch.empty((0, faces.n_faces), dtype=torch.float32, device=device))
+        elif on_gpu and neighbors > 1:
+            face_dev, _ = _sweep_dimension_knn(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu:
             if method == "ball":
                 face_dev, _ = _sweep_dimension_hip(pts_pad, search, axis, dim, sv,
@@ -1777,6 +1860,14 @@ def flood_complex(
                                                     face_slots=None if slots is None else slots[:2])
             else:
                 face_dev, _ = _sweep_dimension_bvh(index, sv, weights, faces, reduce_hook, plan=plan, tile_shard=tile_shard)
+        elif neighbors > 1:
+            samples = weights.unsqueeze(0) @ sv
+            dist, _ = kdtree.query(np.asarray(samples), k=neighbors, workers=CPU_WORKERS)   # (S, R, k), ascending
+            if neighbor_stat == "kth":
+                dist = dist[..., -1]
+            else:
+                dist = np.sqrt(np.square(dist.astype(np.float64)).sum(axis=-1) / neighbors)
+            face_dev = _face_max_cpu(torch.as_tensor(np.ascontiguousarray(dist)), faces)
         else:
             samples = weights.unsqueeze(0) @ sv
             # (the reference queries with scipy's default of ONE worker, core.py:198; the distances do not depend on

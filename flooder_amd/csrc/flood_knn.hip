@@ -1,0 +1,268 @@
+// flood_knn.hip - tree sweep that keeps the k nearest points of every sample (gfx950): the robust filtration.
+//
+// flooder_sweep_knn_f32 writes, per (simplex, sample), the float32 bits of the SQUARED k-distance (the k-th smallest
+// squared distance to the cloud, duplicates counted with their multiplicity) or of the squared distance to the
+// empirical measure (the mean of the k smallest squared distances) into the (S, R) buffer that flooder_face_max_f32
+// reads - the square root and the face maxima stay there.
+//
+//   sweep_knn<DIM, K>   one wave owns (simplex, tile of 64 samples), one sample per lane, rebuilt in registers as in
+//                       sweep_bvh (fma in vertex order) with the same squared distance (t0*t0, then fma(t, t, d2)).
+//                       Every lane keeps its k smallest d2 as an ascending list in K registers, K the smallest of
+//                       2, 4, 8, 16, 32 that holds k.  The list sits at the END of the K registers and the K - k in
+//                       front of it hold -inf: a candidate passes them unchanged, so the insertion is the same
+//                       branch-free chain of K (min, max) pairs for every k, and the k-th best is ALWAYS the last
+//                       register - no register indexed by a run-time k.  (The k live slots start at +inf.)
+//                       Traversal is sweep_bvh's, wave-uniform and nearest-first over the same nodes with the same
+//                       lower bounds and the same safety margin; what it culls against is M = the largest k-th best
+//                       of the wave (+inf until every lane has seen k points).  The nearest-first order IS a greedy
+//                       descent: the first thing a wave does is walk down to the leaf nearest to its tile, so M is
+//                       finite after ceil(k / 16) leaves.
+//
+// Exactness.  The k-th smallest value of a multiset does not depend on the order in which its elements are offered,
+// and a point whose d2 is >= the current k-th best can never lower it - so a subtree whose lower bound is >= M, a leaf
+// whose box is >= the k-th best of every lane, and a point no lane improves on are skipped without changing any list.
+// What is skipped is never among the k smallest of a lane unless it TIES the k-th, and a tie leaves every one of the k
+// values as it is.  The lists at the end are therefore the k smallest d2 of ALL points, value for value, whatever the
+// tree looks like; the mean adds them in ascending order, smallest first, in float32, and divides by (float)k with the
+// correctly rounded division - a function of those k values alone.
+
+#include "flood_common.hpp"
+#include "flood_bvh.hpp"
+
+#include <cstring>
+
+using namespace flooder;
+
+namespace {
+
+constexpr float SAFE = 0.99999f;   // the margin of the other tree sweeps (flood_bvh.hip)
+
+template <int DIM, int K>
+__global__ __launch_bounds__(256) void sweep_knn_kernel(
+    const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
+    const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int k, int stat,
+    int32_t* __restrict__ queue, uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ float s_lb[4][MAXL][FAN];
+  __shared__ int64_t s_grp[4][MAXL];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int tiles = (R + 63) / 64;
+  const int64_t n_items = n_simplices * tiles;
+  const int top = lv.n_levels - 1;
+  const int first = K - k;   // the k live slots are list[first .. K-1]  (wave-uniform)
+  unsigned long long n_leaf_eval = 0, n_leaf_test = 0, n_node_test = 0, max_item_tests = 0;
+
+  int q_shard = (int)(((int64_t)blockIdx.x * 4 + wv) % QSHARDS), q_tried = 0;
+  for (;;) {
+    const int64_t g = queue_pop(queue, q_shard, q_tried, n_items, lane);  // sharded heads (flood_common.hpp)
+    if (g < 0) break;
+    const unsigned long long tests_before = n_leaf_test + n_node_test;
+    const int64_t s = g / tiles;
+    const int tile = (int)(g - s * tiles);
+
+    // ---- this lane's sample: p = sum_j w[r,j] * v[s,j,:], as sweep_bvh builds it
+    int r = tile * 64 + lane;
+    const bool live = r < R;
+    if (!live) r = R - 1;  // duplicate of the last sample, never stored
+    float p[DIM];
+    const float* vs = verts + s * (int64_t)k1 * DIM;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) p[c] = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) p[c] = __builtin_fmaf(w, vs[j * DIM + c], p[c]);
+    }
+    // (kept as the int32 words of the floats: d2 is never negative and never NaN, so the signed integer order of the
+    // words is the order of the values, -inf included, and v_min_i32 / v_max_i32 need no canonicalising copy)
+    int list[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) list[i] = i >= first ? (int)INF_BITS : (int)0xff800000u;
+
+    // ---- bounding box of the tile (wave-uniform)
+    float tlo[DIM], thi[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      tlo[c] = wave_min_f32(p[c]);
+      thi[c] = wave_max_f32(p[c]);
+    }
+    float M = __builtin_inff();  // largest k-th best of the tile (wave-uniform)
+
+    // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound to the tile box
+    float c_lo[DIM], c_hi[DIM];
+    auto child_bounds = [&](int lvl, int64_t grp) -> float {
+      const int64_t idx = grp * FAN + lane;
+      float lb = __builtin_inff();
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) { c_lo[c] = __builtin_inff(); c_hi[c] = -__builtin_inff(); }
+      if (idx < lv.count[lvl]) {
+        float lo[DP], hi[DP];
+        const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
+        load_row<DP>(nb, lo);
+        load_row<DP>(nb + DP, hi);
+        lb = 0.f;
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+          c_lo[c] = lo[c];
+          c_hi[c] = hi[c];
+          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[c] - thi[c], tlo[c] - hi[c]), 0.f);
+          lb = __builtin_fmaf(gap, gap, lb);
+        }
+      }
+      return lb;
+    };
+
+    // inner levels keep their per-lane bounds in LDS; the leaf level runs in registers (lb0, c_lo / c_hi)
+    int lvl = top;
+    float lb0 = child_bounds(top, 0);
+    int64_t grp0 = 0;
+    ++n_node_test;
+    if (top > 0) {
+      s_lb[wv][top][lane] = lb0;
+      if (lane == 0) s_grp[wv][top] = 0;
+    }
+    for (;;) {
+      if (lvl > 0) {
+        const float lbv = s_lb[wv][lvl][lane];
+        const float mn = wave_min_f32(lbv);
+        if (!(mn * SAFE < M)) {  // nothing left at this level can lower a k-th best of the tile
+          if (++lvl > top) break;
+          continue;
+        }
+        const int j = __builtin_ctzll(__ballot(lbv == mn));
+        if (lane == j) s_lb[wv][lvl][lane] = __builtin_inff();  // visited
+        const int64_t c = wave_uniform64(s_grp[wv][lvl]) * FAN + j;
+        --lvl;
+        const float lb = child_bounds(lvl, c);
+        ++n_node_test;
+        if (lvl > 0) {
+          s_lb[wv][lvl][lane] = lb;
+          if (lane == 0) s_grp[wv][lvl] = c;
+        } else {
+          lb0 = lb;
+          grp0 = c;
+        }
+        continue;
+      }
+      // ---- leaf level: nearest unvisited leaf of the current group
+      const float mn = wave_min_f32(lb0);
+      if (!(mn * SAFE < M)) {
+        if (++lvl > top) break;
+        continue;
+      }
+      const int j = __builtin_ctzll(__ballot(lb0 == mn));
+      if (lane == j) lb0 = __builtin_inff();  // visited
+      const int64_t c = grp0 * FAN + j;
+      ++n_leaf_test;
+      // can the k-th best of any lane still drop against leaf c?  (its box comes from lane j)
+      float lbp = 0.f;
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const float blo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[a]), j));
+        const float bhi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[a]), j));
+        const float gap = __builtin_fmaxf(__builtin_fmaxf(blo - p[a], p[a] - bhi), 0.f);
+        lbp = __builtin_fmaf(gap, gap, lbp);
+      }
+      if (__ballot(lbp * SAFE < __int_as_float(list[K - 1])) == 0ull) continue;
+      ++n_leaf_eval;
+      const float* cp = pts + c * (int64_t)LEAF * DP;
+      constexpr int NB = DP == 8 ? 4 : 8;   // rows in SGPRs at a time (32 scalar registers at most)
+#pragma unroll 1
+      for (int h = 0; h < LEAF; h += NB) {   // (not unrolled: the body holds NB insertion chains)
+        typename RowVec<DP>::type cc[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) cc[u] = load_uniform_row<DP>(cp + (h + u) * DP);
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          float d;
+#pragma unroll
+          for (int a = 0; a < DIM; ++a) {
+            const float t = p[a] - cc[u][a];
+            d = a == 0 ? t * t : __builtin_fmaf(t, t, d);
+          }
+          // the chain only when some lane improves (wave vote); a lane that does not passes d through its list
+          // unchanged anyway: every slot is <= its k-th best <= d
+          int di = __float_as_int(d);
+          if (__ballot(di < list[K - 1]) != 0ull) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+              const int hi = list[i] > di ? list[i] : di;
+              list[i] = list[i] < di ? list[i] : di;
+              di = hi;
+            }
+          }
+        }
+      }
+      M = wave_max_f32(__int_as_float(list[K - 1]));
+    }
+
+    if (live) {
+      float v = __int_as_float(list[K - 1]);
+      if (stat != 0) {   // mean of the k smallest: ascending, smallest first, sequential float32 adds
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          if (i == first) acc = __int_as_float(list[i]);
+          else if (i > first) acc = acc + __int_as_float(list[i]);
+        }
+        v = acc / (float)k;
+      }
+      out_bits[s * (int64_t)R + r] = __float_as_uint(v);
+    }
+    const unsigned long long item_tests = n_leaf_test + n_node_test - tests_before;
+    max_item_tests = item_tests > max_item_tests ? item_tests : max_item_tests;
+  }
+  if (stats && lane == 0 && (n_node_test | n_leaf_test) != 0ull) {
+    atomicMax(&stats[3], max_item_tests);
+    atomicAdd(&stats[0], n_leaf_eval);
+    atomicAdd(&stats[1], n_leaf_test);
+    atomicAdd(&stats[2], n_node_test);
+  }
+}
+
+template <int DIM>
+struct SweepKnnOp {
+  static int run(const flooder_knn_sweep_t& a, const Levels& lv, hipStream_t st) {
+    const int64_t n_items = a.n_simplices * ((a.R + 63) / 64);
+    int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
+    if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+#define FLOODER_LAUNCH_KNN(K_)                                                                                       \
+  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, lv, \
+                     a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat, a.queue, a.out_bits,                 \
+                     reinterpret_cast<unsigned long long*>(a.stats))
+    if (a.k <= 2) FLOODER_LAUNCH_KNN(2);
+    else if (a.k <= 4) FLOODER_LAUNCH_KNN(4);
+    else if (a.k <= 8) FLOODER_LAUNCH_KNN(8);
+    else if (a.k <= 16) FLOODER_LAUNCH_KNN(16);
+    else FLOODER_LAUNCH_KNN(32);
+#undef FLOODER_LAUNCH_KNN
+    return check_launch("sweep_knn");
+  }
+};
+// (the tree sweeps exist for one ambient dimension as well; the k-nearest sweep is defined for 2 .. 8)
+template <>
+struct SweepKnnOp<1> {
+  static int run(const flooder_knn_sweep_t&, const Levels&, hipStream_t) {
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
+  }
+};
+
+}  // namespace
+
+extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream) {
+  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_knn_sweep_t))
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad parameter block (abi / size)");
+  flooder_knn_sweep_t a;
+  std::memset(&a, 0, sizeof(a));
+  std::memcpy(&a, p, p->size);
+  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: k must be in 1..32");
+  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
+  if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: stat must be 0 (kth) or 1 (dtm)");
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.n_pts < a.k || a.k1 < 1 ||
+      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad argument (null pointer, fewer points than k, k1, R)");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<SweepKnnOp>(a.dim, a, lv, (hipStream_t)stream);
+}

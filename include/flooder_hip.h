@@ -752,6 +752,44 @@ int flooder_witness_search(const flooder_witness_search_t* p, void* stream);
 int flooder_segment_sum_f32(const float* vals, int dim, const int64_t* order, const int64_t* seg_ptr,
                             const int64_t* seg_target, int64_t n_seg, float* out, void* stream);
 
+/*
+ * ---- Robust filtration: the k nearest points of every sample (csrc/flood_knn.hip) --------------------------------
+ * flooder_sweep_knn_f32: the tree sweep of flooder_sweep_bvh_f32 (same samples p = sum_j weights[r, j] *
+ * verts[s, j, :], fma in vertex order; same squared distance t0*t0, then fma(t, t, d2); same (S, R) output buffer,
+ * plain stores, every cell written once) keeping the k smallest squared distances of every sample, duplicates of a
+ * point counted with their multiplicity.  out_bits[s, r] = the float32 bits of the SQUARED statistic:
+ *   stat 0 ("kth")  the k-th smallest d2;
+ *   stat 1 ("dtm")  the k smallest d2 added in ascending order, smallest first, by sequential float32 additions,
+ *                   divided by (float)k (correctly rounded).
+ * flooder_face_max_f32 takes the square roots and the face maxima.  Both are exact and independent of the tree and
+ * of the order of traversal; k = 1 gives flooder_sweep_bvh_f32's words.  k in 1..FLOODER_KNN_MAX, k <= n_pts, dim in
+ * 2..8.  A lane keeps its best in K vector registers, K = k rounded up to 2, 4, 8, 16 or 32 (one kernel each): the
+ * insertion costs what K costs - k = 17 as much as k = 32 - and 32 is what leaves the kernel four waves per SIMD.
+ * queue: FLOODER_QUEUE_WORDS zeroed int32.  stats: NULL or four zeroed uint64 {leaves evaluated, leaf tests, node
+ * tests, most tests of one tile} as flooder_sweep_bvh_f32.
+ */
+#define FLOODER_KNN_MAX 32
+
+typedef struct flooder_knn_sweep_s {        /* flooder_sweep_knn_f32 */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) */
+  int32_t R;
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_MAX */
+  int64_t n_simplices;
+  int32_t stat;               /* 0 = kth, 1 = dtm */
+  int32_t reserved;
+  int32_t* queue;
+  uint32_t* out_bits;         /* (n_simplices, R) */
+  uint64_t* stats;            /* may be NULL */
+} flooder_knn_sweep_t;
+int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
