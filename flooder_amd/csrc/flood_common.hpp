@@ -73,6 +73,7 @@ extern int g_wit_max_leaves;
 extern int g_wit_max_in_pct;
 extern int g_wit_max_live_pct;
 extern int g_wit_min_bins;  // ... excess bins (of 64) the stage must hold at least
+extern int g_wit_sorted_stage;  // ... 1: its stage is ordered by excess bin and its pair loops stop early
 extern int g_wit_runs;  // ... 1: the run test of its pass over all samples, where a run table is handed in
 extern int g_wit_surface_pct;  // ... and no attempt on a cloud with less than this percentage of its points in interior cells (0: always)
 // face planes of every simplex (flood_cell.hip: simplex_planes_kernel), 24 floats per simplex

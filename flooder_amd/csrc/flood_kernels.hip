@@ -826,6 +826,10 @@ int flooder_set_option(const char* name, int value) {
     g_wit_runs = value;
     return FLOODER_OK;
   }
+  if (name && strcmp(name, "wit_sorted_stage") == 0 && (value == 0 || value == 1)) {
+    g_wit_sorted_stage = value;
+    return FLOODER_OK;
+  }
   if (name && strcmp(name, "wit_surface_pct") == 0 && value >= 0 && value <= 100) {
     g_wit_surface_pct = value;
     return FLOODER_OK;

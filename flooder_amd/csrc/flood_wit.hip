@@ -12,6 +12,9 @@
 //                excesses picks the largest c_sel <= c_max whose points (e(x) < c_sel) fit the LDS stage.  A sample p
 //                with inner slack delta(p) (its distance to the nearest side of P) then has EVERY point within
 //                c_sel + delta(p) of it on the stage: a minimum below (0.999 (c_sel + delta))^2 is exact ("certified").
+//                The stage is filled in the order of the bins: the same bound holds for every bin boundary c and the
+//                points staged from that bin on, and the pair loops of 3. and 4. stop at the first bin whose points
+//                are provably farther than the running minimum of every sample of the wave ("wit_sorted_stage").
 //   3. coarse    a coarse sub-lattice of the samples (every M-th lattice point of every face, <= 256 rows chosen by
 //                the host) is evaluated against the stage; every coarse sample keeps its WITNESS - the staged point
 //                that attains its minimum - and the certified ones raise the running maxima of their faces.
@@ -46,6 +49,7 @@ int g_wit_max_live_pct = 12; // ... and the share of all samples that may surviv
 int g_wit_adaptive = 0;     // 1: once half of the simplices tried had to be abandoned, only every 16th is still tried
 int g_wit_flags = 0;        // test switches: 1 = no exact pass for the open samples, 2 = rounds not shared between waves
 int g_wit_cmax_ext_pct = 60;  // ... and at most this share of the simplex's extent
+int g_wit_sorted_stage = 1; // 1: the stage is filled in the order of the excess bins and the pair loops stop at the first bin no sample needs
 int g_wit_runs = 1;        // 1: the run test of the pass over all samples (phase 4a) where the caller hands in a run table
 int g_wit_surface_pct = 60;   // no attempt at all on a cloud that lies on a surface (the statistic of flood_common.hpp's cloud_kind_block,
 //    // same threshold as the cell sweep's "cell_surface_pct"): every box that meets the sheet is too dense for one stage
@@ -76,6 +80,7 @@ constexpr int UNRF = 1;        // groups of 256 rows in flight in the pass over 
 #endif
 constexpr int FDEPTH = FLOODER_WIT_FDEPTH;  // steps of the pass over all samples whose table rows are in flight
 constexpr int NBIN = 64;
+constexpr int SGRP = 32;       // stage slots between two exit tests of a pair loop (ordered stage)
 constexpr int PLANE_ROW = 24;  // (layout of simplex_planes_kernel, flood_cell.hip)
 static_assert(WCOARSE == WTHREADS, "one coarse sample per thread");
 static_assert(WUR == WTHREADS && WUR >= WCOARSE, "one open sample per thread in the exact pass");
@@ -141,7 +146,14 @@ struct Region {
   }
   // squared radius within which EVERY point around sample p is on a stage that holds all points of excess < c_sel:
   // c_sel plus the sample's own distance to the nearest side of the polytope
-  __device__ __forceinline__ float cert_limit(const float (&p)[DIM], float c_sel) const {
+  __device__ __forceinline__ float cert_limit(const float (&p)[DIM], float c_sel) const { return limit(slack(p), c_sel); }
+  // the same radius for ANY c: every point of excess >= c is farther than sqrt(limit(slack(p), c)) from p
+  static __device__ __forceinline__ float limit(float dl, float c) {
+    const float rr = 0.999f * (c + __builtin_fmaxf(dl, 0.f));
+    return rr * rr;
+  }
+  // inner slack of a sample: its distance to the nearest side of the polytope (negative: outside by rounding)
+  __device__ __forceinline__ float slack(const float (&p)[DIM]) const {
     float dl = __builtin_inff();
 #pragma unroll
     for (int k = 0; k < DIM; ++k) dl = __builtin_fminf(dl, __builtin_fminf(p[k] - blo[k], bhi[k] - p[k]));
@@ -154,21 +166,27 @@ struct Region {
         dl = __builtin_fminf(dl, __builtin_fminf(shi[f] - dd, dd - slo[f]));
       }
     }
-    const float rr = 0.999f * (c_sel + __builtin_fmaxf(dl, 0.f));
-    return rr * rr;
+    return dl;
   }
 };
 
 // excess of a point: the smallest c for which it counts as "within c of the simplex" (<= its distance to the polytope)
+// The bounds built on it add a SAMPLE's inner slack to a point's excess, and a sample is a rounded combination of the
+// vertices: it may lie outside the polytope - four fma per coordinate, 2 eps amax each, 3.5 eps amax in the norm
+// (eps = 2^-23) - where its slack counts as 0, and the slack along a face normal is itself computed with up to
+// 2 eps sext <= 7 eps amax of rounding.  Those 10.5 eps amax are taken off the excess here, as 2 epsb = 16 eps amax on
+// every side: with them  dist(p, x) >= excess(x) + max(slack(p), 0)  holds for the numbers as computed, whatever the
+// size of the coordinates against the simplex (tests/test_wit_sorted_stage_cpu.py: clouds offset by 1e3).
+constexpr float EXCESS_PAD = 2.f;   // in units of epsb (the gather box grows by as much: every point of excess < c_max is gathered)
 template <int DIM>
 struct Excess {
   float pn[DIM + 1][DIM], po[DIM + 1], org[DIM], blo_e[DIM], bhi_e[DIM], slo_t[DIM + 1], shi_t[DIM + 1], inv_den[DIM + 1];
   __device__ __forceinline__ Excess(const Region<DIM>& g, float c_max) {
 #pragma unroll
-    for (int k = 0; k < DIM; ++k) { blo_e[k] = g.blo[k] - g.epsb; bhi_e[k] = g.bhi[k] + g.epsb; org[k] = g.org[k]; }
+    for (int k = 0; k < DIM; ++k) { blo_e[k] = g.blo[k] - (1.f + EXCESS_PAD) * g.epsb; bhi_e[k] = g.bhi[k] + (1.f + EXCESS_PAD) * g.epsb; org[k] = g.org[k]; }
 #pragma unroll
     for (int f = 0; f <= DIM; ++f) {
-      const float tol = g.ps[f] * (g.sext + c_max);
+      const float tol = g.ps[f] * (g.sext + c_max) + EXCESS_PAD * g.epsb;
       slo_t[f] = g.slo[f] - tol;
       shi_t[f] = g.shi[f] + tol;
       inv_den[f] = 1.f / (1.001f + g.ps[f]);
@@ -201,10 +219,11 @@ template <int DIM>
 __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
     const float* __restrict__ plane_tab, const float* __restrict__ weights, int k1, int R, int64_t n_simplices,
-    float w_limit, float cmax_mult, float cmax_ext, int min_bins, int flags, int max_open, int max_live, int max_in, int adaptive, int leaf_cap, int max_eval, const int32_t* __restrict__ item_list, const int32_t* __restrict__ item_count, WitPlan plan, int32_t* __restrict__ queue, WitOut out, FaceAcc acc,
+    float w_limit, float cmax_mult, float cmax_ext, int min_bins, int flags, int max_open, int max_live, int max_in, int adaptive, int leaf_cap, int max_eval, int sorted_stage, const int32_t* __restrict__ item_list, const int32_t* __restrict__ item_count, WitPlan plan, int32_t* __restrict__ queue, WitOut out, FaceAcc acc,
     unsigned long long* __restrict__ stats) {
   constexpr int DP = padded_dim(DIM);
   __shared__ float4 s_pts[WCAP + 4];
+  static_assert(WCAP % SGRP == 0 && SGRP + 4 <= WTHREADS && SGRP % 4 == 0, "whole groups of stage slots, padded by one pass of the workgroup");
   __shared__ int s_leaf[WLEAF];
   __shared__ uint32_t s_qbuf[WQ + WQ / 2];  // queue of live samples: bounds, then rows (16 bit); focus rounds: point batches
   __shared__ int s_front[2 * WFRONT];       // gather: frontier of the current and the next tree level
@@ -227,6 +246,11 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
   __shared__ int s_off;            // the sweep has switched itself off (see below)
   __shared__ float s_run[2];       // run test: [0] sigma (norm bound of the weights -> space map), [1] absolute rounding term
   __shared__ int s_nrun;           // ... runs that survive it
+  // ordered stage (sorted_stage): cursor of every excess bin - its first slot before the staging pass, the slot behind
+  // its last point after it -; per group of SGRP stage slots the c of the bin of the group's first point (the stage
+  // is ascending in the bin: no point from that slot on has a smaller excess bin)
+  __shared__ int s_cur[NBIN];
+  __shared__ float s_gc[(WCAP + SGRP - 1) / SGRP + 2];
   // (their list lives in the leaf list: dead between the focus rounds of phase 3b and those of phase 5b)
   uint16_t* s_runs = reinterpret_cast<uint16_t*>(s_leaf);
   static_assert(WLEAF * sizeof(int) >= (WROWS / 8) * sizeof(uint16_t), "the run list fits the leaf list (runs of 8 rows or more)");
@@ -466,8 +490,8 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     for (int att = 0; att < 1; ++att) {  // (one try: a region with more leaves than the cap is no case for this sweep)
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
-        qlo[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 1] - s_rg[Region<DIM>::WORDS - 1] - c_max;
-        qhi[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 2] + s_rg[Region<DIM>::WORDS - 1] + c_max;
+        qlo[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 1] - (1.f + EXCESS_PAD) * s_rg[Region<DIM>::WORDS - 1] - c_max;
+        qhi[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 2] + (1.f + EXCESS_PAD) * s_rg[Region<DIM>::WORDS - 1] + c_max;
       }
       int* fa = s_front;
       int* fb = s_front + WFRONT;
@@ -518,7 +542,8 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     __syncthreads();
     WPHASE(2);
     {
-      int cum = s_hist[lane];
+      const int h = s_hist[lane];
+      int cum = h;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
         const int t = __shfl_up(cum, o);
@@ -527,13 +552,15 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       const unsigned long long fit = __ballot(cum <= WCAP);  // (cum is non-decreasing: a prefix of the lanes)
       n_keep_bins = __popcll(fit);
       n_stage = n_keep_bins > 0 ? __shfl(cum, n_keep_bins - 1) : 0;
+      if (sorted_stage && wv == 0) s_cur[lane] = cum - h;   // first slot of every bin (read behind the barrier below)
     }
     WIT_REC(2, s_hist[0]); WIT_REC(3, n_stage); WIT_REC(4, n_keep_bins);
     // (bin 0: the points inside the simplex or within c_max / 64 of it)
     if (s_hist[0] > max_in) WIT_ABANDON(ST_DENSE)
     if (n_keep_bins < min_bins || n_stage == 0) WIT_ABANDON(ST_DENSE)   // too dense for one stage (or nothing near)
     c_sel = (float)n_keep_bins / bin_scale;
-    // ---- 2b. stage the points of the kept bins (any order: a minimum does not care)
+    // ---- 2b. stage the points of the kept bins: in the order of their bins (sorted_stage; any order inside a bin: a
+    // point takes the next slot of its bin's cursor), or in any order at all - a minimum does not care
     __syncthreads();  // (the frontier inside the stage is dead)
     for (int ib = 0; ib < n_cand; ib += WTHREADS * UNR) {
       float x[UNR][DP];
@@ -549,26 +576,47 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       for (int u = 0; u < UNR; ++u) {
         const float eb = excess(x[u]) * bin_scale;
         const bool keep = in[u] && eb < (float)n_keep_bins;   // (the same test as the histogram's: bin < n_keep_bins)
+        float4 v;
+        v.x = x[u][0];
+        v.y = x[u][1];
+        v.z = DIM > 2 ? x[u][DIM > 2 ? 2 : 0] : 0.f;
+        v.w = 0.f;
+        if (sorted_stage) {   // (uniform)
+          if (keep) {
+            // (the bin of 2a, from the same expression: the cursors end where the next bin starts, all below n_stage)
+            const int pos = atomicAdd(&s_cur[(int)eb], 1);
+            if (pos < WCAP) s_pts[pos] = v;
+          }
+          continue;
+        }
         const unsigned long long m = __ballot(keep);
         if (m != 0ull) {
           int base = 0;
           if (lane == 0) base = atomicAdd(&s_ctr[0], __popcll(m));
           base = wave_uniform(base);
-          if (keep) {
-            float4 v;
-            v.x = x[u][0];
-            v.y = x[u][1];
-            v.z = DIM > 2 ? x[u][DIM > 2 ? 2 : 0] : 0.f;
-            v.w = 0.f;
-            s_pts[base + lane_rank(m)] = v;
-          }
+          if (keep) s_pts[base + lane_rank(m)] = v;
         }
       }
     }
     }
     __syncthreads();
-    const int K = s_ctr[0];   // (= n_stage)
-    if (tid < 4) s_pts[K + tid] = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
+    const int K = sorted_stage ? n_stage : s_ctr[0];   // (= n_stage either way)
+    // (+inf rows up to the end of the last group of SGRP slots and four behind it: the pair loops take whole groups)
+    if (K + tid < ((K + SGRP - 1) & ~(SGRP - 1)) + 4) s_pts[K + tid] = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
+    if (sorted_stage && wv == 0) {
+      // s_cur[b] is the slot behind bin b's last point now; the bin of slot j is the number of bins that end at or
+      // before j (empty bins included).  Group g of SGRP slots notes c = bin / bin_scale of its first slot, formed as
+      // c_sel is.
+      const int end = lane < n_keep_bins ? s_cur[lane] : 0x7fffffff;
+      int bin = 0;
+      for (int g = 0; g * SGRP < K; ++g) {
+        const int b = __popcll(__ballot(end <= g * SGRP));
+        if (lane == g) bin = b;
+      }
+      // (bin 0 - the points inside the polytope, which violate no side and may sit on a sample - carries no bound:
+      // c = -inf makes the limit overflow, and an overflowed limit holds the wave)
+      if (lane * SGRP < K) s_gc[lane] = bin > 0 ? (float)bin / bin_scale : -__builtin_inff();
+    }
     // running maxima of this simplex's faces as other workgroups have left them
     if (tid < acc.n_faces)
       s_mf[tid] = __hip_atomic_load(acc.face_bits + acc.slot_of(s, tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -799,7 +847,31 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       const uint32_t mb = crow >= 0 ? acc.memb[crow] : 0u;
       float best = __builtin_inff();
       int wj = 0;
-      for (int j = 0; j < K; j += 4) {
+      float dl;   // inner slack of the sample (held across the loop instead of the region's sixty values)
+      {
+        Region<DIM> rg_;
+        rg_.load(s_rg);
+        dl = rg_.slack(p);
+      }
+      // EARLY EXIT (ordered stage).  Every point from slot j0 on has (int)(e * bin_scale) >= k, k the bin noted for the
+      // group of j0, c = (float)k / bin_scale.  That is the situation of the points that were NOT staged, with
+      // k = n_keep_bins and c = c_sel, on which certification has always rested, and the argument is the same:
+      // (int)eb >= k means fl(e * bin_scale) >= k, so e >= c up to two roundings (the product, the quotient);
+      // the computed e is no larger than the point's true violation of a side of the polytope - Excess gives the
+      // planes' tolerance `tol` and the factor `inv_den` away for that -; the sample lies `dl` inside that side, so
+      // the point is at least e + dl away; and the factor 0.999 (2000 times the roundings of c, e, dl, the sum and
+      // the evaluated pair together) leaves d2(p, x) > limit(dl, c) STRICTLY, in the arithmetic of the pair loop.
+      // A lane with best <= limit can therefore not be lowered - `m < best` is strict, so its witness stays too - by
+      // any point behind j0, and the wave leaves once that holds for all its samples.  Bin 0 is no part of this: its
+      // points violate no side (k = 0 is noted as c = -inf; a limit that overflowed holds the wave).  tests/test_wit_sorted_stage_cpu.py replays this without tolerance.
+      int j0 = 0;
+      for (; j0 < K; j0 += SGRP) {
+        if (sorted_stage) {
+          const float lim = Region<DIM>::limit(dl, s_gc[j0 / SGRP]);
+          if (__ballot(crow >= 0 && !(best <= lim && lim < __builtin_inff())) == 0ull) break;
+        }
+#pragma unroll 2
+      for (int j = j0; j < j0 + SGRP; j += 4) {   // (a whole group: +inf rows behind K)
         float4 x[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) x[u] = s_pts[j + u];
@@ -819,7 +891,8 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
         const float m = __builtin_fminf(__builtin_fminf(d[0], d[1]), __builtin_fminf(d[2], d[3]));
         if (m < best) { best = m; wj = j; }
       }
-      if (lane == 0) count(ST_PAIRS, (unsigned long long)K * 64ull);
+      }
+      if (lane == 0) count(ST_PAIRS, (unsigned long long)(j0 < K ? j0 : K) * 64ull);
       {
         // the witness: the first point of the winning group of four that attains the minimum
         float4 x[4];
@@ -843,9 +916,7 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
         s_wit[3 * c + 1] = w.y;
         s_wit[3 * c + 2] = w.z;
       }
-      Region<DIM> rg_;
-      rg_.load(s_rg);
-      const bool cert = crow >= 0 && best <= rg_.cert_limit(p, c_sel);
+      const bool cert = crow >= 0 && best <= Region<DIM>::limit(dl, c_sel);
       if (stats) { const unsigned long long mc_ = __ballot(cert); if (lane == 0) count(ST_CCERT, (unsigned long long)__popcll(mc_)); }
       deliver(cert, mb, best);
       // coarse samples the stage leaves open: on the list of the focus rounds below
@@ -1056,27 +1127,51 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
       if (n_q < n_q_all && tid == 0) count(ST_UNRES, (unsigned long long)(n_q_all - n_q));
       const int n_rounds_q = (n_q + 63) >> 6;
       const int parts = (n_rounds_q >= WWAVES || (flags & 2)) ? 1 : (n_rounds_q >= 2 ? 2 : 4);
-      const int k_part = (((K + parts - 1) / parts) + 3) & ~3;
+      // a round's sample: row, bound, point, slack; is it still live?  (the maxima have risen since it was queued)
+      auto round_sample = [&](int qi, float& best, float (&p)[DIM], float& dl) -> bool {
+        const bool mine = qi < n_q;
+        const int r = mine ? (int)s_qrow[qi] : 0;
+        best = mine ? __uint_as_float(s_qub[qi]) : 0.f;
+        make_sample(r, p);
+        const uint32_t mb = mine ? acc.memb[r] : 0u;
+        const uint32_t thr = threshold(mb);  // (every lane takes part: wave-wide reductions inside)
+        dl = 0.f;
+        if (sorted_stage) {
+          Region<DIM> rg_;
+          rg_.load(s_rg);
+          dl = rg_.slack(p);
+        }
+        return mine && __float_as_uint(best) > thr;
+      };
+      // (ordered stage) the exit of phase 3 with the queued bound in the place of the running minimum: a lane whose
+      // bound is within the limit of a group's bin needs no point from that group on
+      auto lane_holds = [&](bool act, float best, float dl, int j0) -> bool {
+        const float lim = Region<DIM>::limit(dl, s_gc[j0 / SGRP]);
+        return act && !(best <= lim && lim < __builtin_inff());
+      };
+      // a round shared by several waves is dealt to them in GROUPS of SGRP slots, part i taking every parts-th group
+      // from the i-th on: each wave leaves at the first of ITS groups at which its lanes are done (the limits only
+      // grow along the stage, so no later group holds anything for them), and whatever bound a lane holds - the queued
+      // one, or one another part has lowered meanwhile - is the distance to a real point: the group of the point that
+      // attains a lane's minimum can never pass that lane's test, whichever part it belongs to.  The work is shared
+      // evenly up to the bin the round needs, and the parts need not agree on anything.
       for (int t = wv; t < n_rounds_q * parts; t += WWAVES) {
         const int rnd = t / parts, part = t - rnd * parts;
         const int qi = rnd * 64 + lane;
-        const bool mine = qi < n_q;
-        const int r = mine ? (int)s_qrow[qi] : 0;
-        float best = mine ? __uint_as_float(s_qub[qi]) : 0.f;
-        float p[DIM];
-        make_sample(r, p);
-        const uint32_t mb = mine ? acc.memb[r] : 0u;
-        // still live?  (the maxima have risen since the sample was queued)
-        const uint32_t thr = threshold(mb);  // (every lane takes part: wave-wide reductions inside)
-        const bool act = mine && __float_as_uint(best) > thr;
+        float best, p[DIM], dl;
+        const bool act = round_sample(qi, best, p, dl);
         if (__ballot(act) == 0ull) continue;
         if (part == 0 && lane == 0) count(ST_ROUNDS, 1);
-        const int j1 = (part + 1) * k_part < K ? (part + 1) * k_part : K;
         const float seed = best;
-        for (int j = part * k_part; j < j1; j += 4) {
+        int n_ev = 0;
+        for (int j0 = part * SGRP; j0 < K; j0 += parts * SGRP) {
+          if (sorted_stage && __ballot(lane_holds(act, best, dl, j0)) == 0ull) break;
+          n_ev += j0 + SGRP < K ? SGRP : K - j0;
+#pragma unroll 2
+        for (int j = j0; j < j0 + SGRP; j += 4) {   // (a whole group: +inf rows behind K)
           float4 x[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) x[u] = s_pts[j + u];   // (entries behind K: +inf pads or real points - harmless)
+          for (int u = 0; u < 4; ++u) x[u] = s_pts[j + u];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             float t0 = p[0] - x[u].x;
@@ -1090,7 +1185,8 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
             best = __builtin_fminf(best, d2);
           }
         }
-        if (lane == 0) count(ST_PAIRS, (unsigned long long)(j1 - part * k_part) * 64ull);
+        }
+        if (lane == 0 && n_ev > 0) count(ST_PAIRS, (unsigned long long)n_ev * 64ull);
         if (act && best < seed) atomicMin(&s_qub[qi], __float_as_uint(best));
       }
       __syncthreads();
@@ -1292,7 +1388,7 @@ struct WitOp {
                          item_count, g_wit_surface_pct > 0 ? kind : nullptr, g_wit_surface_pct);
       const int grid = (int)(ns < g_wit_grid ? ns : g_wit_grid);
       hipLaunchKernelGGL((wit_sweep_kernel<DIM>), dim3(grid), dim3(WTHREADS), 0, st, pts, nodes, lv, verts, plane_tab, weights, k1,
-                         R, ns, (float)g_wit_weight, 0.01f * (float)g_wit_cmax_pct, 0.01f * (float)g_wit_cmax_ext_pct, g_wit_min_bins, g_wit_flags, g_wit_max_open, (int)((int64_t)R * g_wit_max_live_pct / 100), (int)((int64_t)R * g_wit_max_in_pct / 100), g_wit_adaptive, g_wit_max_leaves < WLEAF ? g_wit_max_leaves : WLEAF, g_wit_max_eval, item_list, item_count, plan, queue, out, acc,
+                         R, ns, (float)g_wit_weight, 0.01f * (float)g_wit_cmax_pct, 0.01f * (float)g_wit_cmax_ext_pct, g_wit_min_bins, g_wit_flags, g_wit_max_open, (int)((int64_t)R * g_wit_max_live_pct / 100), (int)((int64_t)R * g_wit_max_in_pct / 100), g_wit_adaptive, g_wit_max_leaves < WLEAF ? g_wit_max_leaves : WLEAF, g_wit_max_eval, g_wit_sorted_stage, item_list, item_count, plan, queue, out, acc,
                          stats);
       return check_launch("wit_sweep");
     } else {

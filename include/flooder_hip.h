@@ -428,7 +428,10 @@ int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim
  * finish, tiles flagged, pairs evaluated, excess bins kept; [12:22] cycles per phase in builds with -DFLOODER_WIT_TIMERS -
  * without them [21] = runs of samples dropped by the run test (flooder_fused_witness with a run table only); [22], [23]
  * focus rounds, gather overflows in them}.  Options: "wit_cmax_pct" (250: gather radius in percent of
- * the local point spacing), "wit_min_bins" (6), "wit_grid".
+ * the local point spacing), "wit_min_bins" (6), "wit_grid"; "wit_sorted_stage" (1: the stage is filled in the order of
+ * the excess bins, and a wave leaves a pair loop at the first bin whose points are provably farther than the running
+ * minimum of every sample it holds - "pairs evaluated" counts what was actually evaluated; 0: any order, whole loops;
+ * same face values either way).
  */
 int flooder_wit_max_rows(void);
 int flooder_wit_max_coarse(void);
