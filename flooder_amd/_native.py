@@ -56,7 +56,8 @@ class FusedSweep(_Block):
         p face_bits; p face_slot; p d2_scratch; p flag_list; p flag_count; p flag_key; p flag_hist; p flag_sorted; p top;
         p top_list; p top_count; p simplex_weight; p plane_scratch; p wit_queue; p wit_item_list; p wit_stats;
         p cell_queue; p defer_list; p defer_c; p defer_ctl; p light_list; p heavy_list; p cell_stats; p finish_ctl;
-        p hard_scratch; i32 hard_cap; i32 probed; p finish_stats; p wit_runs; i32 wit_run_len; i32 wit_n_runs""")
+        p hard_scratch; i32 hard_cap; i32 probed; p finish_stats; p wit_runs; i32 wit_run_len; i32 wit_n_runs;
+        i32 planes_ready; i32 reserved""")
 
 
 class SortedSweep(_Block):
@@ -99,6 +100,7 @@ SIGNATURES = {
     "flooder_last_error": (c_char_p, []),
     "flooder_device_arch": (c_int, [c_int, c_char_p, c_int]),
     "flooder_set_option": (c_int, [c_char_p, c_int]),
+    "flooder_get_option": (c_int, [c_char_p, ctypes.POINTER(c_int)]),
     "flooder_padded_dim": (c_int, [c_int]),
     "flooder_ball_count_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int64, c_void_p, c_void_p]),

@@ -1477,14 +1477,14 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             blk.wit_queue, blk.wit_item_list, blk.wit_stats = qwit.data_ptr(), split[0].data_ptr(), _native.ptr(wst) or None
             if WIT_RUNS and plan.wit_runs is not None:   # (run test of its pass over all samples)
                 blk.wit_runs, blk.wit_run_len, blk.wit_n_runs = plan.wit_runs[0].data_ptr(), plan.wit_runs[1], plan.wit_runs[2]
+        # (flooder_simplex_prepare_f32 above has written the plane rows of these verts on this stream; else the first of
+        # the two entries writes them for the second)
+        blk.planes_ready = 1 if CELL_SUPER and SWEEP_PREPARE_FUSED else 0
         with _span(timer, "sweep"):
-            try:
-                if use_wit:
-                    _native.check(lib.flooder_fused_witness(ctypes.byref(blk), st), "flooder_fused_witness")
-                _native.check(lib.flooder_fused_cell(ctypes.byref(blk), st), "flooder_fused_cell")
-            except Exception:
-                lib.flooder_simplex_planes_forget()   # (the note flooder_simplex_prepare_f32 left for these two launches)
-                raise
+            if use_wit:
+                _native.check(lib.flooder_fused_witness(ctypes.byref(blk), st), "flooder_fused_witness")
+                blk.planes_ready = 1
+            _native.check(lib.flooder_fused_cell(ctypes.byref(blk), st), "flooder_fused_cell")
         with _span(timer, "fallback"):
             _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
         if stats is not None:  # (diagnostic runs only: a host synchronisation)

@@ -193,7 +193,7 @@ struct DeferList {
   int64_t tail_items = INT64_MAX;  // only the last so many items of the chunk launch hand dense chunks on to the tiles
   int listed_first = 1;  // chunk launch: the deferred chunks ahead of the heavy simplices (0: behind them)
   int chunk_major = 0;   // chunk launch: pilots first - chunk 0 of every heavy simplex ahead of all other chunks (2: always)
-  int pilot_min_items = 262144;  // ... also where the heavy list has at least this many chunks (option "cell_chunk_major_max")
+  int pilot_min_items = 262144;  // ... also where the heavy list has at least this many chunks (long queues: cfg 5; a constant, not an option)
   int drop = 0;          // cell query: interior samples whose running minimum cannot raise the simplex's maximum stop early
 };
 
@@ -1616,7 +1616,8 @@ struct CellOp {
   static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, float* plane_tab,
                  const float* weights, int k1, int R, int64_t ns, float alpha, int32_t* queue,
                  uint32_t* out, int32_t* flag_list, int32_t* flag_count, unsigned long long* stats,
-                 FaceAcc acc, DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, hipStream_t st) {
+                 FaceAcc acc, DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, bool planes_ready,
+                 hipStream_t st) {
     if constexpr (DIM == 2 || DIM == 3) {
       if (!g_cell_density_grid) dg = DensGrid{};
       dg.min_count = g_cell_density_grid;
@@ -1625,7 +1626,7 @@ struct CellOp {
       // persistent blocks of 4 independent waves: 3 per CU fit, but a short queue is swept faster by fewer
       // waves (its longest chunks then share their SIMD with fewer others): about 48 chunks per block,
       // measured on 1/4 and 1/8 shares of cfg 2
-      if (!planes_are_done(verts, plane_tab, ns, st))
+      if (!planes_ready)
         hipLaunchKernelGGL((simplex_planes_kernel<DIM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, verts, k1, ns,
                            plane_tab);
       constexpr int CHUNK = 64 * SPL_CHUNK;
@@ -1652,7 +1653,6 @@ struct CellOp {
       // cfg 5, 504 k chunks: sweep 6.51 -> 6.42 ms; in between - cfg 3, 110 k chunks, every simplex heavy - it costs
       // 0.4 %; option "cell_chunk_major" 2: always)
       dl.chunk_major = g_cell_chunk_major == 2 ? 2 : ((g_cell_chunk_major && n_chunks > ns) ? 1 : 0);
-      dl.pilot_min_items = g_cell_chunk_major_max;
       dl.drop = g_cell_drop;
       CellParams cp{pts, nodes, lv, verts, plane_tab, weights, k1, R, ns, alpha, g_cell_exh_dense, g_cell_exh_sparse,
                     brute_max, g_cell_tries, g_cell_exh_tries, g_cell_retry_pct, g_cell_retry_keep, queue, out, flag_list,
@@ -1688,19 +1688,6 @@ struct CellOp {
 }  // namespace
 
 namespace flooder {
-namespace {
-struct PlanesDone { const float* verts; const float* tab; int64_t ns; hipStream_t st; };
-thread_local PlanesDone g_planes_done = {nullptr, nullptr, 0, nullptr};
-}  // namespace
-void planes_done_for(const float* verts, const float* tab, int64_t n_simplices, hipStream_t st) {
-  g_planes_done = PlanesDone{verts, tab, n_simplices, st};
-}
-bool planes_are_done(const float* verts, const float* tab, int64_t n_simplices, hipStream_t st) {
-  const bool hit = g_planes_done.verts == verts && g_planes_done.tab == tab && g_planes_done.ns == n_simplices &&
-                   g_planes_done.st == st && verts != nullptr;
-  g_planes_done = PlanesDone{nullptr, nullptr, 0, nullptr};
-  return hit;
-}
 int launch_simplex_planes(int dim, const float* verts, int k1, int64_t n_simplices, float* tab, hipStream_t st) {
   if (dim == 2)
     hipLaunchKernelGGL((simplex_planes_kernel<2>), dim3((unsigned)((n_simplices + 255) / 256)), dim3(256), 0, st, verts, k1,
@@ -1960,7 +1947,8 @@ __global__ __launch_bounds__(256) void density_leaves_kernel(const float* __rest
 int sweep_cell_entry(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
                      float* plane_tab, const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
                      uint32_t* out_d2, int32_t* flag_list, int32_t* flag_count, uint64_t* stats, FaceAcc acc,
-                     DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, void* stream, const char* who) {
+                     DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, bool planes_ready, void* stream,
+                     const char* who) {
   if (n_simplices == 0 || R == 0) return FLOODER_OK;
   if (!pts_sorted || !nodes || !verts || !plane_tab || !weights || !queue || !out_d2 || !flag_list || !flag_count ||
       n_pts < 1 || k1 < 1 || k1 > FLOODER_MAX_VERTS || R < 0 || !(alpha > 0.f))
@@ -1975,35 +1963,20 @@ int sweep_cell_entry(const float* pts_sorted, int64_t n_pts, int dim, const floa
     return fail(FLOODER_E_ARG, "cell sweep: cloud too large for the cell sweep (use the tree sweep)");
   return dispatch_dim<CellOp>(dim, pts_sorted, nodes, lv, verts, plane_tab, weights, k1, R, n_simplices, alpha, queue,
                               out_d2, flag_list, flag_count, reinterpret_cast<unsigned long long*>(stats), acc,
-                              dl, queue2, queue3, dg, (hipStream_t)stream);
+                              dl, queue2, queue3, dg, planes_ready, (hipStream_t)stream);
 }
 
 }  // namespace
 
-extern "C" {
-
-int flooder_sweep_cell_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
-                           const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
-                           float alpha, int32_t* queue, uint32_t* out_d2, int32_t* flag_list, int32_t* flag_count,
-                           float* plane_scratch, const int32_t* density_grid, const float* cloud_box, uint64_t* stats,
-                           void* stream) {
-  DensGrid dg;
-  if (density_grid && cloud_box) { dg.grid = density_grid; dg.box = cloud_box; }
-  return sweep_cell_entry(pts_sorted, n_pts, dim, nodes, verts, plane_scratch, weights, k1, R, n_simplices, alpha, queue, out_d2,
-                          flag_list, flag_count, stats, FaceAcc{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr},
-                          DeferList{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr, dg, stream,
-                          "flooder_sweep_cell_f32: bad argument");
-}
-
-int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
-                                 const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
-                                 float alpha, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb,
-                                 int n_faces, uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list,
-                                 int32_t* flag_count, uint32_t* flag_key, int32_t* flag_hist, uint64_t* top,
-                                 int32_t* top_list, int32_t* top_count, int32_t* defer_list,
-                                 float* defer_c, int32_t* defer_ctl, const float* simplex_weight,
-                                 int32_t* light_list, int32_t* heavy_list, float* plane_scratch,
-                                 const int32_t* density_grid, const float* cloud_box, uint64_t* stats, void* stream) {
+// flooder_sweep_cell_faces_f32 plus `planes_ready` (flood_common.hpp; the parameter-block form passes its field)
+int flooder::sweep_cell_faces(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
+                              const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
+                              uint32_t* d2_scratch, const uint32_t* memb, int n_faces, uint32_t* face_bits,
+                              const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count, uint32_t* flag_key,
+                              int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count, int32_t* defer_list,
+                              float* defer_c, int32_t* defer_ctl, const float* simplex_weight, int32_t* light_list,
+                              int32_t* heavy_list, float* plane_scratch, const int32_t* density_grid,
+                              const float* cloud_box, uint64_t* stats, bool planes_ready, void* stream) {
   if (n_simplices == 0 || R == 0) return FLOODER_OK;
   DensGrid dg;
   if (density_grid && cloud_box) { dg.grid = density_grid; dg.box = cloud_box; }
@@ -2050,8 +2023,38 @@ int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim
                           d2_scratch, flag_list, flag_count, stats,
                           FaceAcc{memb, face_bits, n_faces, reinterpret_cast<unsigned long long*>(top), top_list,
                                   top_count, face_slot, flag_key, flag_hist},
-                          dl, queue + FLOODER_QUEUE_WORDS, queue + 2 * FLOODER_QUEUE_WORDS, dg,
+                          dl, queue + FLOODER_QUEUE_WORDS, queue + 2 * FLOODER_QUEUE_WORDS, dg, planes_ready,
                           stream, "flooder_sweep_cell_faces_f32: bad argument");
+}
+
+extern "C" {
+
+int flooder_sweep_cell_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
+                           const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
+                           float alpha, int32_t* queue, uint32_t* out_d2, int32_t* flag_list, int32_t* flag_count,
+                           float* plane_scratch, const int32_t* density_grid, const float* cloud_box, uint64_t* stats,
+                           void* stream) {
+  DensGrid dg;
+  if (density_grid && cloud_box) { dg.grid = density_grid; dg.box = cloud_box; }
+  return sweep_cell_entry(pts_sorted, n_pts, dim, nodes, verts, plane_scratch, weights, k1, R, n_simplices, alpha, queue, out_d2,
+                          flag_list, flag_count, stats, FaceAcc{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr},
+                          DeferList{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr, dg, false,
+                          stream, "flooder_sweep_cell_f32: bad argument");
+}
+
+int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
+                                 const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
+                                 float alpha, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb,
+                                 int n_faces, uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list,
+                                 int32_t* flag_count, uint32_t* flag_key, int32_t* flag_hist, uint64_t* top,
+                                 int32_t* top_list, int32_t* top_count, int32_t* defer_list,
+                                 float* defer_c, int32_t* defer_ctl, const float* simplex_weight,
+                                 int32_t* light_list, int32_t* heavy_list, float* plane_scratch,
+                                 const int32_t* density_grid, const float* cloud_box, uint64_t* stats, void* stream) {
+  return sweep_cell_faces(pts_sorted, n_pts, dim, nodes, verts, weights, k1, R, n_simplices, alpha, queue, d2_scratch, memb,
+                          n_faces, face_bits, face_slot, flag_list, flag_count, flag_key, flag_hist, top, top_list, top_count,
+                          defer_list, defer_c, defer_ctl, simplex_weight, light_list, heavy_list, plane_scratch,
+                          density_grid, cloud_box, stats, false, stream);
 }
 
 

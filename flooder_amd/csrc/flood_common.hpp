@@ -11,77 +11,14 @@ namespace flooder {
 
 constexpr uint32_t INF_BITS = 0x7f800000u;
 
-extern int g_bvh_ks;
-extern int g_bvh_subs;
-extern int g_bvh_grid;
-extern int g_cell_grid;
-extern int g_cell_exh_dense;
-extern int g_bvh_leaf_batch;
-extern int g_bvh_refine_pct;
-extern int g_cell_exh_sparse;
-extern int g_cell_brute_max;
-extern int g_finish_focus_pct;
-extern int g_finish_refresh;
-extern int g_cell_tries;
-extern int g_cell_super_weight;
-extern int g_cell_super_n0;
-extern int g_cell_super_sparse;
-extern int g_cell_super_min_chunks;
-extern int g_cell_density_grid;
-extern int g_cell_chunks_per_block;  // cell sweep: chunks per persistent workgroup that size a short queue's launch
-extern int g_cell_weight_classes;   // cell sweep: the simplex lists in descending weight class (0: in the given order)
-extern int g_cell_listed_first;     // cell sweep, chunk launch: deferred chunks ahead of the heavy simplices
-extern int g_cell_tail_waves;       // cell_tiles = 2: the tail = the last (this percentage of the launch's waves) items
-extern int g_cell_chunk_major;    // cell sweep, chunk launch: heavy simplices chunk by chunk (all first chunks, then all second ones ...)
-extern int g_cell_chunk_major_max;  // ... also for heavy lists of at least this many chunks (long queues: cfg 5)
-extern int g_cell_drop;           // cell query drops interior samples that cannot raise the simplex's maximum
-extern int g_cell_one_pass;         // cell sweep: dense chunks are classified and evaluated in ONE pass over their candidates
-extern int g_cell_queue_block;     // cell sweep: log2 of the item blocks of the XCD-local work queue (-1: interleaved items, any XCD)
-extern int g_cell_min_grid;          // ... and the smallest launch  // > 0: the cell sweep reads the local density from the index's density grid where every probed cell holds at least this many points (no first tree walk there); 0: never
-extern int g_sorted_ks;
-extern int g_sorted_blocks;
-extern int g_sorted_batch_pct;  // sorted sweep: a batch of leaf tests = the bounds within this % of the nearest one (100: one leaf)
-extern int g_sorted_refresh;  // fused sorted sweep: evaluated leaves between two readings of the face maxima
-extern int g_cell_tiles;   // 1: dense chunks hand their tiles to a third launch (one sample per lane) instead of the exhaustive loop (measured slower: off)
-extern int g_curve_bits;
-extern int g_cell_exh_tries;
-extern int g_cell_retry_keep;  // ... and the attempt may have kept at most this many points per chunk
-extern int g_cell_retry_pct;  // share (percent) of a chunk's open samples that must have a point within twice the cell size for a second try (0: always)
-extern int g_finish_items_cap;
-extern int g_finish_budget_min;  // leaves a tile of a SHORT list may evaluate before it counts as hard
-extern int g_cell_surface_pct;    // cell sweep: one cell size per chunk on clouds with less than this percentage of their points in interior cells of the density grid (0: never)
-extern int g_cell_split_launches;  // cell sweep, long queue: light / heavy lists by 1 launch (class_order_kernel) or the 2 of rounds 3 - 5
-extern int g_sort_shape;  // flooder_index_sort_zeroed: block shape of the radix passes (0: by cloud size; 1 small, 2 the library's, 3 large)
-extern int g_finish_wide_points;  // clouds of at least this many points run the finish's per-wave passes with 8 waves per workgroup (0: never)
-extern int g_finish_budget;  // scale of the leaf budget beyond which a tile of the finish counts as hard (0: off)
-extern int g_finish_top;     // 1: the finish settles one sample per simplex (its largest bound) before everything else
-extern int g_finish_order;   // 1: the finish works the flagged tiles off by descending probe bound
-extern int g_fps_switch;
-extern int g_fps_rpl;
-extern int g_fps_lane_best;  // 1: batched FPS ranks one candidate per lane at most (the > 64 candidates path; test hook)
-extern int g_fps_rounds;  // 1: batched FPS enqueues rounds of launches and reads the counter back between them
-extern int g_curve;
-extern int g_wit_weight;    // witness sweep: heaviest simplex (points in its box) it tries
-extern int g_wit_cmax_pct;  // ... its gather radius in percent of the local point spacing
-extern int g_wit_grid;      // ... its persistent one-wave workgroups
-extern int g_wit_cmax_ext_pct;
-extern int g_wit_flags;
-extern int g_wit_adaptive;
-extern int g_wit_max_open;
-extern int g_wit_max_eval;
-extern int g_wit_max_leaves;
-extern int g_wit_max_in_pct;
-extern int g_wit_max_live_pct;
-extern int g_wit_min_bins;  // ... excess bins (of 64) the stage must hold at least
-extern int g_wit_sorted_stage;  // ... 1: its stage is ordered by excess bin and its pair loops stop early
-extern int g_wit_runs;  // ... 1: the run test of its pass over all samples, where a run table is handed in
-extern int g_wit_surface_pct;  // ... and no attempt on a cloud with less than this percentage of its points in interior cells (0: always)
+// the tuning options, one `extern int g_<name>;` per row of flood_options.def (defined in flood_kernels.hip)
+#define FLOODER_OPTION(name, def, lo, hi, desc) extern int g_##name;
+#define FLOODER_OPTION_LIST(name, def, desc, ...) extern int g_##name;
+#include "flood_options.def"
+#undef FLOODER_OPTION
+#undef FLOODER_OPTION_LIST
 // face planes of every simplex (flood_cell.hip: simplex_planes_kernel), 24 floats per simplex
 int launch_simplex_planes(int dim, const float* verts, int k1, int64_t n_simplices, float* tab, hipStream_t st);
-// the witness sweep's entry has just filled `tab` for these simplices on this stream: the cell sweep's entry, called
-// next with the same buffers, skips its own launch (consumed by the first match; any other call clears it)
-void planes_done_for(const float* verts, const float* tab, int64_t n_simplices, hipStream_t st);
-bool planes_are_done(const float* verts, const float* tab, int64_t n_simplices, hipStream_t st);
 char* err_buf();
 int fail(int code, const char* msg);
 int check_launch(const char* what);
@@ -414,13 +351,23 @@ inline void launch_cloud_kind(int dim, int32_t* grid, hipStream_t st) {   // gri
 }
 
 // flood_wit.hip: flooder_sweep_witness_f32 with the index's density grid and the run table of the witness plan (what
-// flooder_fused_witness calls; runs NULL / n_runs 0: no run test)
+// flooder_fused_witness calls; runs NULL / n_runs 0: no run test).  planes_ready: the caller vouches that plane_scratch
+// holds the plane rows of exactly these verts, written earlier on this stream (flooder_fused_sweep_t) - no plane launch
 int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
                   const float* weights, int k1, int R, int64_t n_simplices, const int32_t* coarse_rows, int n_coarse,
                   const uint32_t* parents, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb, int n_faces,
                   uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count,
                   uint32_t* flag_key, int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count,
                   float* simplex_weight, int32_t* item_list, float* plane_scratch, uint64_t* stats,
-                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, void* stream);
+                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, bool planes_ready,
+                  void* stream);
+// flood_cell.hip: flooder_sweep_cell_faces_f32 with the same flag (what flooder_fused_cell calls)
+int sweep_cell_faces(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
+                     const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
+                     uint32_t* d2_scratch, const uint32_t* memb, int n_faces, uint32_t* face_bits, const int32_t* face_slot,
+                     int32_t* flag_list, int32_t* flag_count, uint32_t* flag_key, int32_t* flag_hist, uint64_t* top,
+                     int32_t* top_list, int32_t* top_count, int32_t* defer_list, float* defer_c, int32_t* defer_ctl,
+                     const float* simplex_weight, int32_t* light_list, int32_t* heavy_list, float* plane_scratch,
+                     const int32_t* density_grid, const float* cloud_box, uint64_t* stats, bool planes_ready, void* stream);
 
 }  // namespace flooder

@@ -915,7 +915,6 @@ struct WeightOp {
     else if (plane_tab) return fail(FLOODER_E_ARG, "flooder_simplex_prepare_f32: plane rows only in dim 2 and 3");
     hipLaunchKernelGGL((simplex_weight_kernel<DIM>), dim3((int)(blocks + plane_blocks)), dim3(256), 0, st, nodes, lv, verts,
                        k1, ns, weight, (int)blocks, plane_tab, zero_buf, zero_words);
-    if (plane_blocks) planes_done_for(verts, plane_tab, ns, st);   // (the sweep's entries need not launch theirs)
     return check_launch("simplex_weight");
   }
 };
@@ -932,7 +931,7 @@ extern "C" int flooder_simplex_weight_f32(const float* nodes, int64_t n_pts, int
                                 (int64_t)0, (hipStream_t)stream);
 }
 
-extern "C" void flooder_simplex_planes_forget(void) { (void)planes_are_done(nullptr, nullptr, 0, nullptr); }
+extern "C" void flooder_simplex_planes_forget(void) {}   // (kept so that existing callers link: include/flooder_hip.h)
 
 extern "C" int flooder_simplex_prepare_f32(const float* nodes, int64_t n_pts, int dim, const float* verts, int k1,
                                            int64_t n_simplices, float* weight, float* plane_scratch, int32_t* zero_buf,

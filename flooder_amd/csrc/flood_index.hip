@@ -714,11 +714,6 @@ void os_passes(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals
     to_output = !to_output;
   }
 }
-}  // namespace
-
-namespace flooder { int g_sort_shape = 0; }
-
-namespace {
 int64_t os_state_words(int64_t n, int key_bits) {
   if (n < 1 || n >= (1LL << 30) || key_bits < 1 || key_bits > 32) return 0;
   const int64_t places = os_places(key_bits);

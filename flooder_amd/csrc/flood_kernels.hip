@@ -20,6 +20,8 @@
 //
 // Work is pulled from device-side queues (atomic head) so heavy-tailed candidate counts balance.
 
+#include <limits.h>
+
 #include "flood_common.hpp"
 
 namespace flooder {
@@ -41,11 +43,44 @@ int check_launch(const char* what) {
   return FLOODER_OK;
 }
 
+// the tuning options (flood_options.def): their one definition, with the defaults
+#define FLOODER_OPTION(name, def, lo, hi, desc) int g_##name = def;
+#define FLOODER_OPTION_LIST(name, def, desc, ...) int g_##name = def;
+#include "flood_options.def"
+#undef FLOODER_OPTION
+#undef FLOODER_OPTION_LIST
+
 }  // namespace flooder
 
 using namespace flooder;
 
 namespace {
+
+// ... and the table flooder_set_option / flooder_get_option walk: a value is accepted inside [lo, hi], or, where the
+// row lists its values, when it is one of them
+struct Option {
+  const char* name;
+  int* value;
+  int lo, hi;
+  int n_list;
+  int list[8];
+};
+template <typename... T>
+constexpr int count_of(T...) { return (int)sizeof...(T); }
+#define FLOODER_OPTION(name, def, lo, hi, desc) {#name, &g_##name, lo, hi, 0, {}},
+#define FLOODER_OPTION_LIST(name, def, desc, ...) {#name, &g_##name, 0, 0, count_of(__VA_ARGS__), {__VA_ARGS__}},
+const Option OPTIONS[] = {
+#include "flood_options.def"
+};
+#undef FLOODER_OPTION
+#undef FLOODER_OPTION_LIST
+
+const Option* find_option(const char* name) {
+  if (name)
+    for (const Option& o : OPTIONS)
+      if (strcmp(name, o.name) == 0) return &o;
+  return nullptr;
+}
 
 constexpr int SCAN_PARTS = 8;        // each simplex's slab is scanned by 8 independent work units
 constexpr int SCAN_THREADS = 256;
@@ -53,8 +88,6 @@ constexpr int SWEEP_THREADS = 256;   // 4 independent waves per block
 constexpr int KS = 8;                // samples per lane  -> 512 samples per wave tile
 constexpr int CHUNK = FLOODER_SWEEP_CHUNK;
 static_assert(64 * KS == FLOODER_TILE_SAMPLES, "tile size");
-
-int g_sweep_variant = 0;  // 0 = packed fp32 (v_pk_*), 1 = plain fp32; flooder_set_option("sweep_variant")
 
 // ---------------------------------------------------------------------------------- ball scan
 // Work unit g = simplex * SCAN_PARTS + part.  Blocks stride over the units (uniform cost per point).
@@ -638,267 +671,22 @@ const char* flooder_last_error(void) { return err_buf(); }
 int flooder_padded_dim(int dim) { return padded_dim(dim); }
 
 int flooder_set_option(const char* name, int value) {
-  if (name && strcmp(name, "sweep_variant") == 0 && (value == 0 || value == 1)) {
-    g_sweep_variant = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "bvh_ks") == 0 && (value == 0 || value == 1 || value == 2 || value == 4 || value == 8)) {
-    g_bvh_ks = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "bvh_refine_pct") == 0 && value >= 1) {
-    g_bvh_refine_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "bvh_leaf_batch") == 0 && (value == 1 || value == 4)) {
-    g_bvh_leaf_batch = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "curve") == 0 && (value == 0 || value == 1)) {
-    g_curve = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_exh_sparse") == 0 && value >= 480) {
-    g_cell_exh_sparse = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_budget_min") == 0 && value >= 1) {
-    g_finish_budget_min = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "sort_shape") == 0 && value >= 0 && value <= 3) {
-    g_sort_shape = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_split_launches") == 0 && (value == 1 || value == 2)) {
-    g_cell_split_launches = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_surface_pct") == 0 && value >= 0 && value <= 100) {
-    g_cell_surface_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_wide_points") == 0 && value >= 0) {
-    g_finish_wide_points = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_refresh") == 0 && value >= 1) {
-    g_finish_refresh = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_focus_pct") == 0 && value >= 0 && value <= 100) {
-    g_finish_focus_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "fps_switch") == 0 && value >= 0) {
-    g_fps_switch = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "fps_lane_best") == 0 && (value == 0 || value == 1)) {
-    g_fps_lane_best = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "fps_rounds") == 0 && (value == 0 || value == 1)) {
-    g_fps_rounds = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "fps_rpl") == 0 && (value == 0 || value == 1 || value == 4)) {
-    g_fps_rpl = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_exh_tries") == 0 && value >= 0 && value <= 8) {
-    g_cell_exh_tries = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_items_cap") == 0 && value >= 1024) {
-    g_finish_items_cap = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_budget") == 0 && value >= 0) {
-    g_finish_budget = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_top") == 0 && (value == 0 || value == 1)) {
-    g_finish_top = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_retry_keep") == 0 && value >= 0) {
-    g_cell_retry_keep = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_retry_pct") == 0 && value >= 0) {
-    g_cell_retry_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "finish_order") == 0 && (value == 0 || value == 1)) {
-    g_finish_order = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "curve_bits") == 0 && value >= 0 && value <= 21) {
-    g_curve_bits = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_super_weight") == 0 && value >= 0) {
-    g_cell_super_weight = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_chunks_per_block") == 0 && value >= 1) {
-    g_cell_chunks_per_block = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_weight_classes") == 0 && (value == 0 || value == 1)) {
-    g_cell_weight_classes = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_listed_first") == 0 && (value == 0 || value == 1)) {
-    g_cell_listed_first = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_tail_waves") == 0 && value >= 0) {
-    g_cell_tail_waves = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_weight") == 0 && value >= 0) {
-    g_wit_weight = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_cmax_pct") == 0 && value >= 10 && value <= 10000) {
-    g_wit_cmax_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_cmax_ext_pct") == 0 && value >= 1 && value <= 10000) {
-    g_wit_cmax_ext_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_max_in_pct") == 0 && value >= 0) {
-    g_wit_max_in_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_max_leaves") == 0 && value >= 1) {
-    g_wit_max_leaves = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_chunk_major") == 0 && (value == 0 || value == 1 || value == 2)) {
-    g_cell_chunk_major = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_drop") == 0 && (value == 0 || value == 1)) {
-    g_cell_drop = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "sorted_batch_pct") == 0 && value >= 100) {
-    g_sorted_batch_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "sorted_blocks") == 0 && value >= 0) {
-    g_sorted_blocks = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "sorted_refresh") == 0 && value >= 1) {
-    g_sorted_refresh = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_max_eval") == 0 && value >= 0) {
-    g_wit_max_eval = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_max_open") == 0 && value >= 0) {
-    g_wit_max_open = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_max_live_pct") == 0 && value >= 0 && value <= 100) {
-    g_wit_max_live_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_adaptive") == 0 && (value == 0 || value == 1)) {
-    g_wit_adaptive = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_flags") == 0 && value >= 0) {
-    g_wit_flags = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_grid") == 0 && value >= 1) {
-    g_wit_grid = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_runs") == 0 && (value == 0 || value == 1)) {
-    g_wit_runs = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_sorted_stage") == 0 && (value == 0 || value == 1)) {
-    g_wit_sorted_stage = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_surface_pct") == 0 && value >= 0 && value <= 100) {
-    g_wit_surface_pct = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "wit_min_bins") == 0 && value >= 1 && value <= 64) {
-    g_wit_min_bins = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_one_pass") == 0 && value >= 0 && value <= 100000) {
-    g_cell_one_pass = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_queue_block") == 0 && value >= -1 && value <= 12) {
-    g_cell_queue_block = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_min_grid") == 0 && value >= 1) {
-    g_cell_min_grid = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_super_min_chunks") == 0 && value >= 0) {
-    g_cell_super_min_chunks = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_super_sparse") == 0 && value >= 0) {
-    g_cell_super_sparse = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_super_n0") == 0 && value >= 0) {
-    g_cell_super_n0 = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_density_grid") == 0 && value >= 0) {
-    g_cell_density_grid = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "sorted_ks") == 0 && (value == 1 || value == 2)) {
-    g_sorted_ks = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_tiles") == 0 && value >= 0 && value <= 2) {
-    g_cell_tiles = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_tries") == 0 && value >= 1 && value <= 8) {
-    g_cell_tries = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_brute_max") == 0 && value >= 0) {
-    g_cell_brute_max = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_exh_dense") == 0 && value >= 512) {
-    g_cell_exh_dense = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "cell_grid") == 0 && value >= 1 && value <= 65536) {
-    g_cell_grid = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "bvh_grid") == 0 && value >= 1 && value <= 65536) {
-    g_bvh_grid = value;
-    return FLOODER_OK;
-  }
-  if (name && strcmp(name, "bvh_subs") == 0 && value >= 1 && value <= 64 && (value & (value - 1)) == 0) {
-    g_bvh_subs = value;
-    return FLOODER_OK;
+  if (const Option* o = find_option(name)) {
+    bool ok = o->n_list == 0 && value >= o->lo && value <= o->hi;
+    for (int i = 0; i < o->n_list; ++i) ok = ok || value == o->list[i];
+    if (ok) {
+      *o->value = value;
+      return FLOODER_OK;
+    }
   }
   return fail(FLOODER_E_ARG, "flooder_set_option: unknown option or value");
+}
+
+int flooder_get_option(const char* name, int* value) {
+  const Option* o = find_option(name);
+  if (!o || !value) return fail(FLOODER_E_ARG, "flooder_get_option: unknown option or null pointer");
+  *value = *o->value;
+  return FLOODER_OK;
 }
 
 int flooder_device_arch(int device, char* buf, int buflen) {

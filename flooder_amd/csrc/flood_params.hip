@@ -1,6 +1,7 @@
 // flood_params.hip - the parameter-block forms of the long entry points (include/flooder_hip.h, "parameter blocks"):
 // one struct, bound by field name, instead of up to 34 positional arguments.  Each forwards to the positional function
-// of the same launch; nothing here touches the device.
+// of the same launch (the witness and the cell sweep: to the internal form that also takes `planes_ready`); nothing here
+// touches the device.
 #include "../../include/flooder_hip.h"
 #include "flood_common.hpp"
 
@@ -29,17 +30,17 @@ extern "C" int flooder_fused_witness(const flooder_fused_sweep_t* p, void* strea
                                 a.coarse_rows, a.n_coarse, a.parents, a.wit_queue, a.d2_scratch, a.memb, a.n_faces,
                                 a.face_bits, a.face_slot, a.flag_list, a.flag_count, a.flag_key, a.flag_hist, a.top,
                                 a.top_list, a.top_count, a.simplex_weight, a.wit_item_list, a.plane_scratch, a.wit_stats,
-                                a.density_grid, a.wit_runs, a.wit_run_len, a.wit_n_runs, stream);
+                                a.density_grid, a.wit_runs, a.wit_run_len, a.wit_n_runs, a.planes_ready != 0, stream);
 }
 
 extern "C" int flooder_fused_cell(const flooder_fused_sweep_t* p, void* stream) {
   flooder_fused_sweep_t a;
   if (int rc = take(p, a, "flooder_fused_cell: bad parameter block (abi / size)")) return rc;
-  return flooder_sweep_cell_faces_f32(a.pts_sorted, a.n_pts, a.dim, a.nodes, a.verts, a.weights, a.k1, a.R, a.n_simplices,
-                                      a.alpha, a.cell_queue, a.d2_scratch, a.memb, a.n_faces, a.face_bits, a.face_slot,
-                                      a.flag_list, a.flag_count, a.flag_key, a.flag_hist, a.top, a.top_list, a.top_count,
-                                      a.defer_list, a.defer_c, a.defer_ctl, a.simplex_weight, a.light_list, a.heavy_list,
-                                      a.plane_scratch, a.density_grid, a.cloud_box, a.cell_stats, stream);
+  return flooder::sweep_cell_faces(a.pts_sorted, a.n_pts, a.dim, a.nodes, a.verts, a.weights, a.k1, a.R, a.n_simplices,
+                                   a.alpha, a.cell_queue, a.d2_scratch, a.memb, a.n_faces, a.face_bits, a.face_slot,
+                                   a.flag_list, a.flag_count, a.flag_key, a.flag_hist, a.top, a.top_list, a.top_count,
+                                   a.defer_list, a.defer_c, a.defer_ctl, a.simplex_weight, a.light_list, a.heavy_list,
+                                   a.plane_scratch, a.density_grid, a.cloud_box, a.cell_stats, a.planes_ready != 0, stream);
 }
 
 extern "C" int flooder_fused_finish(const flooder_fused_sweep_t* p, void* stream) {

@@ -20,8 +20,6 @@
 
 using namespace flooder;
 
-namespace flooder { int g_sorted_ks = 1; int g_sorted_refresh = 4; int g_sorted_blocks = 0; int g_sorted_batch_pct = 400; }  // samples per lane of the sorted sweep (option "sorted_ks": 1 or 2)
-
 namespace {
 
 constexpr float SAFE = 0.99999f;

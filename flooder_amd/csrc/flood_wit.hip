@@ -35,27 +35,6 @@
 
 using namespace flooder;
 
-namespace flooder {
-int g_wit_weight = 800;     // simplices with at most this many cloud points in their box (flooder_simplex_weight_f32) are tried
-int g_wit_cmax_pct = 250;   // c_max in percent of the local point spacing
-int g_wit_grid = 256 * 4;   // persistent workgroups (one simplex at a time each)
-int g_wit_min_bins = 48;    // (measured: sparse simplices of a Gaussian keep 50 - 64 bins, the slivers along a surface 10 - 25)
-//    // the stage must hold the points of at least this many of the 64 excess bins
-int g_wit_max_in_pct = 8;   // points inside the simplex itself, in percent of its samples, it may hold at most (denser: every sample has a nearest point of its own, nothing to share)
-int g_wit_max_leaves = 400; // leaves (16 points each) the region around a simplex may overlap; more: too dense around it, no attempt
-int g_wit_max_eval = 768;   // queued samples an item evaluates against its stage at most (the rest: to the finish)
-int g_wit_max_open = 48;    // coarse samples the stage may leave open; more: far field, the simplex is left to the cell sweep
-int g_wit_max_live_pct = 12; // ... and the share of all samples that may survive the bound
-int g_wit_adaptive = 0;     // 1: once half of the simplices tried had to be abandoned, only every 16th is still tried
-int g_wit_flags = 0;        // test switches: 1 = no exact pass for the open samples, 2 = rounds not shared between waves
-int g_wit_cmax_ext_pct = 60;  // ... and at most this share of the simplex's extent
-int g_wit_sorted_stage = 1; // 1: the stage is filled in the order of the excess bins and the pair loops stop at the first bin no sample needs
-int g_wit_runs = 1;        // 1: the run test of the pass over all samples (phase 4a) where the caller hands in a run table
-int g_wit_surface_pct = 60;   // no attempt at all on a cloud that lies on a surface (the statistic of flood_common.hpp's cloud_kind_block,
-//    // same threshold as the cell sweep's "cell_surface_pct"): every box that meets the sheet is too dense for one stage
-//    // (cfg 3: 5581 simplices tried, none handled, 52 us); 0 = always try
-}  // namespace flooder
-
 namespace {
 
 #ifndef FLOODER_WIT_BLOCKS
@@ -1377,13 +1356,12 @@ struct WitOp {
   static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, float* plane_tab,
                  const float* weights, int k1, int R, int64_t ns, WitPlan plan, int32_t* queue, int32_t* item_list,
                  int32_t* item_count, WitOut out, FaceAcc acc, unsigned long long* stats, const int32_t* kind,
-                 hipStream_t st) {
+                 bool planes_ready, hipStream_t st) {
     if constexpr (DIM == 2 || DIM == 3) {
-      if (!planes_are_done(verts, plane_tab, ns, st)) {   // (flooder_simplex_prepare_f32 may have written the rows already)
+      if (!planes_ready) {   // (flooder_simplex_prepare_f32 may have written the rows already)
         const int rc = launch_simplex_planes(DIM, verts, k1, ns, plane_tab, st);
         if (rc != FLOODER_OK) return rc;
       }
-      planes_done_for(verts, plane_tab, ns, st);   // (the cell sweep's entry, next on this stream, need not repeat it)
       hipLaunchKernelGGL(wit_list_kernel, dim3(1), dim3(1024), 0, st, out.weight, (int)ns, (float)g_wit_weight, item_list,
                          item_count, g_wit_surface_pct > 0 ? kind : nullptr, g_wit_surface_pct);
       const int grid = (int)(ns < g_wit_grid ? ns : g_wit_grid);
@@ -1409,7 +1387,8 @@ int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* 
                   uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count,
                   uint32_t* flag_key, int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count,
                   float* simplex_weight, int32_t* item_list, float* plane_scratch, uint64_t* stats,
-                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, void* stream) {
+                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, bool planes_ready,
+                  void* stream) {
   if (n_simplices == 0 || R == 0) return FLOODER_OK;
   if (!pts_sorted || !nodes || !verts || !weights || !coarse_rows || !parents || !queue || !d2_scratch || !memb ||
       !face_bits || !flag_list || !flag_count || !simplex_weight || !item_list || !plane_scratch || n_pts < 1 || k1 < 1 ||
@@ -1440,7 +1419,7 @@ int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* 
                              WitOut{d2_scratch, flag_list, flag_count, simplex_weight}, acc,
                              reinterpret_cast<unsigned long long*>(stats),
                              density_grid ? density_grid + (flooder_density_grid_words(dim) - KIND_WORDS) : nullptr,
-                             (hipStream_t)stream);
+                             planes_ready, (hipStream_t)stream);
 }
 
 }  // namespace flooder
@@ -1460,7 +1439,7 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
   return sweep_witness(pts_sorted, n_pts, dim, nodes, verts, weights, k1, R, n_simplices, coarse_rows, n_coarse, parents,
                        queue, d2_scratch, memb, n_faces, face_bits, face_slot, flag_list, flag_count, flag_key, flag_hist,
                        top, top_list, top_count, simplex_weight, item_list, plane_scratch, stats, nullptr, nullptr, 0, 0,
-                       stream);
+                       false, stream);
 }
 
 }  // extern "C"

@@ -53,33 +53,15 @@ const char* flooder_last_error(void);
 /* Name of the GPU architecture of `device` copied into buf (e.g. "gfx950:sramecc+:xnack-"). */
 int flooder_device_arch(int device, char* buf, int buflen);
 
-/* Tuning switches (process-wide); none of them changes a result bit.
- *   "sweep_variant": 0 = packed-fp32 inner loop (default), 1 = plain fp32 inner loop (ball sweep);
- *   "bvh_ks": samples per lane of the tree sweep (0 = auto: 1 for R <= 64, else 2);
- *   "bvh_subs": sub-tiles a tree-sweep item may be split into (default 16);
- *   "bvh_grid": persistent workgroups of the tree sweep (default 1024 = 4 per CU);
- *   "cell_grid": persistent workgroups of the cell sweep (default 768 = the 3 per CU that fit LDS);
- *   "bvh_refine_pct": threshold of the tree sweep's transposed refine in percent of its cost model (100;
- *                     the full sweep uses three times the value), "bvh_leaf_batch": leaves fetched per step
- *                     by the work-list tree sweep (1, or 4 through LDS);
- *   "curve": 1 (default) Hilbert, 0 Morton order of the cloud in flooder_morton_f32; "curve_bits": bits per axis;
- *   "cell_brute_max": kept points up to which a chunk is evaluated straight from the compacted list (160);
- *   "cell_retry_keep" / "cell_retry_pct": a chunk of the per-chunk launch gets its second cell size only if the first
- *                     try kept at most this many points (200) and this share of its open samples has a point within
- *                     twice the cell size (50 %; 0: whatever they are) - else its open tiles go to the finish;
- *   "cell_tries" / "cell_exh_tries": cell sizes tried per chunk (2) / attempts that may fall back to the exhaustive
- *                     evaluation (3); "finish_focus_pct", "finish_items_cap", "finish_budget", "finish_order", "finish_top":
- *                     focus rounds, tile splitting and hard tiles of flooder_finish_faces_f32; "finish_wide_points"
- *                     (4194304; 0 = never): clouds of at least this many points - a box tree of four levels and more -
- *                     run its per-wave passes with eight waves per workgroup sharing one staged tree top (6 waves per
- *                     SIMD at an 80-register cap instead of 4: a search in a deep tree is a longer chain of dependent
- *                     steps; cfg 5 finish 1.68 -> 1.47 ms, no gain at a million points); "fps_switch", "fps_rpl": see flooder_fps_indexed_f32;
- *   "cell_exh_dense": most kept points a dense chunk of the cell sweep evaluates exhaustively before it is
- *                     handed to the tree sweep (default 32768);
- *   "cell_split_launches": 1 (default) the light / heavy simplex lists of a long queue come from ONE launch, 2 from the
- *                     split + reorder pair of rounds 3 - 5 (same lists); "wit_surface_pct", "cell_surface_pct": see
- *                     flooder_cloud_kind. */
+/* Tuning options (process-wide ints); none of them changes a result bit.  THE list - every name with its default, the
+ * values it accepts and what it does - is flooder_amd/csrc/flood_options.def, one row per option; the comments of the
+ * entry points below name the options that bear on them.  flooder_set_option returns FLOODER_E_ARG for a NULL or
+ * unknown name and for a value outside the option's row, and then changes nothing.  flooder_get_option stores the
+ * current value in *value (FLOODER_E_ARG: NULL or unknown name, NULL value): save and restore with it instead of
+ * copying defaults.  The options are read by the host code of the entry points when they are called - set them between
+ * calls, from one thread at a time. */
 int flooder_set_option(const char* name, int value);
+int flooder_get_option(const char* name, int* value);
 
 /* Row stride (floats) of a padded point / candidate row for ambient dimension `dim`:
  * 1,2 -> 2; 3,4 -> 4; 5..8 -> 8.  Rows in this layout are read with one vector load. */
@@ -345,7 +327,9 @@ int flooder_cloud_kind(int32_t* density_grid, int dim, void* stream);
  * flagged, re-staging rounds, chunks given up: tree gather overflow at density / at staging, kept list
  * full, cell doublings exhausted; rounds evaluated exhaustively because the LDS stage was full}.
  * plane_scratch: 24 * n_simplices floats of device scratch (the face planes of every simplex, computed once by a
- * small kernel instead of by each of its chunks).
+ * small kernel instead of by each of its chunks; this entry point and the positional witness / cell-face entry points
+ * below each launch that kernel themselves - chained, they repeat it: same rows, same values.  Only the parameter-block
+ * forms can be told that the rows are there: flooder_fused_sweep_t, planes_ready).
  * density_grid / cloud_box (both NULL, or the grid of flooder_density_grid_f32 and the 16-float box of
  * flooder_bbox_f32): with them a chunk whose box lies over well filled cells (option "cell_density_grid": at least
  * that many points in each, default 16; 0 = never) takes the local density from the grid instead of walking the tree
@@ -378,7 +362,7 @@ int flooder_sweep_cell_f32(const float* pts_sorted, int64_t n_pts, int dim, cons
  * "cell_tiles" 1; off by default: four re-centred gathers and classifications cost more than the exhaustive loop they
  * replace (cfg 3 sweep 3.95 vs 2.55 ms).
  * simplex_weight (NULL or n_simplices floats of flooder_simplex_weight_f32) with light_list / heavy_list
- * (n_simplices int32 scratch each): simplices heavier than option "cell_super_weight" (3000) skip the first launch -
+ * (n_simplices int32 scratch each): simplices heavier than option "cell_super_weight" (2000) skip the first launch -
  * in a dense region no run of four chunks fits the stage - and are worked off chunk by chunk by the second.  When
  * fewer than half of the simplices are sparse (weight <= option "cell_super_sparse", 600) the first launch gets no
  * work at all and the second sweeps everything in plain order.
@@ -428,7 +412,7 @@ int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim
  * finish, tiles flagged, pairs evaluated, excess bins kept; [12:22] cycles per phase in builds with -DFLOODER_WIT_TIMERS -
  * without them [21] = runs of samples dropped by the run test (flooder_fused_witness with a run table only); [22], [23]
  * focus rounds, gather overflows in them}.  Options: "wit_cmax_pct" (250: gather radius in percent of
- * the local point spacing), "wit_min_bins" (6), "wit_grid"; "wit_sorted_stage" (1: the stage is filled in the order of
+ * the local point spacing), "wit_min_bins" (48), "wit_grid"; "wit_sorted_stage" (1: the stage is filled in the order of
  * the excess bins, and a wave leaves a pair loop at the first bin whose points are provably farther than the running
  * minimum of every sample it holds - "pairs evaluated" counts what was actually evaluated; 0: any order, whole loops;
  * same face values either way).
@@ -485,17 +469,15 @@ int flooder_simplex_weight_f32(const float* nodes, int64_t n_pts, int dim, const
                                int64_t n_simplices, float* weight, void* stream);
 
 /* The same launch PREPARING a fused sweep: weights as above, plus (plane_scratch != NULL, dim 2 / 3) the face-plane rows
- * the witness and the cell sweep read - their entry points, next on this stream with the same verts / plane_scratch /
- * n_simplices, then skip their own plane launch - plus a zero fill of zero_words int32 words at zero_buf (the control
+ * the witness and the cell sweep read - flooder_fused_witness / flooder_fused_cell skip their own plane launch when
+ * the caller says so (flooder_fused_sweep_t, planes_ready) - plus a zero fill of zero_words int32 words at zero_buf (the control
  * words, queue heads and face words the sweep's launches start from; NULL / 0: none).  One launch instead of three
  * (fill, weights, planes): ~8 us of cfg 2's step. */
 int flooder_simplex_prepare_f32(const float* nodes, int64_t n_pts, int dim, const float* verts, int k1,
                                 int64_t n_simplices, float* weight, float* plane_scratch, int32_t* zero_buf,
                                 int64_t zero_words, void* stream);
-/* The note "the plane rows of (verts, plane_scratch, n_simplices) on this stream are written" lives in the calling
- * thread until the next witness / cell sweep entry point reads it.  A caller that gives up between the two (an error
- * in between) drops the note with this call - a later sweep with recycled buffers at the same addresses must not
- * inherit it. */
+/* Does nothing; exported so that callers of earlier versions still link (whether the plane rows are written is the
+ * caller's to say: flooder_fused_sweep_t, planes_ready). */
 void flooder_simplex_planes_forget(void);
 
 /* Device self-test of the 64-lane DPP reductions: out128[0:64] = min(in64), out128[64:128] = max. */
@@ -653,6 +635,12 @@ typedef struct flooder_fused_sweep_s {
   const uint32_t* wit_runs;
   int32_t wit_run_len;
   int32_t wit_n_runs;
+  /* non-zero: the caller vouches that plane_scratch already holds the plane rows of exactly these `verts` - written by
+   * flooder_simplex_prepare_f32, flooder_fused_witness or flooder_fused_cell on the SAME stream, and `verts` unchanged
+   * since - and flooder_fused_witness / flooder_fused_cell skip their plane-row launch.  0 (and every caller whose
+   * struct ends before this field): they launch it.  The library keeps no memory of what it wrote between calls. */
+  int32_t planes_ready;
+  int32_t reserved;
 } flooder_fused_sweep_t;
 
 /* flooder_sweep_witness_f32, flooder_sweep_cell_faces_f32, flooder_finish_faces_f32 on the fields of *p (host memory;
@@ -660,7 +648,9 @@ typedef struct flooder_fused_sweep_s {
  * then stands back on a cloud that lies on a surface (option "wit_surface_pct"), and the run table (wit_runs): a
  * whole run of samples is dropped with one bound - the distance of the run's centre to a parent's witness plus the
  * run's radius - where that bound cannot raise a face value; the positional function has neither argument: it always
- * tries and looks at every sample.  Face values are the same bit for bit either way. */
+ * tries and looks at every sample.  Face values are the same bit for bit either way.  planes_ready (see the field) is
+ * likewise a field only: the positional functions always write the plane rows themselves, so a caller that chains the
+ * positional witness and cell entry points pays one redundant small launch; the values are the same. */
 int flooder_fused_witness(const flooder_fused_sweep_t* p, void* stream);
 int flooder_fused_cell(const flooder_fused_sweep_t* p, void* stream);
 int flooder_fused_finish(const flooder_fused_sweep_t* p, void* stream);

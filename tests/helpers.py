@@ -19,6 +19,24 @@ RTOL = 1e-5
 COORD_ULPS = 2.0
 
 
+def get_options(lib, *names):
+    """{name: current value} of these options of libflooder_hip.so (names as bytes): what a test records before it
+    changes one, and puts back with ``set_options`` afterwards - no copies of the defaults in the tests."""
+    import ctypes
+
+    found = {}
+    for name in names:
+        value = ctypes.c_int()
+        assert lib.flooder_get_option(name, ctypes.byref(value)) == 0, name
+        found[name] = value.value
+    return found
+
+
+def set_options(lib, values):
+    for name, value in values.items():
+        assert lib.flooder_set_option(name, int(value)) == 0, name
+
+
 def tolerances(points):
     scale = float(np.abs(np.asarray(points)).max())
     return RTOL, COORD_ULPS * np.finfo(np.float32).eps * max(scale, 1e-30)

@@ -13,7 +13,7 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native, core
 from oracle import flood_oracle as fo
-from helpers import assert_close_filtration, assert_tree_matches_kdtree, kdtree_face_values
+from helpers import assert_close_filtration, assert_tree_matches_kdtree, get_options, kdtree_face_values, set_options
 
 pytestmark = pytest.mark.gpu
 
@@ -158,13 +158,13 @@ def test_bucketed_fps_equals_brute_force(dev, case):
     b = core.fps_indices(tp, k, start, method="bucket").cpu().numpy()
     assert np.array_equal(a, b)
     lib = _native.load()
+    keep = get_options(lib, b"fps_rpl", b"fps_switch")
     for rpl, sw in ((4, 8), (1, 1), (4, 1)):
         try:
             assert lib.flooder_set_option(b"fps_rpl", rpl) == 0 and lib.flooder_set_option(b"fps_switch", sw) == 0
             c = core.fps_indices(tp, min(k, 200), start, method="bucket").cpu().numpy()
         finally:
-            lib.flooder_set_option(b"fps_rpl", 0)
-            lib.flooder_set_option(b"fps_switch", 0)
+            set_options(lib, keep)
         assert np.array_equal(a[:len(c)], c), (rpl, sw)
 
 
@@ -209,12 +209,13 @@ def test_batched_fps_hard_cases_equal_brute_force(dev, case, monkeypatch):
     assert core.LAST_FPS_LAUNCHES < k or case in ("two_clusters", "all_points")
     assert np.array_equal(a[:40], fo.exact_fps(P, 40, start))
     lib = _native.load()
+    keep = get_options(lib, b"fps_switch", b"fps_lane_best", b"fps_rounds")
     for sw in (2, 7):   # switch to the batched steps almost at once
         try:
             assert lib.flooder_set_option(b"fps_switch", sw) == 0
             c = core.fps_indices(tp, min(k, 250), start, method="bucket").cpu().numpy()
         finally:
-            lib.flooder_set_option(b"fps_switch", 0)
+            set_options(lib, keep)
         assert np.array_equal(a[:len(c)], c), sw
     # the other paths of the same entry point: one candidate per lane (what > 64 candidates fall back to) and rounds
     # of launches with a counter read-back (what a host without pinned memory falls back to)
@@ -223,7 +224,7 @@ def test_batched_fps_hard_cases_equal_brute_force(dev, case, monkeypatch):
             assert lib.flooder_set_option(opt, 1) == 0
             c = core.fps_indices(tp, k, start, method="bucket").cpu().numpy()
         finally:
-            lib.flooder_set_option(opt, 0)
+            set_options(lib, keep)
         assert np.array_equal(a, c), opt
     if P.shape[1] <= 3:  # the one-landmark-per-launch kernels stay selectable
         monkeypatch.setattr(core, "FPS_BATCHED", False)

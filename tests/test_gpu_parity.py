@@ -9,7 +9,8 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native, core
 from oracle import flood_oracle as fo
-from helpers import assert_tree_matches_kdtree, GOLDEN, assert_close_filtration, e2e_cases, load_e2e, dict_values
+from helpers import (assert_tree_matches_kdtree, GOLDEN, assert_close_filtration, e2e_cases, load_e2e, dict_values,
+                     get_options, set_options)
 
 pytestmark = pytest.mark.gpu
 
@@ -95,11 +96,12 @@ def test_plain_and_packed_variants_are_bit_identical(dev):
     lib = _native.load()
     z, kw, keys = load_e2e("torus3d_grid")
     pts, lms = torch.as_tensor(z["points"], device=dev), torch.as_tensor(z["landmarks"], device=dev)
+    keep = get_options(lib, b"sweep_variant")
     try:
         assert lib.flooder_set_option(b"sweep_variant", 1) == 0
         a = fa.flood_complex(pts, lms, method="ball", **kw)
     finally:
-        assert lib.flooder_set_option(b"sweep_variant", 0) == 0
+        set_options(lib, keep)
     b = fa.flood_complex(pts, lms, method="ball", **kw)
     assert a == b
 
@@ -237,6 +239,7 @@ def test_fused_sorted_sweep_equals_unfused(refresh, dev, monkeypatch):
     lib = _native.load()
     monkeypatch.setattr(core, "BVH_SORTED_MIN_SAMPLES", 0)
     rng = np.random.default_rng(5)
+    keep = get_options(lib, b"sorted_refresh")
     assert lib.flooder_set_option(b"sorted_refresh", refresh) == 0
     try:
         for dim, n, k, kw in ((6, 40_000, 24, dict(max_dimension=2, points_per_edge=6)),
@@ -252,7 +255,7 @@ def test_fused_sorted_sweep_equals_unfused(refresh, dev, monkeypatch):
                 out[fused] = fa.flood_complex(tp, tl, method="bvh", **kw)
             assert out[True] == out[False], (dim, kw)
     finally:
-        assert lib.flooder_set_option(b"sorted_refresh", 4) == 0
+        set_options(lib, keep)
 
 
 def test_sorted_sample_sweep_random_dimensions(dev, monkeypatch):
@@ -307,6 +310,7 @@ def test_dense_chunk_tile_launch_changes_nothing(dev):
     launch (one sample per lane) instead of the exhaustive loop.  Off by default (slower); bit-identical when on: a
     surface cloud (most chunks near the sheet overflow) and a dense Gaussian core."""
     lib = _native.load()
+    keep = get_options(lib, b"cell_tiles")
     for pts, n_l, ppe in ((fo.noisy_torus(400_000, seed=3), 150, 30),
                           (np.random.default_rng(4).normal(size=(500_000, 3)).astype(np.float32) * 0.05, 40, 30)):
         lms = pts[fo.exact_fps(pts, n_l, 0)]
@@ -316,7 +320,7 @@ def test_dense_chunk_tile_launch_changes_nothing(dev):
             assert lib.flooder_set_option(b"cell_tiles", 1) == 0
             on = fa.flood_complex(tp, tl, points_per_edge=ppe)
         finally:
-            lib.flooder_set_option(b"cell_tiles", 0)
+            set_options(lib, keep)
         assert on == off
 
 
@@ -327,6 +331,8 @@ def test_cell_sweep_queue_and_pass_options_change_nothing(dev):
     change the order and the amount of work, never a value: a surface cloud (overflowing chunks), a dense Gaussian
     core (exhaustive chunks) and a cloud large enough for runs of four."""
     lib = _native.load()
+    keep = get_options(lib, b"cell_one_pass", b"cell_weight_classes", b"cell_listed_first", b"cell_chunks_per_block",
+                       b"cell_min_grid", b"cell_super_min_chunks", b"cell_drop", b"cell_chunk_major")
     cases = ((fo.noisy_torus(400_000, seed=3), 150, 30),
              (np.random.default_rng(4).normal(size=(500_000, 3)).astype(np.float32) * 0.05, 40, 30),
              (np.random.default_rng(6).normal(size=(600_000, 3)).astype(np.float32), 700, 30))
@@ -343,10 +349,7 @@ def test_cell_sweep_queue_and_pass_options_change_nothing(dev):
                     assert lib.flooder_set_option(k, v) == 0
                 got = fa.flood_complex(tp, tl, points_per_edge=ppe)
             finally:
-                for k, v in ((b"cell_one_pass", 125), (b"cell_weight_classes", 1), (b"cell_listed_first", 1),
-                             (b"cell_chunks_per_block", 12), (b"cell_min_grid", 384), (b"cell_super_min_chunks", 49152),
-                             (b"cell_drop", 1), (b"cell_chunk_major", 1)):
-                    lib.flooder_set_option(k, v)
+                set_options(lib, keep)
             assert got == ref, opts
 
 
@@ -739,6 +742,7 @@ def test_long_queue_lists_from_one_launch_equal_the_two_launches(dev, cloud):
     assert verts.shape[0] * ((weights.shape[0] + 255) // 256) >= 49152, "not a long queue"
     index = core.PointIndex(tp)
     keep = core.WIT_MIN_SIMPLICES, core.CELL_WITNESS
+    keep_options = get_options(lib, b"cell_split_launches")
     try:
         core.WIT_MIN_SIMPLICES = 0
         for witness in (True, False):
@@ -755,7 +759,7 @@ def test_long_queue_lists_from_one_launch_equal_the_two_launches(dev, cloud):
             assert torch.equal(got[1][0].view(torch.int32), got[2][0].view(torch.int32)), (cloud, witness)
     finally:
         core.WIT_MIN_SIMPLICES, core.CELL_WITNESS = keep
-        assert lib.flooder_set_option(b"cell_split_launches", 1) == 0
+        set_options(lib, keep_options)
 
 
 @pytest.mark.parametrize("cloud", ["gauss3d", "torus3d", "eight2d"])
@@ -797,7 +801,6 @@ def test_launch_lean_paths_change_nothing(dev, cloud, monkeypatch):
     _native.check(lib.flooder_simplex_prepare_f32(_native.ptr(index.nodes), index.n, dim, _native.ptr(verts), dim + 1, S,
                                                   _native.ptr(w_b), _native.ptr(planes), _native.ptr(junk), junk.numel(), 0),
                   "flooder_simplex_prepare_f32")
-    lib.flooder_simplex_planes_forget()   # (no sweep follows here)
     torch.cuda.synchronize()
     assert torch.equal(w_a.view(torch.int32), w_b.view(torch.int32))
     assert int(junk.abs().sum()) == 0 and not bool(torch.isnan(planes).any())
@@ -842,6 +845,7 @@ def test_runs_of_four_chunks_equal_chunk_by_chunk(dev, cloud, monkeypatch):
         n_l = 150
     tp = torch.as_tensor(pts, device=dev)
     tl = fa.generate_landmarks(tp, n_l, start_idx=0)
+    keep = get_options(lib, b"cell_super_min_chunks", b"cell_super_sparse", b"cell_super_weight", b"cell_super_n0")
     for kw in (dict(points_per_edge=30), dict(points_per_edge=None, num_rand=3000)):
         monkeypatch.setattr(core, "CELL_SUPER", False)
         torch.manual_seed(5)
@@ -855,9 +859,7 @@ def test_runs_of_four_chunks_equal_chunk_by_chunk(dev, cloud, monkeypatch):
                 torch.manual_seed(5)
                 got = fa.flood_complex(tp, tl, method="cell", **kw)
             finally:
-                for name, val in ((b"cell_super_min_chunks", 49152), (b"cell_super_sparse", 600),
-                                  (b"cell_super_weight", 2000), (b"cell_super_n0", 480)):
-                    lib.flooder_set_option(name, val)
+                set_options(lib, keep)
             assert got == ref, (cloud, kw, weight, n0)
 
 
@@ -881,6 +883,7 @@ def test_finish_hard_tiles_and_ordering_change_nothing(dev, cloud, monkeypatch):
     faces = core._FaceTable(fi, weights.shape[0], dev)
     index = core.PointIndex(pts)
     stats = torch.zeros(16, dtype=torch.int64, device=dev)
+    keep = get_options(lib, b"finish_order", b"finish_budget", b"finish_top", b"finish_budget_min")
 
     def run(order, budget, cap, top=0):
         monkeypatch.setattr(core, "FINISH_HARD_CAP", cap)
@@ -893,8 +896,7 @@ def test_finish_hard_tiles_and_ordering_change_nothing(dev, cloud, monkeypatch):
             torch.cuda.synchronize()
             return out.cpu().numpy(), core.LAST_STATS.hard_entries
         finally:
-            for name, val in ((b"finish_order", 1), (b"finish_budget", 14), (b"finish_top", 0), (b"finish_budget_min", 64)):
-                lib.flooder_set_option(name, val)
+            set_options(lib, keep)
 
     ref, hard = run(0, 0, 32768)
     assert hard == (0, 0)
@@ -935,6 +937,7 @@ def test_index_sort_is_a_stable_sort(dev):
     """flooder_index_sort (radix sort over the used key bits; uint32 words for keys of at most 32 bits) against torch's
     stable sort: identical permutations, duplicates included."""
     lib = _native.load()
+    keep = get_options(lib, b"sort_shape")
     g = torch.Generator().manual_seed(9)
     # (12288 = 3 x 512 x 8 and 1638400 = 200 x 1024 x 8: whole blocks only, in the small and the large block shape)
     for n, bits in ((1, 30), (63, 30), (5000, 8), (12_288, 24), (100_000, 30), (1_000_003, 30), (300_000, 17),
@@ -972,7 +975,7 @@ def test_index_sort_is_a_stable_sort(dev):
             torch.cuda.synchronize()
             assert torch.equal(order2, order), (n, bits, rep)
             assert torch.equal(out2.view(torch.int32)[:n], out.view(torch.int32)[:n]), (n, bits, rep)
-        assert lib.flooder_set_option(b"sort_shape", 0) == 0
+        set_options(lib, keep)
 
 
 def test_index_of_a_modified_cloud_is_refused(dev):
@@ -1077,9 +1080,10 @@ def test_cloud_kind_words_tell_a_surface_from_a_volume(dev):
     tp = clouds["torus"].to(dev)
     lms = fa.generate_landmarks(tp, 300, start_idx=0)
     a = fa.flood_complex(tp, lms, points_per_edge=20)
+    keep = get_options(lib, b"cell_surface_pct")
     assert lib.flooder_set_option(b"cell_surface_pct", 0) == 0
     try:
         b = fa.flood_complex(tp, lms, points_per_edge=20)
     finally:
-        assert lib.flooder_set_option(b"cell_surface_pct", 60) == 0
+        set_options(lib, keep)
     assert a == b

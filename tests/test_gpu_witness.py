@@ -7,12 +7,13 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native, core
 from oracle import flood_oracle as fo
+from helpers import get_options, set_options as helpers_set_options
 
 pytestmark = pytest.mark.gpu
 
-WIT_DEFAULTS = {"wit_max_eval": 768, "wit_max_leaves": 400, "wit_adaptive": 0, "wit_weight": 800, "wit_cmax_pct": 250, "wit_cmax_ext_pct": 60, "wit_min_bins": 48, "wit_flags": 0,
-                "wit_max_open": 48, "wit_max_live_pct": 12, "wit_max_in_pct": 8}
-WIT_SURFACE_PCT = 60   # the product's default: the witness sweep stands back on clouds that lie on a surface
+# the options the tests here change: the fixture records what it finds (the product's values) and puts it back
+WIT_OPTIONS = (b"wit_max_eval", b"wit_max_leaves", b"wit_adaptive", b"wit_weight", b"wit_cmax_pct", b"wit_cmax_ext_pct",
+               b"wit_min_bins", b"wit_flags", b"wit_max_open", b"wit_max_live_pct", b"wit_max_in_pct")
 
 
 @pytest.fixture(scope="module")
@@ -23,17 +24,18 @@ def dev():
 
 
 @pytest.fixture(autouse=True)
-def restore_options():
+def found_options():
+    """The values of the witness options as the test finds them: {b"name": value} of WIT_OPTIONS and, apart,
+    b"wit_surface_pct" (the product's: the witness sweep stands back on clouds that lie on a surface)."""
     keep = core.WIT_MIN_SIMPLICES, core.WIT_MAX_POINTS_PER_SIMPLEX
+    lib = _native.load()
+    found = get_options(lib, b"wit_surface_pct", *WIT_OPTIONS)
     core.WIT_MIN_SIMPLICES = 0    # (the product skips the witness sweep on short queues: the tests here want it run)
     core.WIT_MAX_POINTS_PER_SIMPLEX = 1 << 40   # (... and on clouds with many points per simplex)
-    assert _native.load().flooder_set_option(b"wit_surface_pct", 0) == 0   # (... and on clouds that lie on a surface)
-    yield
+    assert lib.flooder_set_option(b"wit_surface_pct", 0) == 0   # (... and on clouds that lie on a surface)
+    yield found
     core.WIT_MIN_SIMPLICES, core.WIT_MAX_POINTS_PER_SIMPLEX = keep
-    lib = _native.load()
-    assert lib.flooder_set_option(b"wit_surface_pct", WIT_SURFACE_PCT) == 0
-    for k, v in WIT_DEFAULTS.items():
-        assert lib.flooder_set_option(k.encode(), v) == 0
+    helpers_set_options(lib, found)
     core.CELL_WITNESS = True
 
 
@@ -113,7 +115,7 @@ def test_witness_sweep_takes_the_sparse_simplices_and_leaves_the_dense_ones(dev)
     assert int(st_d[0]) == 0, "a dense uniform cloud has nothing for the witness sweep"
 
 
-def test_witness_sweep_stands_back_on_a_surface_cloud(dev):
+def test_witness_sweep_stands_back_on_a_surface_cloud(dev, found_options):
     """Decided on the device from the density grid's cloud-kind words (flood_common.hpp): on the noisy torus no simplex
     is tried at all with the default option, every simplex is looked at with the gate off - and the values are the same."""
     tor = clouds("torus", 400_000).to(dev)
@@ -121,7 +123,7 @@ def test_witness_sweep_stands_back_on_a_surface_cloud(dev):
     st_open = sweep_stats(tor, lms)
     assert int(st_open[:4].sum()) > 0, "gate off: the sweep looks at the simplices (handled / heavy / over / dense)"
     off = run(tor, lms, True)
-    set_options(wit_surface_pct=WIT_SURFACE_PCT)
+    set_options(wit_surface_pct=found_options[b"wit_surface_pct"])
     st_gate = sweep_stats(tor, lms)
     assert int(st_gate[:12].sum()) == 0, st_gate[:12]
     assert_same(run(tor, lms, True), off, "torus: surface gate on / off")
@@ -152,7 +154,7 @@ def test_witness_sweep_random_weights_and_off_cloud_landmarks(dev):
     dict(wit_min_bins=1, wit_max_eval=64, wit_weight=5000), dict(wit_min_bins=1, wit_max_leaves=1024, wit_weight=3000),
     dict(wit_max_open=100000, wit_max_live_pct=100, wit_flags=8),  # nothing is abandoned: queue / list overflow paths
 ])
-def test_witness_sweep_options_change_nothing(opts, dev):
+def test_witness_sweep_options_change_nothing(opts, dev, found_options):
     pts = clouds("two_blobs", 150_000).to(dev)
     lms = fa.generate_landmarks(pts, 300, start_idx=0)
     ref = run(pts, lms, False)
@@ -160,7 +162,7 @@ def test_witness_sweep_options_change_nothing(opts, dev):
     assert_same(run(pts, lms, True), ref, str(opts))
     tor = clouds("torus", 100_000).to(dev)
     lms_t = fa.generate_landmarks(tor, 200, start_idx=0)
-    set_options(**WIT_DEFAULTS)
+    helpers_set_options(_native.load(), {k: found_options[k] for k in WIT_OPTIONS})
     ref_t = run(tor, lms_t, False)
     set_options(**opts)
     assert_same(run(tor, lms_t, True), ref_t, f"torus {opts}")
