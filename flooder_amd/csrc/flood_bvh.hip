@@ -811,6 +811,9 @@ struct IndexRowsOp {
       hipLaunchKernelGGL((bvh_inner_kernel<DIM>), dim3(nb + (phase == 1 ? 16u : 0u)), dim3(256), 0, st,
                          nodes + lv.off[l - 1] * 2 * DP, lv.count[l - 1], pad, nodes + lv.off[l] * 2 * DP, dens, phase, (int)nb);
     }
+    // (a tree of one level - at most 1024 points - has no such launch to ride in: the statistic gets one of its own, so
+    // that the words are those of flooder_cloud_kind for every cloud size)
+    if (dens != nullptr && lv.n_levels == 1) launch_cloud_kind(DIM, dens, st);
     return check_launch("index_rows");
   }
 };

@@ -219,9 +219,10 @@ int flooder_gather_rows_f32(const float* pts, int64_t n_pts, int dim, int ld, co
 /* Number of nodes (all levels, each padded to a multiple of 64) of the tree over n_pts points. */
 int64_t flooder_bvh_node_count(int64_t n_pts);
 
-/* Build the tree.  pts_sorted: padded rows (flooder_padded_dim(dim) floats), Morton order, row count
- * rounded up to a multiple of FLOODER_BVH_LEAF with +inf rows.  nodes: flooder_bvh_node_count(n_pts)
- * x 2 x padded_dim floats (box lo then hi per node). */
+/* Build the tree.  pts_sorted: padded rows (flooder_padded_dim(dim) floats) in ANY order (the boxes are taken from the
+ * rows as they come; curve or k-d order only makes them tight), row count rounded up to a multiple of
+ * FLOODER_BVH_LEAF with +inf rows.  nodes: flooder_bvh_node_count(n_pts) x 2 x padded_dim floats (box lo then hi per
+ * node). */
 int flooder_bvh_build_f32(const float* pts_sorted, int64_t n_pts, int dim, float* nodes, void* stream);
 
 /* flooder_gather_rows_f32 + flooder_bvh_build_f32 in one call: the rows are written in curve order and the leaf boxes
@@ -308,7 +309,10 @@ int flooder_density_grid_f32(const float* nodes, int64_t n_pts, int dim, const f
  * and [3] behind the fine grid.  The cell sweep reads them and tries ONE cell size per chunk instead of two on surface
  * clouds (option "cell_surface_pct", 60; 0 = never): cfg 3 3.88 -> 3.75 ms; flooder_fused_witness reads them too and
  * tries no simplex at all on such a cloud (option "wit_surface_pct", 60; 0 = always try): 3.75 -> 3.70 ms.  flooder_index_rows_f32 computes the
- * statistic itself (in spare workgroups of the launch that builds the first inner tree level); this entry point is for grids filled by flooder_density_grid_f32 (one launch; the four words must be zero).
+ * statistic itself (in spare workgroups of the launch that builds the first inner tree level; a tree of one level, at
+ * most 1024 points, has no such launch and gets one for the statistic alone: the same words for every cloud size); this
+ * entry point is for grids filled by flooder_density_grid_f32 (one launch; the four words must be zero).  Words [0] and
+ * [1] are reserved: nothing writes them, they stay zero.
  * Without it the words stay zero and the sweep tries two sizes, as before round 6.  No result depends on it. */
 int flooder_cloud_kind(int32_t* density_grid, int dim, void* stream);
 
