@@ -90,6 +90,14 @@ class KnnSweep(_Block):
         i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats""")
 
 
+class WitnessKnn(_Block):
+    """``flooder_witness_knn_t``: the k points that realise a robust value (flooder_amd.grad, neighbors > 1)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p order; p verts; p weights;
+        i32 R; i32 k; i64 n_simplices; i64 n_queries; p q_simplex; p q_row; p q_stat; p out_ids; p out_d2; p not_found;
+        i32 stat; i32 reserved""")
+
+
 _lib = None
 _load_error: Exception | None = None
 _load_missing = False  # the last failure was "file not found" (worth another look after a build)
@@ -181,6 +189,8 @@ SIGNATURES = {
     "flooder_segment_sum_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     # the k nearest points of every sample (flood_complex(neighbors=k))
     "flooder_sweep_knn_f32": (c_int, [ctypes.POINTER(KnnSweep), c_void_p]),
+    # ... and which k points realise the statistic of a witness sample (flood_filtration(neighbors=k))
+    "flooder_witness_knn": (c_int, [ctypes.POINTER(WitnessKnn), c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -1308,14 +1308,47 @@ KNN_MAX = 32
 NEIGHBOR_STATS = ("kth", "dtm")
 
 
+def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, reduce_hook=None, shard_blocks=False):
+    """The robust filtration's arguments as ``flood_complex`` and ``flood_filtration`` judge them, before any work is
+    done -> (neighbors as int, method: ``"bvh"`` in place of None / "auto" when neighbors > 1)."""
+    if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
+        raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
+    neighbors = int(neighbors)
+    if not 1 <= neighbors <= KNN_MAX:
+        raise ValueError(f"neighbors must be in 1..{KNN_MAX} (KNN_MAX: the k best of a sample live in registers of the "
+                         f"kernel), got {neighbors}")
+    if neighbor_stat not in NEIGHBOR_STATS:
+        raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
+    if points.dim() == 2 and neighbors > max(points.shape[0], 1):
+        raise ValueError(f"neighbors={neighbors} exceeds the number of points ({points.shape[0]})")
+    if neighbors > 1:
+        if method in ("cell", "ball"):
+            raise ValueError(f"neighbors > 1 needs the tree sweep: method {method!r} evaluates the nearest point only "
+                             "(use method=None, 'auto' or 'bvh')")
+        if reduce_hook is not None:
+            raise ValueError("neighbors > 1 cannot be combined with reduce_hook: a MIN over point shards is not the "
+                             "k-th nearest of their union")
+        if shard_blocks:
+            raise ValueError("neighbors > 1 cannot be combined with shard_blocks=True: a block's sub-cloud holds the "
+                             "points inside its simplices' bounding balls, which bound the nearest point only")
+        if points.is_cuda and points.dtype is torch.float64:
+            raise ValueError("neighbors > 1 on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
+        if points.is_cuda and points.dim() == 2 and not 2 <= points.shape[1] <= 8:
+            raise ValueError("neighbors > 1 on ROCm tensors needs ambient dimension 2 to 8")
+        if method is None or method == "auto":
+            method = "bvh"   # (the tree sweep in every dimension; any other name is judged by the caller as always)
+    return neighbors, method
+
+
 def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                          k: int, stat: str, plan: Optional["SamplePlan"] = None,
-                         stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None):
+                         stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None, keep=None):
     """All simplices of one dimension against an indexed point set, ``k`` nearest points per sample -> (S, F) face
     maxima of the k-distance (``stat="kth"``) or of the distance to the empirical measure (``"dtm"``).
 
     sweep_knn (plain stores of the SQUARED statistic's bits into the (S, R) buffer, samples in the order of
-    ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  No host synchronisation."""
+    ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  No host synchronisation.  ``keep``: a callable
+    that is handed the (S, R) int32 buffer (columns in swept order) - ``flood_filtration`` finds its witnesses there."""
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
@@ -1336,6 +1369,8 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
                                                _native.ptr(plan.rows_perm), faces.n_faces,
                                                _native.ptr(out_face), None, st),
                       "flooder_face_max_f32")
+    if keep is not None:
+        keep(d2)
     return out_face, None
 
 
@@ -1622,32 +1657,7 @@ def flood_complex(
     NEAREST point only) and ROCm float64 tensors are refused; ``simplex_shard`` without blocks works as before.
     """
     # ---- the robust filtration's arguments, before any work is done
-    if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
-        raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
-    neighbors = int(neighbors)
-    if not 1 <= neighbors <= KNN_MAX:
-        raise ValueError(f"neighbors must be in 1..{KNN_MAX} (KNN_MAX: the k best of a sample live in registers of the "
-                         f"kernel), got {neighbors}")
-    if neighbor_stat not in NEIGHBOR_STATS:
-        raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
-    if points.dim() == 2 and neighbors > max(points.shape[0], 1):
-        raise ValueError(f"neighbors={neighbors} exceeds the number of points ({points.shape[0]})")
-    if neighbors > 1:
-        if method in ("cell", "ball"):
-            raise ValueError(f"neighbors > 1 needs the tree sweep: method {method!r} evaluates the nearest point only "
-                             "(use method=None, 'auto' or 'bvh')")
-        if reduce_hook is not None:
-            raise ValueError("neighbors > 1 cannot be combined with reduce_hook: a MIN over point shards is not the "
-                             "k-th nearest of their union")
-        if shard_blocks:
-            raise ValueError("neighbors > 1 cannot be combined with shard_blocks=True: a block's sub-cloud holds the "
-                             "points inside its simplices' bounding balls, which bound the nearest point only")
-        if points.is_cuda and points.dtype is torch.float64:
-            raise ValueError("neighbors > 1 on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
-        if points.is_cuda and points.dim() == 2 and not 2 <= points.shape[1] <= 8:
-            raise ValueError("neighbors > 1 on ROCm tensors needs ambient dimension 2 to 8")
-        if method is None or method == "auto":
-            method = "bvh"   # (the tree sweep in every dimension; any other name is judged below as always)
+    neighbors, method = _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks)
     if use_triton is None:
         use_triton = HAS_HIP_KERNELS
     if use_triton and not _has_hip_kernels():

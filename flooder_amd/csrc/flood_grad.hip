@@ -11,6 +11,8 @@
 //                    then a fixed-radius walk of the box tree of the cloud (flood_bvh.hpp): only leaves whose lower
 //                    bound is <= the known d2 are opened, and the smallest original id whose d2, in the sweeps'
 //                    arithmetic, has exactly the target bits is the witness.  A face with no such point is counted.
+//   witness_knn      the robust filtration's witness: the k smallest (d2 word, original id) keys of p* over the whole
+//                    cloud, in order, and a check that they reproduce the swept statistic bit for bit.
 //   segment_sum      backward: contributions sorted (stably) by their target row are summed segment by segment in
 //                    that order - no float atomics, the gradient is bit-identical run to run.
 
@@ -191,6 +193,185 @@ struct WitnessOp {
   }
 };
 
+// ------------------------------------------------------------------------------------------------ witness k nearest
+// The witness of a robust value (flood_complex(neighbors=k)): WHICH k points realise the statistic of the sample p*.
+// One wave per query, the stack of witness_search_kernel.  The wave keeps the k smallest keys (d2 word, original id)
+// seen so far sorted ascending, one key per lane (k <= 32 < 64; the other lanes hold the all-ones key).  A popped
+// group's children are tested one per lane; the nearest qualifying child is pushed LAST, so the first thing a query
+// does is walk down to the leaf group nearest to it and the k-th best is small from then on.  Leaves are evaluated
+// four at a time, one point per lane, and the leaves still waiting are tested again after every four.
+//
+// Exactness.  Keys are distinct (ids are), so "the k smallest keys of all points" is one set, and inserting any
+// superset of it in any order leaves exactly that set, sorted.  A subtree or leaf is skipped only when
+// lb * GRAD_SAFE > (k-th best d2) - every point in it then has d2 > the k-th best and hence a LARGER key, whatever its
+// id.  A box at lb == k-th best is opened: a point at an equal d2 with a smaller id displaces the k-th entry.
+// Nothing is skipped before the list holds k points (its k-th d2 word is all ones: +inf here).
+template <int DIM>
+__global__ __launch_bounds__(256) void witness_knn_kernel(const float* __restrict__ pts, int64_t n_pts,
+                                                          const float* __restrict__ nodes, Levels lv,
+                                                          const int32_t* __restrict__ order,
+                                                          const float* __restrict__ verts,
+                                                          const float* __restrict__ weights, int k1, int R,
+                                                          int64_t n_simplices, int64_t n_queries, int k, int stat,
+                                                          const int32_t* __restrict__ q_simplex,
+                                                          const int32_t* __restrict__ q_row,
+                                                          const uint32_t* __restrict__ q_stat,
+                                                          int64_t* __restrict__ out_ids, uint32_t* __restrict__ out_d2,
+                                                          int32_t* __restrict__ not_found) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ int32_t s_stack[WAVES_PER_BLOCK][STACK];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
+  const int64_t n_waves = (int64_t)gridDim.x * WAVES_PER_BLOCK;
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int top = lv.n_levels - 1;
+  for (int64_t q = wave; q < n_queries; q += n_waves) {
+    const int64_t s = q_simplex[q];
+    const int64_t r = q_row[q];
+    bool found = !(s < 0 || s >= n_simplices || r < 0 || r >= R);   // (else: not a swept sample, no witness)
+    uint32_t l_hi = 0xffffffffu, l_lo = 0xffffffffu;   // this lane's entry of the list: (d2 word, original id)
+    if (found) {
+      // p* exactly as the sweeps build a sample: p = 0; p[c] = fma(w_j, v_j[c], p[c]) in vertex order
+      float p[DIM];
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) p[c] = 0.f;
+      const float* vs = verts + s * (int64_t)k1 * DIM;
+      for (int j = 0; j < k1; ++j) {
+        const float w = weights[r * k1 + j];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) p[c] = __builtin_fmaf(w, vs[j * DIM + c], p[c]);
+      }
+      uint32_t kth_hi = 0xffffffffu, kth_lo = 0xffffffffu;   // the list's k-th key (wave-uniform)
+      float kth_f = __builtin_inff();
+      int sp = 1;
+      if (lane == 0) s_stack[wv][0] = top;   // (level top, group 0): the <= 64 top nodes
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      while (sp > 0) {
+        --sp;
+        const int e = s_stack[wv][sp];
+        const int lvl = e & 7;
+        const int64_t grp = e >> 3;
+        const int64_t idx = grp * FAN + lane;
+        bool ok = false;
+        float lb = __builtin_inff();
+        if (idx < lv.count[lvl]) {
+          float lo[DP], hi[DP];
+          const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
+          load_row<DP>(nb, lo);
+          load_row<DP>(nb + DP, hi);
+          lb = 0.f;
+#pragma unroll
+          for (int c = 0; c < DIM; ++c) {
+            const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[c] - p[c], p[c] - hi[c]), 0.f);
+            lb = __builtin_fmaf(gap, gap, lb);
+          }
+          ok = !(lb * GRAD_SAFE > kth_f);
+        }
+        unsigned long long mask = __ballot(ok);
+        __builtin_amdgcn_wave_barrier();   // (every lane has read the popped entry before a push may overwrite it)
+        if (lvl == 0) {
+          while (mask) {
+            int64_t leaf[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              if (mask) {
+                const int j = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                leaf[u] = grp * FAN + j;
+              } else {
+                leaf[u] = -1;
+              }
+            }
+            const int u = lane >> 4;
+            const int64_t lf = u == 0 ? leaf[0] : (u == 1 ? leaf[1] : (u == 2 ? leaf[2] : leaf[3]));
+            const int64_t rw = lf * LEAF + (lane & 15);
+            uint32_t c_hi = 0xffffffffu, c_lo = 0xffffffffu;   // this lane's candidate key
+            if (lf >= 0 && rw < n_pts) {   // (rows of the padded last leaf are never candidates)
+              float x[DP];
+              load_row<DP>(pts + rw * DP, x);
+              float d2;
+#pragma unroll
+              for (int c = 0; c < DIM; ++c) {
+                const float t = p[c] - x[c];
+                if (c == 0) d2 = t * t;
+                else d2 = __builtin_fmaf(t, t, d2);
+              }
+              c_hi = __float_as_uint(d2);
+              c_lo = (uint32_t)order[rw];
+            }
+            // insert every candidate below the k-th key, first lane first
+            for (;;) {
+              const unsigned long long better = __ballot(c_hi < kth_hi || (c_hi == kth_hi && c_lo < kth_lo));
+              if (!better) break;
+              const int j = __builtin_ctzll(better);
+              const uint32_t b_hi = (uint32_t)__builtin_amdgcn_readlane((int)c_hi, j);
+              const uint32_t b_lo = (uint32_t)__builtin_amdgcn_readlane((int)c_lo, j);
+              if (lane == j) c_hi = c_lo = 0xffffffffu;
+              const int pos = __popcll(__ballot(l_hi < b_hi || (l_hi == b_hi && l_lo < b_lo)));
+              const uint32_t u_hi = (uint32_t)__shfl_up((int)l_hi, 1);
+              const uint32_t u_lo = (uint32_t)__shfl_up((int)l_lo, 1);
+              if (lane > pos) { l_hi = u_hi; l_lo = u_lo; }
+              if (lane == pos) { l_hi = b_hi; l_lo = b_lo; }
+              if (lane >= k) l_hi = l_lo = 0xffffffffu;   // (what fell off the end)
+              kth_hi = (uint32_t)__builtin_amdgcn_readlane((int)l_hi, k - 1);
+              kth_lo = (uint32_t)__builtin_amdgcn_readlane((int)l_lo, k - 1);
+            }
+            kth_f = kth_hi == 0xffffffffu ? __builtin_inff() : __uint_as_float(kth_hi);
+            mask &= __ballot(!(lb * GRAD_SAFE > kth_f));   // the leaves still waiting, against the new k-th best
+          }
+        } else {
+          if (mask) {
+            // the nearest qualifying child goes on top of the stack, the others below it in lane order
+            const float mn = wave_min_f32(ok ? lb : __builtin_inff());
+            const int jn = __builtin_ctzll(__ballot(ok && lb == mn));
+            const unsigned long long rest = mask & ~(1ull << jn);
+            if (ok) {
+              const int at = lane == jn ? __popcll(rest) : __popcll(rest & below);
+              s_stack[wv][sp + at] = (int)((idx << 3) | (lvl - 1));
+            }
+            sp += __popcll(mask);
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+      // the statistic of the k words, as sweep_knn_kernel computes it
+      float v = __uint_as_float(kth_hi);
+      if (stat != 0) {
+        float acc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)l_hi, 0));
+        for (int i = 1; i < k; ++i) acc = acc + __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)l_hi, i));
+        v = acc / (float)k;
+      }
+      found = kth_hi != 0xffffffffu && __float_as_uint(v) == q_stat[q];
+    }
+    if (lane < k) {
+      out_ids[q * k + lane] = found ? (int64_t)l_lo : -1;
+      if (out_d2) out_d2[q * k + lane] = found ? l_hi : 0xffffffffu;
+    }
+    if (!found && lane == 0) atomicAdd(not_found, 1);
+  }
+}
+
+template <int DIM>
+struct WitnessKnnOp {
+  static int run(const flooder_witness_knn_t& a, const Levels& lv, hipStream_t st) {
+    int64_t blocks = (a.n_queries + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(witness_knn_kernel<DIM>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
+                       a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
+                       a.n_queries, a.k, a.stat, a.q_simplex, a.q_row, a.q_stat, a.out_ids, a.out_d2, a.not_found);
+    return check_launch("witness_knn");
+  }
+};
+template <>
+struct WitnessKnnOp<1> {
+  static int run(const flooder_witness_knn_t&, const Levels&, hipStream_t) {
+    return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ segment sum
 // Thread (segment, axis): out[target[g], k] = sum of vals[order[i], k] over i in [seg_ptr[g], seg_ptr[g+1]), in order.
 __global__ __launch_bounds__(256) void segment_sum_kernel(const float* __restrict__ vals, int dim,
@@ -240,6 +421,27 @@ int flooder_witness_search(const flooder_witness_search_t* p, void* stream) {
   if ((lv.count[0] + FAN - 1) / FAN >= (1LL << 27))
     return fail(FLOODER_E_ARG, "flooder_witness_search: cloud too large for the search stack encoding");
   return dispatch_dim<WitnessOp>(a.dim, a, lv, (hipStream_t)stream);
+}
+
+int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream) {
+  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_witness_knn_t))
+    return fail(FLOODER_E_ARG, "flooder_witness_knn: bad parameter block (abi / size)");
+  flooder_witness_knn_t a;
+  std::memset(&a, 0, sizeof(a));
+  std::memcpy(&a, p, p->size);
+  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_witness_knn: k must be in 1..32");
+  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
+  if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_witness_knn: stat must be 0 (kth) or 1 (dtm)");
+  if (a.n_pts < a.k) return fail(FLOODER_E_ARG, "flooder_witness_knn: fewer points than k");
+  if (a.n_pts > 0x7fffffffLL) return fail(FLOODER_E_ARG, "flooder_witness_knn: more than 2^31 - 1 points");
+  if (a.n_queries == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.order || !a.verts || !a.weights || !a.q_simplex || !a.q_row || !a.q_stat ||
+      !a.out_ids || !a.not_found || a.k1 < 1 || a.R < 1 || a.n_queries < 0)
+    return fail(FLOODER_E_ARG, "flooder_witness_knn: bad argument (null pointer, k1, R, n_queries)");
+  const Levels lv = make_levels(a.n_pts);
+  if ((lv.count[0] + FAN - 1) / FAN >= (1LL << 27))
+    return fail(FLOODER_E_ARG, "flooder_witness_knn: cloud too large for the search stack encoding");
+  return dispatch_dim<WitnessKnnOp>(a.dim, a, lv, (hipStream_t)stream);
 }
 
 int flooder_segment_sum_f32(const float* vals, int dim, const int64_t* order, const int64_t* seg_ptr,

@@ -10,6 +10,11 @@ runs the sweep of ``flood_complex`` and recovers (w*, j*) exactly: on ROCm tenso
 of the unfused sweep (``csrc/flood_grad.hip``: face argmax, witness search in the box tree of the cloud), on CPU tensors
 from the indices of the kd-tree query.  The values themselves are the ones ``flood_complex`` returns.  See DESIGN.md,
 "Witnesses and gradients".
+
+``neighbors=k`` (the robust filtration): the witness is p* and its k nearest points x_(1) .. x_(k), ordered by (distance,
+id) - on ROCm tensors recovered exactly by ``flooder_witness_knn`` from the bits of the k-nearest sweep's statistic.
+``"kth"``: f = |p* - x_(k)|, the formulas above at x_(k); ``"dtm"``: f = sqrt(mean_i |p* - x_(i)|^2),
+df/dpoints[id_(i)] = -(p* - x_(i)) / (k f), df/dL_j = w*_j (p* - mean x) / f.
 """
 
 from __future__ import annotations
@@ -38,11 +43,14 @@ class FloodFiltration:
     ``values[d]``           (n_d,) on the points' device and dtype, differentiable w.r.t. points and landmarks
     ``witness_point[d]``    (n_d,) int64: j*, the row of ``points`` nearest to the witness sample (-1: none)
     ``witness_weights[d]``  (n_d, d+1): barycentric weights w* of the witness sample over the simplex's OWN vertices
+    ``witness_neighbors[d]`` (n_d, k) int64: the ``neighbors`` = k nearest points of the witness sample, ascending by
+                            (distance, id) (-1: none); its last column is ``witness_point[d]``, the k-th nearest
+    ``neighbors``, ``neighbor_stat``  the robust filtration's arguments (1, "kth": the plain filtration)
     ``tree``                the ``flooder_amd.SimplexTree`` with the (detached) values
     """
 
     def __init__(self, tree: SimplexTree, simplices, values, witness_point, witness_weights, landmark_ids,
-                 faces_not_found: int = 0):
+                 faces_not_found: int = 0, witness_neighbors=None, neighbors: int = 1, neighbor_stat: str = "kth"):
         self.tree = tree
         self.simplices: List[torch.Tensor] = simplices
         self.values: List[torch.Tensor] = values
@@ -50,6 +58,10 @@ class FloodFiltration:
         self.witness_weights: List[torch.Tensor] = witness_weights
         self.landmark_ids = landmark_ids   # int64 rows of `points` the landmarks were taken from (integer landmarks)
         self.faces_not_found = faces_not_found   # faces the device witness search found no point for (0; else it raises)
+        self.witness_neighbors: List[torch.Tensor] = (witness_neighbors if witness_neighbors is not None
+                                                      else [p.unsqueeze(1) for p in witness_point])
+        self.neighbors = neighbors
+        self.neighbor_stat = neighbor_stat
 
     def to_dict(self) -> Dict[tuple, float]:
         """``{simplex: value}``, what ``flood_complex`` returns for the same arguments."""
@@ -121,12 +133,25 @@ def _check_index(index: "core.PointIndex", points: torch.Tensor) -> None:
 
 def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[int] = None, points_per_edge: int = 30,
                      num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, method: Optional[str] = None,
-                     index: Optional["core.PointIndex"] = None) -> FloodFiltration:
+                     index: Optional["core.PointIndex"] = None, neighbors: int = 1,
+                     neighbor_stat: str = "kth") -> FloodFiltration:
     """Flood filtration with exact witnesses: the values of ``flood_complex(points, landmarks, max_dimension,
-    points_per_edge, num_rand, start_idx=start_idx, method=method, index=index)``, differentiable w.r.t. ``points`` and
-    ``landmarks``.  Integer ``landmarks``: farthest-point sampling as ``flood_complex`` does it, the landmarks are
-    ``points.index_select(0, idx)`` (their gradient flows into ``points``).  CPU tensors (float32, float64) and ROCm
-    float32 in ambient dimension 2 to 8, methods ``"cell"`` / ``"bvh"``."""
+    points_per_edge, num_rand, start_idx=start_idx, method=method, index=index, neighbors=neighbors,
+    neighbor_stat=neighbor_stat)``, differentiable w.r.t. ``points`` and ``landmarks``.  Integer ``landmarks``:
+    farthest-point sampling as ``flood_complex`` does it, the landmarks are ``points.index_select(0, idx)`` (their
+    gradient flows into ``points``).  CPU tensors (float32, float64) and ROCm float32 in ambient dimension 2 to 8,
+    methods ``"cell"`` / ``"bvh"``.
+
+    ``neighbors=k`` / ``neighbor_stat``: the robust filtration of ``flood_complex``, judged by the same rules with the
+    same messages (k > 1 on ROCm: the tree sweep, ``method`` None / "auto" / "bvh").  The witness of a value is then the
+    sample p* with the largest statistic and its k nearest points x_(1) .. x_(k), ``witness_neighbors``, ordered by
+    (distance, id); ``"kth"``: f = |p* - x_(k)| with the plain gradient at x_(k); ``"dtm"``: f = sqrt(mean_i |p* - x_(i)|^2),
+    df/dx_(i) = -(p* - x_(i)) / (k f), df/dp* = (p* - mean x) / f.  On ROCm tensors the k are the k smallest by (d2 in
+    the sweep's float32 arithmetic, id): among points equidistant at the k-th place the smallest ids.  On CPU tensors
+    they are what ``scipy.spatial.KDTree.query(k=neighbors)`` returns, stably sorted by (distance, id): WHICH of
+    several points equidistant at the k-th place is among them is scipy's choice.  ``neighbors=1`` is the call without
+    the argument, whichever statistic is named."""
+    neighbors, method = core._check_neighbors(points, neighbors, neighbor_stat, method)
     method = _check_args(points, method)
     if index is not None:
         _check_index(index, points)
@@ -162,28 +187,35 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
         own_val = [np.full(s.shape[0], np.nan) for s in simplices]
         own_pt = [np.full(s.shape[0], -1, dtype=np.int64) for s in simplices]
         own_w = [np.zeros((s.shape[0], d + 1)) for d, s in enumerate(simplices)]
+        # (neighbors > 1: the k nearest points of every witness sample; own_pt is then its last column)
+        own_nb = [np.full((s.shape[0], neighbors), -1, dtype=np.int64) for s in simplices] if neighbors > 1 else None
+        knn = (neighbors, neighbor_stat, own_nb) if neighbors > 1 else None
         not_found = 0
         if points.is_cuda:
             not_found = _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index,
-                                   own_val, own_pt, own_w)
+                                   own_val, own_pt, own_w, knn)
         else:
-            _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w)
+            _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w, knn)
         for d in range(n_dims):
             vals = tree.filtrations_of_dimension(d)
             if vals.shape[0]:
                 vals[:] = own_val[d]
         tree._persistence = None
         tree.make_filtration_non_decreasing()
-        wp, ww = _inherit(tree, own_val, own_pt, own_w, n_dims)
+        wp, ww, wn = _inherit(tree, own_val, own_pt, own_w, n_dims, own_nb)
 
     dev, dt = points.device, points.dtype
     vals_t = [torch.as_tensor(tree.filtrations_of_dimension(d), dtype=dt).to(dev) for d in range(n_dims)]
     F = FloodFiltration(tree, [torch.as_tensor(s) for s in simplices], None,
                         [torch.as_tensor(p).to(dev) for p in wp], [torch.as_tensor(w, dtype=dt).to(dev) for w in ww],
-                        landmark_ids, not_found)
+                        landmark_ids, not_found, None if wn is None else [torch.as_tensor(n).to(dev) for n in wn],
+                        neighbors, neighbor_stat)
     # (the context keeps the witness tensors, not F: F holds the outputs of this very node - a cycle through autograd's
     # C++ graph that the garbage collector cannot break)
-    flat = _FloodValues.apply(points, landmarks, torch.cat(vals_t), (F.simplices, F.witness_point, F.witness_weights))
+    witnesses = (F.simplices, F.witness_point, F.witness_weights)
+    if neighbors > 1 and neighbor_stat == "dtm":    # ("kth": the gradient sits at witness_point, the k-th nearest)
+        witnesses += (F.witness_neighbors,)
+    flat = _FloodValues.apply(points, landmarks, torch.cat(vals_t), witnesses)
     F.values = list(torch.split(flat, [v.shape[0] for v in vals_t]))
     return F
 
@@ -248,7 +280,8 @@ def _grad_face_rows(plan: "core.SamplePlan"):
     return got
 
 
-def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index, own_val, own_pt, own_w):
+def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index, own_val, own_pt, own_w,
+               knn=None):
     lib = _native.load()
     dev = pts.device
     torch.cuda.set_device(dev)
@@ -279,8 +312,11 @@ def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
             plan, v_idx_np = core.SamplePlan(weights, faces), None
         R = weights.shape[0]
         got = []
-        sweep = core._sweep_dimension_cell if method == "cell" else core._sweep_dimension_bvh
-        face_dev, _ = sweep(index, sv, weights, faces, got.append, plan=plan)
+        if knn is not None:    # (S, R) bits of the squared statistic instead of the minimum d2
+            face_dev, _ = core._sweep_dimension_knn(index, sv, weights, faces, knn[0], knn[1], plan=plan, keep=got.append)
+        else:
+            sweep = core._sweep_dimension_cell if method == "cell" else core._sweep_dimension_bvh
+            face_dev, _ = sweep(index, sv, weights, faces, got.append, plan=plan)
         d2 = got[0]
         F = faces.n_faces
         keys = torch.empty((S, F), dtype=torch.int64, device=dev)
@@ -312,15 +348,25 @@ def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
             r_q = torch.where(ok_r, plan.inv[torch.where(ok_r, r_w, 0)], -1)   # ... and its swept column (-1: none)
             bits = (kw >> 32)
             n_q = int(covered.shape[0])
-            out_pt = torch.empty(n_q, dtype=torch.int64, device=dev)
             q_s = s_q.to(torch.int32).contiguous()
             q_r = r_q.to(torch.int32).contiguous()
             q_b = bits.to(torch.int32).contiguous()
-            blk = _native.WitnessSearch(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=d + 1, nodes=index.nodes,
-                                        order=index.order32, verts=sv, weights=plan.w_perm, R=R, n_simplices=S, n_queries=n_q,
-                                        q_simplex=q_s, q_row=q_r, q_d2=q_b, out_point=out_pt, not_found=not_found)
-            _native.check(lib.flooder_witness_search(ctypes.byref(blk), st), "flooder_witness_search")
             cov = covered.cpu().numpy()
+            if knn is not None:
+                out_nb = torch.empty((n_q, knn[0]), dtype=torch.int64, device=dev)
+                blk = _native.WitnessKnn(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=d + 1, nodes=index.nodes,
+                                         order=index.order32, verts=sv, weights=plan.w_perm, R=R, k=knn[0], n_simplices=S,
+                                         n_queries=n_q, q_simplex=q_s, q_row=q_r, q_stat=q_b, out_ids=out_nb,
+                                         not_found=not_found, stat=core.NEIGHBOR_STATS.index(knn[1]))
+                _native.check(lib.flooder_witness_knn(ctypes.byref(blk), st), "flooder_witness_knn")
+                knn[2][k - 1][cov] = out_nb.cpu().numpy()
+                out_pt = out_nb[:, -1]
+            else:
+                out_pt = torch.empty(n_q, dtype=torch.int64, device=dev)
+                blk = _native.WitnessSearch(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=d + 1, nodes=index.nodes,
+                                            order=index.order32, verts=sv, weights=plan.w_perm, R=R, n_simplices=S, n_queries=n_q,
+                                            q_simplex=q_s, q_row=q_r, q_d2=q_b, out_point=out_pt, not_found=not_found)
+                _native.check(lib.flooder_witness_search(ctypes.byref(blk), st), "flooder_witness_search")
             own_val[k - 1][cov] = val[win].cpu().numpy().astype(np.float64)
             own_pt[k - 1][cov] = out_pt.cpu().numpy()
             w_full = plan.w_perm[r_q.clamp(min=0)]           # (n_q, d+1) over the swept simplex's vertices
@@ -333,7 +379,7 @@ def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
     return missing
 
 
-def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w):
+def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w, knn=None):
     from scipy.spatial import KDTree
 
     kdtree = KDTree(np.asarray(pts))
@@ -359,7 +405,15 @@ def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
             faces = core._FaceTable(None, weights.shape[0], pts.device)
             v_idx_np = None
         samples = weights.unsqueeze(0) @ sv
-        dist, idx = kdtree.query(np.asarray(samples), workers=core.CPU_WORKERS)
+        if knn is not None:   # the statistic as flood_complex's CPU branch computes it
+            dist_k, idx_k = kdtree.query(np.asarray(samples), k=knn[0], workers=core.CPU_WORKERS)   # (S, R, k), ascending
+            if knn[1] == "kth":
+                dist = dist_k[..., -1]
+            else:
+                dist = np.sqrt(np.square(dist_k.astype(np.float64)).sum(axis=-1) / knn[0])
+            idx = idx_k[..., -1]
+        else:
+            dist, idx = kdtree.query(np.asarray(samples), workers=core.CPU_WORKERS)
         fptr = faces.ptr.numpy()
         frows = faces.rows.numpy()
         w_np = weights.numpy()
@@ -388,6 +442,14 @@ def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
             own_val[k - 1][tr] = val.reshape(-1)[win]
             own_pt[k - 1][tr] = idx[s_q, r_q]
             own_w[k - 1][tr] = w_np[r_q[:, None], v_idx[j_q]]
+            if knn is not None:   # the k neighbours, stably sorted by (distance, id)
+                dk, ik = dist_k[s_q, r_q], idx_k[s_q, r_q].astype(np.int64)
+                by_id = np.argsort(ik, axis=1, kind="stable")
+                dk, ik = np.take_along_axis(dk, by_id, axis=1), np.take_along_axis(ik, by_id, axis=1)
+                by_d = np.argsort(dk, axis=1, kind="stable")
+                ik = np.take_along_axis(ik, by_d, axis=1)
+                knn[2][k - 1][tr] = ik
+                own_pt[k - 1][tr] = ik[:, -1]
 
 
 def _facet_rows(tree: SimplexTree, d: int) -> np.ndarray:
@@ -398,12 +460,14 @@ def _facet_rows(tree: SimplexTree, d: int) -> np.ndarray:
     return np.stack([tree._locate(d - 1, np.delete(rows, j, axis=1)) for j in range(d + 1)], axis=1)
 
 
-def _inherit(tree: SimplexTree, own_val, own_pt, own_w, n_dims: int):
+def _inherit(tree: SimplexTree, own_val, own_pt, own_w, n_dims: int, own_nb=None):
     """Witnesses of the final (monotone) values: a simplex that ``make_filtration_non_decreasing`` raised to a facet's
     value takes that facet's witness (the first facet, omitting vertex j, that holds the value), its weights
-    re-expressed over the simplex's own vertices (0 at the omitted one)."""
+    re-expressed over the simplex's own vertices (0 at the omitted one).  ``own_nb`` (the k nearest points of the
+    witness samples, neighbors > 1) goes along with the witness point."""
     wp = [p.copy() for p in own_pt]
     ww = [w.copy() for w in own_w]
+    wn = [n.copy() for n in own_nb] if own_nb is not None else None
     for d in range(1, n_dims):
         n = wp[d].shape[0]
         if n == 0 or wp[d - 1].shape[0] == 0:
@@ -422,13 +486,15 @@ def _inherit(tree: SimplexTree, own_val, own_pt, own_w, n_dims: int):
         sel, j = sel[has], j[has]
         src = facets[np.nonzero(has)[0], j]
         wp[d][sel] = wp[d - 1][src]
+        if wn is not None:
+            wn[d][sel] = wn[d - 1][src]
         w = np.zeros((sel.shape[0], d + 1))
         for m in range(d + 1):
             take = np.nonzero(j != m)[0]
             col = np.where(m < j[take], m, m - 1)
             w[take, m] = ww[d - 1][src[take], col]
         ww[d][sel] = w
-    return wp, ww
+    return wp, ww, wn
 
 
 # ---------------------------------------------------------------------------------------------------- autograd
@@ -443,14 +509,17 @@ class _FloodValues(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad):
         points, landmarks = ctx.saved_tensors
-        gp, gl = witness_backward(*ctx.witnesses, points.detach(), landmarks.detach(), grad)
+        gp, gl = witness_backward(*ctx.witnesses[:3], points.detach(), landmarks.detach(), grad, *ctx.witnesses[3:])
         return (gp if ctx.needs_input_grad[0] else None), (gl if ctx.needs_input_grad[1] else None), None, None
 
 
 def witness_backward(simplices, witness_point, witness_weights, points: torch.Tensor, landmarks: torch.Tensor,
-                     grad: torch.Tensor):
+                     grad: torch.Tensor, witness_neighbors=None):
     """(grad_points (n, dim), grad_landmarks (L, dim)) of sum(grad * values), in the input dtype.  ROCm tensors: the
-    contributions are summed per target row in a fixed order (``flooder_segment_sum_f32``): bit-identical run to run."""
+    contributions are summed per target row in a fixed order (``flooder_segment_sum_f32``): bit-identical run to run.
+    ``witness_neighbors`` (per dimension (n_d, k)): the values are distances to the empirical measure of those k
+    points, f = sqrt(mean_i |p* - x_(i)|^2); without it f = |p* - points[witness_point]| (the nearest point, or the
+    k-th nearest of the k-distance)."""
     dev, dt = points.device, points.dtype
     dim = points.shape[1]
     tg_p, vl_p, tg_l, vl_l = [], [], [], []
@@ -470,12 +539,25 @@ def witness_backward(simplices, witness_point, witness_weights, points: torch.Te
         V = simp.to(dev)[keep]                                 # (m, d+1) landmark ids
         W = witness_weights[d][keep]                           # (m, d+1)
         p = (W.unsqueeze(2) * landmarks[V]).sum(dim=1)         # p* (m, dim)
-        diff = p - points[jp]
-        f = diff.norm(dim=1, keepdim=True)
-        u = torch.where(f > 0, diff / torch.where(f > 0, f, torch.ones_like(f)), torch.zeros_like(diff))
-        gu = g.unsqueeze(1) * u
-        tg_p.append(jp)
-        vl_p.append(-gu)
+        if witness_neighbors is not None:
+            nb = witness_neighbors[d][keep]                    # (m, k) ids, ascending by (distance, id)
+            kk = nb.shape[1]
+            diffs = p.unsqueeze(1) - points[nb]                # (m, k, dim)
+            f = ((diffs * diffs).sum(dim=2).sum(dim=1, keepdim=True) / kk).sqrt()
+            safe = torch.where(f > 0, f, torch.ones_like(f))
+            # df/dx_(i) = -(p* - x_(i)) / (k f);  df/dp* = (p* - mean x) / f, the sum of the k terms
+            each = torch.where(f.unsqueeze(2) > 0, g.reshape(-1, 1, 1) * diffs / (kk * safe).unsqueeze(2),
+                               torch.zeros_like(diffs))
+            gu = each.sum(dim=1)
+            tg_p.append(nb.reshape(-1))
+            vl_p.append(-each.reshape(-1, dim))
+        else:
+            diff = p - points[jp]
+            f = diff.norm(dim=1, keepdim=True)
+            u = torch.where(f > 0, diff / torch.where(f > 0, f, torch.ones_like(f)), torch.zeros_like(diff))
+            gu = g.unsqueeze(1) * u
+            tg_p.append(jp)
+            vl_p.append(-gu)
         nz = W != 0
         rows_i, cols_i = torch.nonzero(nz, as_tuple=True)
         tg_l.append(V[rows_i, cols_i])

@@ -787,6 +787,41 @@ typedef struct flooder_knn_sweep_s {        /* flooder_sweep_knn_f32 */
 } flooder_knn_sweep_t;
 int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream);
 
+/*
+ * flooder_witness_knn (csrc/flood_grad.hip; flooder_amd.grad with neighbors > 1): the witness of a robust value.  Per
+ * query q, p* = sum_j weights[q_row[q], j] * verts[q_simplex[q], j, :] (fma in vertex order, as the sweeps), then the
+ * k smallest keys (d2 word, original id = order[row]) over ALL n_pts points - d2 = t0*t0, then fma(t, t, d2), a point
+ * that occurs twice is two ids, rows of the padded last leaf are no candidates - are written ascending:
+ * out_ids[q, 0..k) and, unless NULL, out_d2[q, 0..k).  The statistic is recomputed from the k words as
+ * flooder_sweep_knn_f32 computes it (stat 0: the last word; stat 1: ascending sequential float32 sum / (float)k) and
+ * compared with q_stat[q]: if the bits differ, or q_simplex / q_row is out of range, the whole row is -1 (all ones in
+ * out_d2) and *not_found (one zeroed word) grows by 1.  k in 1..FLOODER_KNN_MAX, k <= n_pts <= 2^31 - 1, dim in 2..8.
+ */
+typedef struct flooder_witness_knn_s {      /* flooder_witness_knn */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const int32_t* order;       /* PointIndex.order32: tree row -> original id */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) the swept weight rows */
+  int32_t R;
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_MAX */
+  int64_t n_simplices;
+  int64_t n_queries;
+  const int32_t* q_simplex;   /* (n_queries,) queue position of the simplex */
+  const int32_t* q_row;       /* (n_queries,) weight row */
+  const uint32_t* q_stat;     /* (n_queries,) bits of the squared statistic, as flooder_sweep_knn_f32 wrote them */
+  int64_t* out_ids;           /* (n_queries, k) */
+  uint32_t* out_d2;           /* (n_queries, k); may be NULL */
+  int32_t* not_found;         /* one zeroed word */
+  int32_t stat;               /* 0 = kth, 1 = dtm */
+  int32_t reserved;
+} flooder_witness_knn_t;
+int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
