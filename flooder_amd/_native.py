@@ -157,6 +157,8 @@ SIGNATURES = {
     "flooder_cloud_kind": (c_int, [c_void_p, c_int, c_void_p]),
     "flooder_wit_max_rows": (c_int, []),
     "flooder_wit_max_coarse": (c_int, []),
+    "flooder_finish_single_tiles": (c_int, []),
+    "flooder_finish_single_batches": (c_int, []),
     "flooder_face_values_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "flooder_simplex_weight_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "flooder_simplex_planes_forget": (None, []),

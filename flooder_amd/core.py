@@ -367,6 +367,7 @@ class SweepStats:
         self.deferred_chunks = 0     # chunks the run-of-four launch handed to the per-chunk launch
         self.dense_tiles = 0         # tiles of 64 samples the per-chunk launch handed to the tile launch
         self.hard_entries = (0, 0)   # tiles the finish gave to a whole workgroup (top pass, rest pass)
+        self.finish_single_left = 0  # samples the finish's short-list kernel left to the passes behind it
 
 
 LAST_STATS = SweepStats()
@@ -1528,6 +1529,7 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             LAST_STATS.dense_tiles = int(ctl[18].item())
             c_h = fctl[:24].tolist()
             LAST_STATS.hard_entries = (int(c_h[5]), int(c_h[7]))
+            LAST_STATS.finish_single_left = int(c_h[8])
         out_face = torch.empty(n_slots if face_slots is not None else (S, F), dtype=torch.float32, device=dev)
         with _span(timer, "face_max"):
             _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), n_slots, _native.ptr(out_face), st),

@@ -69,7 +69,33 @@ struct HardLists {
   int cap;     // entries per list
   int budget;  // scale of the leaf budget of a tile (0: no hard tiles)
   int budget_min = 64;  // ... and what a tile of a SHORT list may evaluate at least before it counts as hard (leaves)
+  // samples finish_single_kernel ran in front of this launch and left over (null: it did not run)
+  const int32_t* single_left = nullptr;
 };
+
+// Short lists (finish_single_kernel below): the longest list it takes, the four-leaf batches a sample may cost there
+// before it is left to the passes behind it, and the control word that counts those samples.
+#ifndef FLOODER_FINISH_SINGLE_TILES
+#define FLOODER_FINISH_SINGLE_TILES 1024
+#endif
+#ifndef FLOODER_FINISH_SINGLE_BATCHES
+#define FLOODER_FINISH_SINGLE_BATCHES 48
+#endif
+
+constexpr int FINISH_SINGLE_TILES = FLOODER_FINISH_SINGLE_TILES;
+constexpr int FINISH_SINGLE_BATCHES = FLOODER_FINISH_SINGLE_BATCHES;
+#ifndef FLOODER_FINISH_SINGLE_WAVES
+#define FLOODER_FINISH_SINGLE_WAVES 4
+#endif
+constexpr int SINGLE_WAVES = FLOODER_FINISH_SINGLE_WAVES;  // waves per workgroup (independent of each other)
+constexpr int SINGLE_LEFT_WORD = 8;
+// The budget follows option "finish_budget_min" - what a wave of a short list may spend alone before the stronger
+// machinery takes over - in proportion: FINISH_SINGLE_BATCHES batches at the option's default of 64 leaves, at least one.
+inline int single_batches() {
+  const long long b = (long long)FINISH_SINGLE_BATCHES * g_finish_budget_min / 64;
+  return (int)(b < 1 ? 1 : (b > (1 << 20) ? (1 << 20) : b));
+}
+static_assert(FINISH_SINGLE_TILES >= 1 && FINISH_SINGLE_TILES <= SHORT_LIST, "a list finish_single_kernel takes is a short one");
 
 constexpr int TEAM_WAVES = 16;
 
@@ -118,6 +144,8 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
   if (n_base == 0) return;
   // a short list goes straight to the last pass (every tile is searched at once anyway; two launches saved)
   if (mode < 2 && n_list <= SHORT_LIST) return;
+  // ... and a list that finish_single_kernel has worked off completely needs no pass at all
+  if (!TEAM && hl.single_left != nullptr && n_list <= FINISH_SINGLE_TILES && hl.single_left[0] == 0) return;
   const int64_t n_items = TEAM ? n_base : n_base * subs;
   // a workgroup that will find nothing leaves before it stages the tree top (32 KB from L2): with a wave per item
   // (the static deal below) those are the workgroups behind the last item - 800 of 1024 on cfg 2's short list -, in a
@@ -622,6 +650,184 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
   }
 }
 
+// Short lists: one wave per SAMPLE.  A list of a few hundred tiles (cfg 2's 207, a rank's share of a multi-GPU run, a
+// small cloud) has fewer live samples than the chip has waves, and the passes above then last as long as their
+// longest wave: four samples one after the other, each a chain of dependent one-leaf steps whose 64 lanes hold the
+// same few samples.  Here wave w owns sample w % 64 of tile flag_list[w / 64] (static deal: no queue, no hand-over,
+// nothing waits on another workgroup) and spends its lanes on POINTS: the lanes hold the 64 child boxes of a node on
+// the way down, and at the leaf level lane l evaluates point l % 16 of candidate leaf l / 16 - the nearest unvisited
+// leaf of the group and up to three more that the bound does not exclude - with one vector load and one wave minimum
+// for four leaves.  The arithmetic is that of finish_faces_kernel: the sample from the same fmaf chain, d2 as t * t
+// then one fmaf per further axis, the box bound of child_bounds with the sample as its own box, pruning by
+// !(lb * SAFE < best).  A search that runs to its end has seen every leaf whose box could hold a nearer point, so its
+// minimum is exact and is delivered as a focus round delivers; a search whose bound falls to the running maximum of
+// every face of its sample stops (the sample cannot raise a face: the drop rule above) and leaves that bound in d2.
+// A sample that has cost more than `budget` batches (far field: thousands of leaves at almost the same distance)
+// writes the bound it reached, unsettled, and is counted in left[0]: the passes above run behind this launch on the
+// same list, drop on arrival what is settled or bounded, and search the left-overs with all their machinery.  Face
+// values therefore do not depend on what this kernel gets done - and are the exhaustive ones bit for bit, since only
+// exact minima are ever delivered.
+// A list longer than FINISH_SINGLE_TILES is not touched (every workgroup returns on its first load).
+template <int DIM>
+__global__ __launch_bounds__(64 * SINGLE_WAVES) void finish_single_kernel(
+    const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
+    const float* __restrict__ weights, int k1, int R, const int32_t* __restrict__ flag_list,
+    const int32_t* __restrict__ flag_count, int refresh_every, int budget, uint32_t* __restrict__ d2, FaceAcc acc,
+    int32_t* __restrict__ left, unsigned long long* __restrict__ stats) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ float s_lb[SINGLE_WAVES][MAXL][FAN];  // per wave and inner level: bounds of the open group's children
+  const int lane = threadIdx.x & 63;
+  const int wv = wave_uniform((int)(threadIdx.x >> 6));
+  const int n_list = flag_count[0];
+  if (n_list > FINISH_SINGLE_TILES) return;
+  const int wave_id = (int)blockIdx.x * SINGLE_WAVES + wv;
+  if ((wave_id >> 6) >= n_list) return;
+  const int tiles = (R + 63) >> 6;
+  const int item = flag_list[wave_id >> 6];
+  const int64_t s = item / tiles;
+  const int r = (item - (int)(s * tiles)) * 64 + (wave_id & 63);
+  if (r >= R) return;  // (rows of the last tile beyond R)
+
+  // ---- arrival: the sample, its seed, its faces and the smallest of their running maxima
+  const int64_t cell = s * (int64_t)R + r;
+  const uint32_t seed = d2[cell];
+  if ((seed & SETTLED_BIT) != 0u) return;  // settled by the cell sweep: delivered already
+  const uint32_t mb = acc.memb[r];
+  if (mb == 0u) return;                    // on no face: nothing to deliver
+  float p[DIM];
+  const float* vs = verts + s * (int64_t)k1 * DIM;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) p[k] = 0.f;
+  for (int j = 0; j < k1; ++j) {
+    const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) p[k] = __builtin_fmaf(w, vs[j * DIM + k], p[k]);
+  }
+  float best = __uint_as_float(seed);
+  // lane f of a face the sample lies on keeps that face's slot and the last value read of its maximum
+  const bool my_face = lane < acc.n_faces && ((mb >> lane) & 1u) != 0u;
+  const int64_t my_slot = my_face ? acc.slot_of(s, lane) : 0;
+  uint32_t fb_seen = 0u;
+  auto threshold = [&]() -> uint32_t {
+    uint32_t fb = 0xffffffffu;
+    if (my_face) {
+      fb = __hip_atomic_load(acc.face_bits + my_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      fb_seen = fb;
+    }
+    return wave_min_u32(fb);
+  };
+  uint32_t thr = threshold();
+  if (!(__float_as_uint(best) > thr)) return;  // not live: below the maximum of each of its faces
+
+  // ---- search, nearest first; `grp` is the open group of level `lvl` (its parent's index: grp >> 6 one level up)
+  auto child_lb = [&](int lvl, int64_t grp) -> float {
+    const int64_t idx = grp * FAN + lane;
+    float lb = __builtin_inff();
+    if (idx < lv.count[lvl]) {
+      float lo[DP], hi[DP];
+      const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
+      load_row<DP>(nb, lo);
+      load_row<DP>(nb + DP, hi);
+      lb = 0.f;
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) {
+        const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - p[k], p[k] - hi[k]), 0.f);
+        lb = __builtin_fmaf(gap, gap, lb);
+      }
+    }
+    return lb;
+  };
+  const int topl = lv.n_levels - 1;
+  unsigned long long n_leaf = 0, n_node = 1;
+  int lvl = topl;
+  int64_t grp = 0;
+  float lb0 = child_lb(topl, 0);  // the bounds of the open LEAF group stay in registers
+  if (topl > 0) s_lb[wv][topl][lane] = lb0;
+  int batches = 0, since = 0;
+  const int refresh_batches = refresh_every >= 4 ? refresh_every / 4 : 1;
+  bool exact = true, over = false;
+  for (;;) {
+    if (lvl > 0) {
+      const float lbv = s_lb[wv][lvl][lane];
+      const float mn = wave_min_f32(lbv);
+      if (!(mn * SAFE < best)) {  // nothing left in this group can hold a nearer point
+        if (++lvl > topl) break;
+        grp >>= 6;
+        continue;
+      }
+      const int j = __builtin_ctzll(__ballot(lbv == mn));
+      if (lane == j) s_lb[wv][lvl][lane] = __builtin_inff();  // visited
+      grp = grp * FAN + j;
+      --lvl;
+      const float lb = child_lb(lvl, grp);
+      ++n_node;
+      if (lvl > 0) s_lb[wv][lvl][lane] = lb;
+      else lb0 = lb;
+      continue;
+    }
+    // ---- leaf level: the nearest unvisited leaf of the group and up to three more the bound does not exclude
+    const float mn = wave_min_f32(lb0);
+    if (!(mn * SAFE < best)) {
+      if (++lvl > topl) break;
+      grp >>= 6;
+      continue;
+    }
+    if (batches >= budget) {  // too long for a wave alone: left to the passes behind this launch
+      exact = false;
+      over = true;
+      break;
+    }
+    const int j0 = __builtin_ctzll(__ballot(lb0 == mn));
+    unsigned long long cm = __ballot(lb0 * SAFE < best) & ~(1ull << j0);
+    int jq[4] = {j0, -1, -1, -1};
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+      if (cm != 0ull) {
+        jq[q] = __builtin_ctzll(cm);
+        cm &= cm - 1ull;
+      }
+    if (lane == jq[0] || lane == jq[1] || lane == jq[2] || lane == jq[3]) lb0 = __builtin_inff();  // visited
+    const int q = lane >> 4;
+    const int jm = q == 0 ? jq[0] : (q == 1 ? jq[1] : (q == 2 ? jq[2] : jq[3]));
+    float d = __builtin_inff();
+    if (jm >= 0) {  // (a leaf with a finite bound exists, pad rows of the last one included: +inf rows, never nearest)
+      float x[DP];
+      load_row<DP>(pts + ((grp * FAN + jm) * (int64_t)LEAF + (lane & 15)) * DP, x);
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) {
+        const float t = p[k] - x[k];
+        d = k == 0 ? t * t : __builtin_fmaf(t, t, d);
+      }
+    }
+    best = __builtin_fminf(best, wave_min_f32(d));
+    n_leaf += 1 + (jq[1] >= 0) + (jq[2] >= 0) + (jq[3] >= 0);
+    ++batches;
+    if (++since >= refresh_batches) {  // other waves may have raised the face maxima meanwhile
+      since = 0;
+      thr = threshold();
+    }
+    if (!(__float_as_uint(best) > thr)) {  // cannot raise a face any more: dropped, as a focus round drops it
+      exact = false;
+      break;
+    }
+  }
+  if (exact) {
+    // ---- deliver: only where the value can raise the maximum as last read
+    const uint32_t v = __float_as_uint(best);
+    if (my_face && v > fb_seen) atomicMax(&acc.face_bits[my_slot], v);
+    if (lane == 0) d2[cell] = v | SETTLED_BIT;
+  } else if (lane == 0) {
+    d2[cell] = __float_as_uint(best);  // the bound reached: the passes behind this launch start from it
+    if (over) atomicAdd(left, 1);
+  }
+  if (stats && lane == 0) {
+    atomicAdd(&stats[0], n_leaf);
+    atomicAdd(&stats[1], n_leaf);
+    atomicAdd(&stats[2], n_node);
+    atomicAdd(&stats[5], 1ull);
+  }
+}
+
 // Counting sort of the flagged tiles by the top 12 bits of their probe bound, largest first (sweep: keys and the
 // histogram; here: every block scans the histogram for itself, then scatters its share of the list).  The bound
 // predicts the length of a tile's search well (rank correlation 0.8 on the torus of cfg 3); with the long searches
@@ -710,6 +916,13 @@ struct FinishOp {
     if (ordered)
       hipLaunchKernelGGL(order_flags_kernel, dim3(256), dim3(256), 0, st, flag_list, flag_key, flag_count, flag_hist,
                          flag_hist + KEY_BUCKETS, flag_sorted);
+    // a short list: a wave per sample first (finish_single_kernel); what it leaves over, the passes below pick up.
+    // (option "bvh_subs" 1 - tiles are not split over waves - turns it off)
+    const bool single = g_bvh_subs > 1;
+    if (single)
+      hipLaunchKernelGGL((finish_single_kernel<DIM>), dim3(FINISH_SINGLE_TILES * 64 / SINGLE_WAVES), dim3(64 * SINGLE_WAVES),
+                         0, st, pts, nodes, lv, verts, weights, k1, R, flag_list, flag_count, g_finish_refresh,
+                         single_batches(), d2, acc, ctl + SINGLE_LEFT_WORD, stats);
     const int64_t words = (int64_t)hard_cap * 2;  // entries, masks (u64)
     auto list = [&](int which, bool in, int32_t* cnt, HardLists& hl) {
       unsigned long long* base = hard + which * words;
@@ -740,7 +953,8 @@ struct FinishOp {
                            g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f, g_finish_refresh,
                            queue, d2, acc, top, top_list, ctl + 3, hl, stats);
     };
-    const HardLists none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hard_cap, 0};
+    HardLists none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hard_cap, 0};
+    none.single_left = single ? ctl + SINGLE_LEFT_WORD : nullptr;
     // (the per-wave passes pop from sharded heads behind the 24 control words; the team passes keep one word)
     int32_t* q0 = ctl + 24;
     int32_t* q1 = ctl + 24 + FLOODER_QUEUE_WORDS;
@@ -752,7 +966,8 @@ struct FinishOp {
       return check_launch("finish_faces");
     }
     // ctl: [0..2] queue heads of the probe / top / rest passes, [3] simplices with a top tile, [4], [5] queue head
-    // and list length of the top pass's hard entries, [6], [7] those of the rest pass's
+    // and list length of the top pass's hard entries, [6], [7] those of the rest pass's, [8] samples the short-list
+    // kernel left over
     HardLists a = none, b = none, c = none, d = none;
     a.budget = c.budget = g_finish_budget;
     a.budget_min = c.budget_min = g_finish_budget_min;
@@ -774,6 +989,9 @@ struct FinishOp {
 }  // namespace
 
 extern "C" {
+
+int flooder_finish_single_tiles(void) { return FINISH_SINGLE_TILES; }
+int flooder_finish_single_batches(void) { return single_batches(); }
 
 int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                              const float* verts, const float* weights, int k1, int R, int64_t n_simplices,

@@ -452,8 +452,18 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
  *   searching an interleaved share of the level-1 nodes of the box tree, the minima combined in LDS round by round
  *   (one more launch; without scratch, or with the budget 0, one wave works every tile off alone);
  *   stats: NULL or 7 zeroed uint64 {leaves evaluated, leaves tested, nodes expanded, -, tiles dropped on arrival in
- *   the last pass, samples live on arrival in the last pass, -}.
+ *   the last pass, samples live on arrival in the last pass, focus rounds}.
+ * A list of at most flooder_finish_single_tiles() tiles first gets a launch with ONE WAVE PER SAMPLE (wave w: sample
+ * w % 64 of tile flag_list[w / 64]; lanes = the child boxes of a node on the way down, then the 16 points of four
+ * candidate leaves per step).  A sample that costs more than flooder_finish_single_batches() such steps writes the
+ * bound it reached and is counted in ctl[8]; the passes above run behind that launch, drop what is settled and
+ * search the left-overs, so the values do not depend on it.  It counts leaves, nodes and live samples in stats like
+ * the passes, but no focus rounds: stats[6] = 0 with stats[0] > 0 says the short-list launch did all the work.
+ * Option "bvh_subs" 1 (tiles are not split over waves) turns it off; the batch budget follows option
+ * "finish_budget_min" in proportion (48 batches at its default of 64 leaves, never fewer than one).
  */
+int flooder_finish_single_tiles(void);
+int flooder_finish_single_batches(void);
 int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                              const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
                              const int32_t* flag_list, const int32_t* flag_count, const uint32_t* flag_key,
