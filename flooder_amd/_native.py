@@ -98,6 +98,17 @@ class WitnessKnn(_Block):
         i32 stat; i32 reserved""")
 
 
+# The control words of the fused sweep (include/flooder_hip.h, FLOODER_<name>: int32 word offsets into finish_ctl,
+# defer_ctl and the queue areas); tests/test_host.py compiles the header and compares
+QUEUE_WORDS = 512
+FINISH_CTL_PASS_HEADS, FINISH_CTL_TOP_COUNT = 0, 3
+FINISH_CTL_TOP_HARD_HEAD, FINISH_CTL_TOP_HARD_LEN, FINISH_CTL_REST_HARD_HEAD, FINISH_CTL_REST_HARD_LEN = 4, 5, 6, 7
+FINISH_CTL_SINGLE_LEFT, FINISH_CTL_QUEUES, FINISH_CTL_WORDS = 8, 24, 24 + 3 * QUEUE_WORDS
+DEFER_CTL_COUNT, DEFER_CTL_QUEUE, DEFER_CTL_LIGHT, DEFER_CTL_HEAVY, DEFER_CTL_SPLIT_DONE = 0, 1, 2, 3, 4
+DEFER_CTL_TILE_COUNT, DEFER_CTL_WORDS = 6, 8
+CELL_QUEUE_RUNS, CELL_QUEUE_CHUNKS, CELL_QUEUE_TILES, CELL_QUEUE_WORDS = 0, QUEUE_WORDS, 2 * QUEUE_WORDS, 3 * QUEUE_WORDS
+WIT_QUEUE_ITEM_COUNT = QUEUE_WORDS - 1
+
 _lib = None
 _load_error: Exception | None = None
 _load_missing = False  # the last failure was "file not found" (worth another look after a build)

@@ -53,7 +53,7 @@ CAND_ALIGN = 8
 SWEEP_CHUNK = 2048
 TILE_SAMPLES = 512
 BVH_LEAF = 16
-QUEUE_WORDS = 512   # FLOODER_QUEUE_WORDS: zeroed int32 words of one sharded work queue
+QUEUE_WORDS = _native.QUEUE_WORDS   # FLOODER_QUEUE_WORDS: zeroed int32 words of one sharded work queue
 # device sweep: "cell" = per-simplex LDS cell grid + exact tree finish (default in 2D/3D); "bvh" = box-tree
 # culled exact nearest neighbour (default in other dimensions); "ball" = the reference's formulation
 # (bounding-ball candidate lists + exhaustive sweep of each list)
@@ -1448,9 +1448,10 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         F = faces.n_faces
         tiles = (R + 63) // 64
         slot_t, n_slots = face_slots if face_slots is not None else (None, S * F)
-        # [0] sweep queue, [1] flag count, [12] deferred chunks, [13] their queue, [14:17] light / heavy simplices,
-        # lists on; [24:48] finish (queue heads, [27] top count, [29], [31] hard tiles of the top / rest pass);
-        # [48:] histogram of the flagged tiles' bounds and the cursors of the finish's counting sort
+        # `ctl`, this function's own control block: the flag count, the cell sweep's defer_ctl (its words by name:
+        # _native.DEFER_CTL_*), then the histogram of the flagged tiles' bounds and the cursors of the finish's counting
+        # sort; `fctl` is the finish's (_native.FINISH_CTL_*)
+        CTL_FLAG_COUNT, CTL_DEFER, CTL_HIST = 1, 12, 48
         # (one zero fill for everything that starts at zero: top | ctl | face_bits)
         # (the sharded work-queue heads of the sweep's launches sit in front: QUEUE_WORDS each)
         # (a short queue - a rank's share of a multi-GPU run - leaves the witness sweep's workgroups one simplex each: the
@@ -1460,18 +1461,19 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
                    and index.n <= WIT_MAX_POINTS_PER_SIMPLEX * S and plan.wit is not None)
         # (with the simplex weights wanted, the launch that computes them clears these words and writes the plane rows on
         # its way - flooder_simplex_prepare_f32 below -: one launch instead of three)
-        n_zeroed = (1 if use_wit else 0) * QUEUE_WORDS + 6 * QUEUE_WORDS + 24 + 2 * S + 48 + 8192 + n_slots
+        n_zeroed = ((1 if use_wit else 0) * QUEUE_WORDS + _native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS + 2 * S
+                    + CTL_HIST + 8192 + n_slots)
         zeroed = (torch.empty if CELL_SUPER and SWEEP_PREPARE_FUSED else torch.zeros)(n_zeroed, dtype=torch.int32, device=dev)
         zeroed_all = zeroed
         if use_wit:
             qwit = zeroed[:QUEUE_WORDS]
             zeroed = zeroed[QUEUE_WORDS:]
-        qbuf = zeroed[:3 * QUEUE_WORDS]
-        fctl = zeroed[3 * QUEUE_WORDS:6 * QUEUE_WORDS + 24]   # finish: 24 control words, then its sharded queue heads
-        zeroed = zeroed[6 * QUEUE_WORDS + 24:]
+        qbuf = zeroed[:_native.CELL_QUEUE_WORDS]
+        fctl = zeroed[_native.CELL_QUEUE_WORDS:_native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS]
+        zeroed = zeroed[_native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS:]
         top = zeroed[:2 * S].view(torch.int64)
-        ctl = zeroed[2 * S:2 * S + 48 + 8192]
-        face_bits = zeroed[2 * S + 48 + 8192:]
+        ctl = zeroed[2 * S:2 * S + CTL_HIST + 8192]
+        face_bits = zeroed[2 * S + CTL_HIST + 8192:]
         hard = torch.empty(4 * FINISH_HARD_CAP, dtype=torch.int64, device=dev)
         top_list = torch.empty(S, dtype=torch.int32, device=dev)
         d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
@@ -1499,15 +1501,16 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, density_grid=index.dens,
             cloud_box=index.box, verts=verts, weights=w_perm, R=R, n_faces=F, n_simplices=S, memb=plan.memb_all,
             alpha=float(CELL_ALPHA), face_bits=face_bits, face_slot=slot_t, d2_scratch=d2, flag_list=flags[0],
-            flag_count=ctl[1:].data_ptr(), simplex_weight=wgt, plane_scratch=planes,
+            flag_count=ctl[CTL_FLAG_COUNT:].data_ptr(), simplex_weight=wgt, plane_scratch=planes,
             cell_queue=qbuf.data_ptr(), defer_list=defer_list, defer_c=defer_c, cell_stats=sub(0, 9),
             finish_ctl=fctl.data_ptr(), hard_scratch=hard, hard_cap=FINISH_HARD_CAP, probed=1 if CELL_PROBE else 0,
             finish_stats=sub(9, 16))
         if CELL_PROBE:
-            blk.flag_key, blk.flag_hist, blk.flag_sorted = flags[1].data_ptr(), ctl[48:].data_ptr(), flags[2].data_ptr()
-            blk.top, blk.top_list, blk.top_count = top.data_ptr(), top_list.data_ptr(), fctl[3:].data_ptr()
+            blk.flag_key, blk.flag_hist, blk.flag_sorted = flags[1].data_ptr(), ctl[CTL_HIST:].data_ptr(), flags[2].data_ptr()
+            blk.top, blk.top_list = top.data_ptr(), top_list.data_ptr()
+            blk.top_count = fctl[_native.FINISH_CTL_TOP_COUNT:].data_ptr()
         if CELL_SUPER:
-            blk.defer_ctl, blk.light_list, blk.heavy_list = ctl[12:].data_ptr(), split[0].data_ptr(), split[1].data_ptr()
+            blk.defer_ctl, blk.light_list, blk.heavy_list = ctl[CTL_DEFER:].data_ptr(), split[0].data_ptr(), split[1].data_ptr()
         if use_wit:   # (split[0]: the witness sweep's item list - scratch until the cell sweep's entry fills it)
             blk.n_coarse, blk.coarse_rows, blk.parents = plan.wit[2], plan.wit[0].data_ptr(), plan.wit[1].data_ptr()
             blk.wit_queue, blk.wit_item_list, blk.wit_stats = qwit.data_ptr(), split[0].data_ptr(), _native.ptr(wst) or None
@@ -1524,12 +1527,13 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         with _span(timer, "fallback"):
             _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
         if stats is not None:  # (diagnostic runs only: a host synchronisation)
-            LAST_STATS.deferred_chunks = int(ctl[12].item())
-            LAST_STATS.light_heavy = (int(ctl[14].item()), int(ctl[15].item()))
-            LAST_STATS.dense_tiles = int(ctl[18].item())
-            c_h = fctl[:24].tolist()
-            LAST_STATS.hard_entries = (int(c_h[5]), int(c_h[7]))
-            LAST_STATS.finish_single_left = int(c_h[8])
+            c_d = ctl[CTL_DEFER:CTL_DEFER + _native.DEFER_CTL_WORDS].tolist()
+            LAST_STATS.deferred_chunks = int(c_d[_native.DEFER_CTL_COUNT])
+            LAST_STATS.light_heavy = (int(c_d[_native.DEFER_CTL_LIGHT]), int(c_d[_native.DEFER_CTL_HEAVY]))
+            LAST_STATS.dense_tiles = int(c_d[_native.DEFER_CTL_TILE_COUNT])
+            c_h = fctl[:_native.FINISH_CTL_QUEUES].tolist()
+            LAST_STATS.hard_entries = (int(c_h[_native.FINISH_CTL_TOP_HARD_LEN]), int(c_h[_native.FINISH_CTL_REST_HARD_LEN]))
+            LAST_STATS.finish_single_left = int(c_h[_native.FINISH_CTL_SINGLE_LEFT])
         out_face = torch.empty(n_slots if face_slots is not None else (S, F), dtype=torch.float32, device=dev)
         with _span(timer, "face_max"):
             _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), n_slots, _native.ptr(out_face), st),

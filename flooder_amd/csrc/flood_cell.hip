@@ -1613,12 +1613,11 @@ s_pts.get4(j, x);
 
 template <int DIM>
 struct CellOp {
-  static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, float* plane_tab,
-                 const float* weights, int k1, int R, int64_t ns, float alpha, int32_t* queue,
-                 uint32_t* out, int32_t* flag_list, int32_t* flag_count, unsigned long long* stats,
-                 FaceAcc acc, DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, bool planes_ready,
-                 hipStream_t st) {
+  static int run(const flooder_fused_sweep_t& a, const Levels& lv, FaceAcc acc, DeferList dl, DensGrid dg, hipStream_t st) {
     if constexpr (DIM == 2 || DIM == 3) {
+      const int R = a.R;
+      const int64_t ns = a.n_simplices;
+      int32_t* const queue = a.cell_queue + FLOODER_CELL_QUEUE_RUNS;
       if (!g_cell_density_grid) dg = DensGrid{};
       dg.min_count = g_cell_density_grid;
       dg.one_pass = g_cell_one_pass;
@@ -1626,9 +1625,9 @@ struct CellOp {
       // persistent blocks of 4 independent waves: 3 per CU fit, but a short queue is swept faster by fewer
       // waves (its longest chunks then share their SIMD with fewer others): about 48 chunks per block,
       // measured on 1/4 and 1/8 shares of cfg 2
-      if (!planes_ready)
-        hipLaunchKernelGGL((simplex_planes_kernel<DIM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, verts, k1, ns,
-                           plane_tab);
+      if (!a.planes_ready)
+        hipLaunchKernelGGL((simplex_planes_kernel<DIM>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, a.verts, a.k1, ns,
+                           a.plane_scratch);
       constexpr int CHUNK = 64 * SPL_CHUNK;
       const int64_t n_chunks = ns * ((R + CHUNK - 1) / CHUNK);
       int64_t want = n_chunks / (g_cell_chunks_per_block > 0 ? g_cell_chunks_per_block : 48);
@@ -1654,9 +1653,9 @@ struct CellOp {
       // 0.4 %; option "cell_chunk_major" 2: always)
       dl.chunk_major = g_cell_chunk_major == 2 ? 2 : ((g_cell_chunk_major && n_chunks > ns) ? 1 : 0);
       dl.drop = g_cell_drop;
-      CellParams cp{pts, nodes, lv, verts, plane_tab, weights, k1, R, ns, alpha, g_cell_exh_dense, g_cell_exh_sparse,
-                    brute_max, g_cell_tries, g_cell_exh_tries, g_cell_retry_pct, g_cell_retry_keep, queue, out, flag_list,
-                    flag_count, stats, acc, dl, dg, 0};
+      CellParams cp{a.pts_sorted, a.nodes, lv, a.verts, a.plane_scratch, a.weights, a.k1, R, ns, a.alpha, g_cell_exh_dense,
+                    g_cell_exh_sparse, brute_max, g_cell_tries, g_cell_exh_tries, g_cell_retry_pct, g_cell_retry_keep, queue,
+                    a.d2_scratch, a.flag_list, a.flag_count, reinterpret_cast<unsigned long long*>(a.cell_stats), acc, dl, dg, 0};
       // blocks of consecutive items per XCD-local queue shard (flood_common.hpp): about a simplex and a half of chunks,
       // two simplices of runs of four
       const int qb = g_cell_queue_block;
@@ -1671,12 +1670,12 @@ struct CellOp {
         // (split: every simplex is on the heavy list of a short queue - the split kernel was told - and the chunk
         // launch takes them heaviest first)
         if (runs_launch) FLOODER_CELL_LAUNCH(true, SPL_CHUNK, queue);
-        FLOODER_CELL_LAUNCH(false, SPL_CHUNK, queue2);
+        FLOODER_CELL_LAUNCH(false, SPL_CHUNK, a.cell_queue + FLOODER_CELL_QUEUE_CHUNKS);
       } else {
         FLOODER_CELL_LAUNCH(false, SPL_CHUNK, queue);
       }
       // ... and the tiles of the chunks whose neighbourhood overflowed the stage, one sample per lane
-      if (dl.tile_list) FLOODER_CELL_LAUNCH(false, 1, queue3);
+      if (dl.tile_list) FLOODER_CELL_LAUNCH(false, 1, a.cell_queue + FLOODER_CELL_QUEUE_TILES);
 #undef FLOODER_CELL_LAUNCH
       return check_launch("cell_sweep");
     } else {
@@ -1944,87 +1943,78 @@ __global__ __launch_bounds__(256) void density_leaves_kernel(const float* __rest
   atomicAdd(&grid[fine], (int)(left < LEAF ? left : LEAF));
 }
 
-int sweep_cell_entry(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
-                     float* plane_tab, const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
-                     uint32_t* out_d2, int32_t* flag_list, int32_t* flag_count, uint64_t* stats, FaceAcc acc,
-                     DeferList dl, int32_t* queue2, int32_t* queue3, DensGrid dg, bool planes_ready, void* stream,
-                     const char* who) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !plane_tab || !weights || !queue || !out_d2 || !flag_list || !flag_count ||
-      n_pts < 1 || k1 < 1 || k1 > FLOODER_MAX_VERTS || R < 0 || !(alpha > 0.f))
+// What the fused and the unfused cell sweep share: the checks of the cloud and the lattice, then the launches.  `a`: the
+// block of the fused sweep (the unfused entry fills the fields it has: d2_scratch is its out_d2).
+int sweep_cell_entry(const flooder_fused_sweep_t& a, FaceAcc acc, DeferList dl, const char* who, void* stream) {
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.plane_scratch || !a.weights || !a.cell_queue || !a.d2_scratch ||
+      !a.flag_list || !a.flag_count || a.n_pts < 1 || a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS || a.R < 0 || !(a.alpha > 0.f))
     return fail(FLOODER_E_ARG, who);
-  if (dim != 2 && dim != 3) return fail(FLOODER_E_ARG, "cell sweep: only dim 2 and 3");
-  if (n_simplices * (int64_t)((R + 63) / 64) > 0x7fffffffLL)
+  if (a.dim != 2 && a.dim != 3) return fail(FLOODER_E_ARG, "cell sweep: only dim 2 and 3");
+  if (a.n_simplices * (int64_t)((a.R + 63) / 64) > 0x7fffffffLL)
     return fail(FLOODER_E_ARG, "cell sweep: too many (simplex, tile) pairs");
-  const Levels lv = make_levels(n_pts);
+  const Levels lv = make_levels(a.n_pts);
   // the kernel addresses rows and node boxes with 32-bit byte offsets
-  if ((n_pts + FLOODER_BVH_LEAF) * (int64_t)(padded_dim(dim) * sizeof(float)) >= (1LL << 32) ||
-      total_nodes(lv) * (int64_t)(2 * padded_dim(dim) * sizeof(float)) >= (1LL << 32))
+  if ((a.n_pts + FLOODER_BVH_LEAF) * (int64_t)(padded_dim(a.dim) * sizeof(float)) >= (1LL << 32) ||
+      total_nodes(lv) * (int64_t)(2 * padded_dim(a.dim) * sizeof(float)) >= (1LL << 32))
     return fail(FLOODER_E_ARG, "cell sweep: cloud too large for the cell sweep (use the tree sweep)");
-  return dispatch_dim<CellOp>(dim, pts_sorted, nodes, lv, verts, plane_tab, weights, k1, R, n_simplices, alpha, queue,
-                              out_d2, flag_list, flag_count, reinterpret_cast<unsigned long long*>(stats), acc,
-                              dl, queue2, queue3, dg, planes_ready, (hipStream_t)stream);
+  DensGrid dg;
+  if (a.density_grid && a.cloud_box) { dg.grid = a.density_grid; dg.box = a.cloud_box; }
+  return dispatch_dim<CellOp>(a.dim, a, lv, acc, dl, dg, (hipStream_t)stream);
 }
 
 }  // namespace
 
-// flooder_sweep_cell_faces_f32 plus `planes_ready` (flood_common.hpp; the parameter-block form passes its field)
-int flooder::sweep_cell_faces(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
-                              const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
-                              uint32_t* d2_scratch, const uint32_t* memb, int n_faces, uint32_t* face_bits,
-                              const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count, uint32_t* flag_key,
-                              int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count, int32_t* defer_list,
-                              float* defer_c, int32_t* defer_ctl, const float* simplex_weight, int32_t* light_list,
-                              int32_t* heavy_list, float* plane_scratch, const int32_t* density_grid,
-                              const float* cloud_box, uint64_t* stats, bool planes_ready, void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  DensGrid dg;
-  if (density_grid && cloud_box) { dg.grid = density_grid; dg.box = cloud_box; }
-  if (!memb || !face_bits || n_faces < 1 || n_faces > 32 || (top && (!top_list || !top_count)) ||
-      (defer_list && (!defer_c || !defer_ctl)) || (simplex_weight && (!defer_list || !light_list || !heavy_list)) ||
-      (flag_key && (!flag_hist || !top)) || n_simplices > 0x7fffffffLL)
+// The fused cell sweep on its parameter block (flood_common.hpp)
+int flooder::fused_cell(const flooder_fused_sweep_t& a, void* stream) {
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.memb || !a.face_bits || a.n_faces < 1 || a.n_faces > 32 || (a.top && (!a.top_list || !a.top_count)) ||
+      (a.defer_list && (!a.defer_c || !a.defer_ctl)) ||
+      (a.simplex_weight && (!a.defer_list || !a.light_list || !a.heavy_list)) || (a.flag_key && (!a.flag_hist || !a.top)) ||
+      a.n_simplices > 0x7fffffffLL)
     return fail(FLOODER_E_ARG, "flooder_sweep_cell_faces_f32: bad argument");
-  if (!simplex_weight) light_list = heavy_list = nullptr;
-  if (simplex_weight) {  // split the simplices (order kept) into the light and the heavy list
-    const bool long_queue = n_simplices * (int64_t)((R + 255) / 256) >= (int64_t)g_cell_super_min_chunks;
+  const float* const weight = a.simplex_weight;
+  int32_t* const light = weight ? a.light_list : nullptr;
+  int32_t* const heavy = weight ? a.heavy_list : nullptr;
+  int32_t* const split = weight ? a.defer_ctl + FLOODER_DEFER_CTL_LIGHT : nullptr;   // light, heavy, done
+  const int n = (int)a.n_simplices;
+  const hipStream_t st = (hipStream_t)stream;
+  if (weight) {  // split the simplices (order kept) into the light and the heavy list
+    const bool long_queue = a.n_simplices * (int64_t)((a.R + 255) / 256) >= (int64_t)g_cell_super_min_chunks;
     // (more simplices than the one-launch form stages in LDS - its runs would be read from memory, a chain of cache
     // misses: 50 us for cfg 5's 25 217 - take the pair; option 2: the pair always, for A/B runs and the tests)
-    if (long_queue && (g_cell_split_launches == 2 || n_simplices > 7680)) {
-      hipLaunchKernelGGL(split_simplices_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, simplex_weight,
-                         (int)n_simplices, (float)g_cell_super_weight, (float)g_cell_super_sparse, light_list, heavy_list,
-                         defer_ctl + 2);
+    if (long_queue && (g_cell_split_launches == 2 || a.n_simplices > 7680)) {
+      hipLaunchKernelGGL(split_simplices_kernel, dim3(1), dim3(1024), 0, st, weight, n, (float)g_cell_super_weight,
+                         (float)g_cell_super_sparse, light, heavy, split);
       // ... and the heavy list heaviest first: its densest simplices hold the chunks that one wave evaluates
       // exhaustively for 150 us and more, and the last of them to start was the tail of the chunk launch
       if (g_cell_weight_classes)
-        hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, (hipStream_t)stream, simplex_weight,
-                           (int)n_simplices, (float)g_cell_super_weight, (float)g_cell_super_sparse, 2, 1, light_list,
-                           heavy_list, defer_ctl + 2);
+        hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, st, weight, n,
+                           (float)g_cell_super_weight, (float)g_cell_super_sparse, 2, 1, light, heavy, split);
     } else if (long_queue) {
       // light list in the given order + heavy list heaviest first (its densest simplices hold the chunks that one wave
       // evaluates exhaustively for 150 us and more: started last they were the tail of the chunk launch) in ONE launch
-      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS_LONG>, dim3(1), dim3(SPLIT_THREADS_LONG), 0, (hipStream_t)stream, simplex_weight,
-                         (int)n_simplices, (float)g_cell_super_weight, (float)g_cell_super_sparse,
-                         (g_cell_weight_classes ? 2 : 0) | 1 | 4, 0, light_list, heavy_list, defer_ctl + 2);
+      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS_LONG>, dim3(1), dim3(SPLIT_THREADS_LONG), 0, st, weight, n,
+                         (float)g_cell_super_weight, (float)g_cell_super_sparse, (g_cell_weight_classes ? 2 : 0) | 1 | 4, 0,
+                         light, heavy, split);
     } else {
-      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, (hipStream_t)stream, simplex_weight,
-                         (int)n_simplices, (float)g_cell_super_weight, (float)g_cell_super_sparse,
-                         g_cell_weight_classes ? 2 : 0, 0, light_list, heavy_list, defer_ctl + 2);
+      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, st, weight, n,
+                         (float)g_cell_super_weight, (float)g_cell_super_sparse, g_cell_weight_classes ? 2 : 0, 0, light,
+                         heavy, split);
     }
   }
-  DeferList dl{defer_list, defer_c, defer_list ? defer_ctl : nullptr, light_list, heavy_list,
-               light_list ? defer_ctl + 2 : nullptr, g_cell_super_n0};
-  if (defer_list) {  // the tile list lives behind the chunk list (the caller sizes both buffers for 5 x S x chunks)
-    const int64_t n_chunk_slots = n_simplices * (int64_t)((R + 255) / 256);
-    dl.tile_list = defer_list + n_chunk_slots;
-    dl.tile_c = defer_c + n_chunk_slots;
-    dl.tile_count = defer_ctl + 6;
+  DeferList dl{a.defer_list, a.defer_c, a.defer_list ? a.defer_ctl + FLOODER_DEFER_CTL_COUNT : nullptr, light, heavy,
+               split, g_cell_super_n0};
+  if (a.defer_list) {  // the tile list lives behind the chunk list (the caller sizes both buffers for 5 x S x chunks)
+    const int64_t n_chunk_slots = a.n_simplices * (int64_t)((a.R + 255) / 256);
+    dl.tile_list = a.defer_list + n_chunk_slots;
+    dl.tile_c = a.defer_c + n_chunk_slots;
+    dl.tile_count = a.defer_ctl + FLOODER_DEFER_CTL_TILE_COUNT;
   }
-  return sweep_cell_entry(pts_sorted, n_pts, dim, nodes, verts, plane_scratch, weights, k1, R, n_simplices, alpha, queue,
-                          d2_scratch, flag_list, flag_count, stats,
-                          FaceAcc{memb, face_bits, n_faces, reinterpret_cast<unsigned long long*>(top), top_list,
-                                  top_count, face_slot, flag_key, flag_hist},
-                          dl, queue + FLOODER_QUEUE_WORDS, queue + 2 * FLOODER_QUEUE_WORDS, dg, planes_ready,
-                          stream, "flooder_sweep_cell_faces_f32: bad argument");
+  return sweep_cell_entry(a,
+                          FaceAcc{a.memb, a.face_bits, a.n_faces, reinterpret_cast<unsigned long long*>(a.top), a.top_list,
+                                  a.top_count, a.face_slot, a.flag_key, a.flag_hist},
+                          dl, "flooder_sweep_cell_faces_f32: bad argument", stream);
 }
 
 extern "C" {
@@ -2034,14 +2024,17 @@ int flooder_sweep_cell_f32(const float* pts_sorted, int64_t n_pts, int dim, cons
                            float alpha, int32_t* queue, uint32_t* out_d2, int32_t* flag_list, int32_t* flag_count,
                            float* plane_scratch, const int32_t* density_grid, const float* cloud_box, uint64_t* stats,
                            void* stream) {
-  DensGrid dg;
-  if (density_grid && cloud_box) { dg.grid = density_grid; dg.box = cloud_box; }
-  return sweep_cell_entry(pts_sorted, n_pts, dim, nodes, verts, plane_scratch, weights, k1, R, n_simplices, alpha, queue, out_d2,
-                          flag_list, flag_count, stats, FaceAcc{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr},
-                          DeferList{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr, dg, false,
-                          stream, "flooder_sweep_cell_f32: bad argument");
+  flooder_fused_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.alpha = alpha; a.cell_queue = queue; a.d2_scratch = out_d2;
+  a.flag_list = flag_list; a.flag_count = flag_count; a.plane_scratch = plane_scratch; a.density_grid = density_grid;
+  a.cloud_box = cloud_box; a.cell_stats = stats;
+  return sweep_cell_entry(a, FaceAcc{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr},
+                          DeferList{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0},
+                          "flooder_sweep_cell_f32: bad argument", stream);
 }
 
+// (planes_ready never set: include/flooder_hip.h)
 int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                                  const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
                                  float alpha, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb,
@@ -2051,10 +2044,15 @@ int flooder_sweep_cell_faces_f32(const float* pts_sorted, int64_t n_pts, int dim
                                  float* defer_c, int32_t* defer_ctl, const float* simplex_weight,
                                  int32_t* light_list, int32_t* heavy_list, float* plane_scratch,
                                  const int32_t* density_grid, const float* cloud_box, uint64_t* stats, void* stream) {
-  return sweep_cell_faces(pts_sorted, n_pts, dim, nodes, verts, weights, k1, R, n_simplices, alpha, queue, d2_scratch, memb,
-                          n_faces, face_bits, face_slot, flag_list, flag_count, flag_key, flag_hist, top, top_list, top_count,
-                          defer_list, defer_c, defer_ctl, simplex_weight, light_list, heavy_list, plane_scratch,
-                          density_grid, cloud_box, stats, false, stream);
+  flooder_fused_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.alpha = alpha; a.cell_queue = queue; a.d2_scratch = d2_scratch;
+  a.memb = memb; a.n_faces = n_faces; a.face_bits = face_bits; a.face_slot = face_slot; a.flag_list = flag_list;
+  a.flag_count = flag_count; a.flag_key = flag_key; a.flag_hist = flag_hist; a.top = top; a.top_list = top_list;
+  a.top_count = top_count; a.defer_list = defer_list; a.defer_c = defer_c; a.defer_ctl = defer_ctl;
+  a.simplex_weight = const_cast<float*>(simplex_weight); a.light_list = light_list; a.heavy_list = heavy_list;
+  a.plane_scratch = plane_scratch; a.density_grid = density_grid; a.cloud_box = cloud_box; a.cell_stats = stats;
+  return fused_cell(a, stream);
 }
 
 

@@ -350,24 +350,15 @@ inline void launch_cloud_kind(int dim, int32_t* grid, hipStream_t st) {   // gri
   else if (dim == 3) hipLaunchKernelGGL((cloud_kind_kernel<3>), dim3(16), dim3(256), 0, st, grid, grid + 64 * 64 * 64);
 }
 
-// flood_wit.hip: flooder_sweep_witness_f32 with the index's density grid and the run table of the witness plan (what
-// flooder_fused_witness calls; runs NULL / n_runs 0: no run test).  planes_ready: the caller vouches that plane_scratch
-// holds the plane rows of exactly these verts, written earlier on this stream (flooder_fused_sweep_t) - no plane launch
-int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
-                  const float* weights, int k1, int R, int64_t n_simplices, const int32_t* coarse_rows, int n_coarse,
-                  const uint32_t* parents, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb, int n_faces,
-                  uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count,
-                  uint32_t* flag_key, int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count,
-                  float* simplex_weight, int32_t* item_list, float* plane_scratch, uint64_t* stats,
-                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, bool planes_ready,
-                  void* stream);
-// flood_cell.hip: flooder_sweep_cell_faces_f32 with the same flag (what flooder_fused_cell calls)
-int sweep_cell_faces(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
-                     const float* weights, int k1, int R, int64_t n_simplices, float alpha, int32_t* queue,
-                     uint32_t* d2_scratch, const uint32_t* memb, int n_faces, uint32_t* face_bits, const int32_t* face_slot,
-                     int32_t* flag_list, int32_t* flag_count, uint32_t* flag_key, int32_t* flag_hist, uint64_t* top,
-                     int32_t* top_list, int32_t* top_count, int32_t* defer_list, float* defer_c, int32_t* defer_ctl,
-                     const float* simplex_weight, int32_t* light_list, int32_t* heavy_list, float* plane_scratch,
-                     const int32_t* density_grid, const float* cloud_box, uint64_t* stats, bool planes_ready, void* stream);
+// The launches that have a parameter block (include/flooder_hip.h), each ONE function on its block: it makes the checks
+// and fills the kernel's own structs from the named fields.  flood_params.hip calls them with the caller's block, the
+// positional exports with a zeroed block they have filled by name (so: no density grid, no run table and planes_ready 0
+// from the positional witness entry, planes_ready 0 from the positional cell entry).
+int fused_witness(const flooder_fused_sweep_t& a, void* stream);   // flood_wit.hip
+int fused_cell(const flooder_fused_sweep_t& a, void* stream);      // flood_cell.hip
+int fused_finish(const flooder_fused_sweep_t& a, void* stream);    // flood_finish.hip
+enum class SortedMode { minima, shard, faces };                    // out_d2 of all tiles / of one rank's tiles / face maxima
+int sorted_sweep(const flooder_sorted_sweep_t& a, SortedMode mode, void* stream);   // flood_sorted.hip
+int fps_batched(const flooder_fps_batched_t& a, void* stream);     // flood_fps2.hip
 
 }  // namespace flooder

@@ -88,7 +88,6 @@ constexpr int FINISH_SINGLE_BATCHES = FLOODER_FINISH_SINGLE_BATCHES;
 #define FLOODER_FINISH_SINGLE_WAVES 4
 #endif
 constexpr int SINGLE_WAVES = FLOODER_FINISH_SINGLE_WAVES;  // waves per workgroup (independent of each other)
-constexpr int SINGLE_LEFT_WORD = 8;
 // The budget follows option "finish_budget_min" - what a wave of a short list may spend alone before the stronger
 // machinery takes over - in proportion: FINISH_SINGLE_BATCHES batches at the option's default of 64 leaves, at least one.
 inline int single_batches() {
@@ -897,32 +896,31 @@ __global__ void face_values_kernel(const uint32_t* __restrict__ bits, int64_t n,
 
 template <int DIM>
 struct FinishOp {
-  static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, const float* weights,
-                 int k1, int R, int64_t ns, const int32_t* flag_list, const int32_t* flag_count,
-                 const uint32_t* flag_key, int32_t* flag_hist, int32_t* flag_sorted, int32_t* ctl,
-                 uint32_t* d2, FaceAcc acc, unsigned long long* top, int32_t* top_list, int probed,
-                 unsigned long long* hard, int hard_cap, unsigned long long* stats, hipStream_t st) {
+  static int run(const flooder_fused_sweep_t& a, const Levels& lv, FaceAcc acc, hipStream_t st) {
     // (the finish follows the cell sweep, which exists in 2D and 3D: the other dimensions are not instantiated -
     // they were 91 KB of LDS and spilled registers for kernels nobody launches)
     if constexpr (DIM != 2 && DIM != 3) {
       return fail(FLOODER_E_ARG, "flooder_finish_faces_f32: only dim 2 and 3");
     } else {
+    int32_t* const ctl = a.finish_ctl;   // its words: FLOODER_FINISH_CTL_* (include/flooder_hip.h)
+    const int hard_cap = a.hard_cap;
+    unsigned long long* top = reinterpret_cast<unsigned long long*>(a.top);
+    unsigned long long* hard = reinterpret_cast<unsigned long long*>(a.hard_scratch);
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(a.finish_stats);
     const int grid = g_bvh_grid;
     const bool wide = g_finish_wide_points > 0 && lv.count[0] * (int64_t)FLOODER_BVH_LEAF >= (int64_t)g_finish_wide_points;
-    // ctl[0..2]: work-queue heads of the three passes, ctl[3]: simplices with a top tile (filled by the probe -
-    // the cell sweep's when `probed`, else pass 0 here); the hard-entry launches' words: below
     const bool hard_on = hard != nullptr && hard_cap > 0 && g_finish_budget > 0;
-    const bool ordered = flag_key != nullptr && flag_hist != nullptr && flag_sorted != nullptr && g_finish_order != 0;
+    const bool ordered = a.flag_key != nullptr && a.flag_hist != nullptr && a.flag_sorted != nullptr && g_finish_order != 0;
     if (ordered)
-      hipLaunchKernelGGL(order_flags_kernel, dim3(256), dim3(256), 0, st, flag_list, flag_key, flag_count, flag_hist,
-                         flag_hist + KEY_BUCKETS, flag_sorted);
+      hipLaunchKernelGGL(order_flags_kernel, dim3(256), dim3(256), 0, st, a.flag_list, a.flag_key, a.flag_count, a.flag_hist,
+                         a.flag_hist + KEY_BUCKETS, a.flag_sorted);
     // a short list: a wave per sample first (finish_single_kernel); what it leaves over, the passes below pick up.
     // (option "bvh_subs" 1 - tiles are not split over waves - turns it off)
     const bool single = g_bvh_subs > 1;
     if (single)
       hipLaunchKernelGGL((finish_single_kernel<DIM>), dim3(FINISH_SINGLE_TILES * 64 / SINGLE_WAVES), dim3(64 * SINGLE_WAVES),
-                         0, st, pts, nodes, lv, verts, weights, k1, R, flag_list, flag_count, g_finish_refresh,
-                         single_batches(), d2, acc, ctl + SINGLE_LEFT_WORD, stats);
+                         0, st, a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.flag_list, a.flag_count,
+                         g_finish_refresh, single_batches(), a.d2_scratch, acc, ctl + FLOODER_FINISH_CTL_SINGLE_LEFT, stats);
     const int64_t words = (int64_t)hard_cap * 2;  // entries, masks (u64)
     auto list = [&](int which, bool in, int32_t* cnt, HardLists& hl) {
       unsigned long long* base = hard + which * words;
@@ -936,57 +934,61 @@ struct FinishOp {
         hl.cnt_out = cnt;
       }
     };
+    // (TOP_COUNT: simplices with a top tile, filled by the probe - the cell sweep's when `probed`, else pass 0 here)
     auto launch = [&](int mode, int32_t* queue, const HardLists& hl) {
-      if (mode == 3)  // one workgroup of 16 waves per hard tile, one workgroup per CU
-        hipLaunchKernelGGL((finish_faces_kernel<DIM, true>), dim3(g_bvh_grid / 4), dim3(64 * TEAM_WAVES), 0, st, pts,
-                           nodes, lv, verts, weights, k1, R, ns, flag_list, ordered ? flag_sorted : nullptr, flag_count,
-                           mode, g_bvh_subs, g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f,
-                           g_finish_refresh, queue, d2, acc, top, top_list, ctl + 3, hl, stats);
-      else if (wide)   // (deep tree: eight waves per workgroup, three workgroups per CU)
-        hipLaunchKernelGGL((finish_faces_kernel<DIM, false, 8>), dim3(grid * 3 / 4), dim3(512), 0, st, pts, nodes, lv, verts,
-                           weights, k1, R, ns, flag_list, ordered ? flag_sorted : nullptr, flag_count, mode, g_bvh_subs,
-                           g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f, g_finish_refresh,
-                           queue, d2, acc, top, top_list, ctl + 3, hl, stats);
-      else
-        hipLaunchKernelGGL((finish_faces_kernel<DIM, false>), dim3(grid), dim3(256), 0, st, pts, nodes, lv, verts,
-                           weights, k1, R, ns, flag_list, ordered ? flag_sorted : nullptr, flag_count, mode, g_bvh_subs,
-                           g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f, g_finish_refresh,
-                           queue, d2, acc, top, top_list, ctl + 3, hl, stats);
+      auto go = [&](auto kernel, int blocks, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, st, a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R,
+                           a.n_simplices, a.flag_list, ordered ? a.flag_sorted : nullptr, a.flag_count, mode, g_bvh_subs,
+                           g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f, g_finish_refresh, queue,
+                           a.d2_scratch, acc, top, a.top_list, ctl + FLOODER_FINISH_CTL_TOP_COUNT, hl, stats);
+      };
+      if (mode == 3) go(finish_faces_kernel<DIM, true>, g_bvh_grid / 4, 64 * TEAM_WAVES);   // a workgroup of 16 waves per hard tile, one per CU
+      else if (wide) go(finish_faces_kernel<DIM, false, 8>, grid * 3 / 4, 512);   // (deep tree: eight waves per workgroup, three per CU)
+      else go(finish_faces_kernel<DIM, false>, grid, 256);
     };
     HardLists none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hard_cap, 0};
-    none.single_left = single ? ctl + SINGLE_LEFT_WORD : nullptr;
+    none.single_left = single ? ctl + FLOODER_FINISH_CTL_SINGLE_LEFT : nullptr;
     // (the per-wave passes pop from sharded heads behind the 24 control words; the team passes keep one word)
-    int32_t* q0 = ctl + 24;
-    int32_t* q1 = ctl + 24 + FLOODER_QUEUE_WORDS;
-    int32_t* q2 = ctl + 24 + 2 * FLOODER_QUEUE_WORDS;
-    if (!probed) launch(0, q0, none);
+    int32_t* q0 = ctl + FLOODER_FINISH_CTL_QUEUES;
+    int32_t* q1 = q0 + FLOODER_QUEUE_WORDS;
+    int32_t* q2 = q0 + 2 * FLOODER_QUEUE_WORDS;
+    if (!a.probed) launch(0, q0, none);
     if (!hard_on) {
       if (g_finish_top) launch(1, q1, none);
       launch(2, q2, none);
       return check_launch("finish_faces");
     }
-    // ctl: [0..2] queue heads of the probe / top / rest passes, [3] simplices with a top tile, [4], [5] queue head
-    // and list length of the top pass's hard entries, [6], [7] those of the rest pass's, [8] samples the short-list
-    // kernel left over
-    HardLists a = none, b = none, c = none, d = none;
-    a.budget = c.budget = g_finish_budget;
-    a.budget_min = c.budget_min = g_finish_budget_min;
+    HardLists t_out = none, t_in = none, r_out = none, r_in = none;
+    t_out.budget = r_out.budget = g_finish_budget;
+    t_out.budget_min = r_out.budget_min = g_finish_budget_min;
     if (g_finish_top) {
-      list(0, false, ctl + 5, a);  // top pass: hard entries -> list 0
-      launch(1, q1, a);
-      list(0, true, ctl + 5, b);   // ... one workgroup each (one sample per entry: one round)
-      launch(3, ctl + 4, b);
+      list(0, false, ctl + FLOODER_FINISH_CTL_TOP_HARD_LEN, t_out);  // top pass: hard entries -> list 0
+      launch(1, q1, t_out);
+      list(0, true, ctl + FLOODER_FINISH_CTL_TOP_HARD_LEN, t_in);    // ... one workgroup each (one sample per entry: one round)
+      launch(3, ctl + FLOODER_FINISH_CTL_TOP_HARD_HEAD, t_in);
     }
-    list(1, false, ctl + 7, c);  // the other samples: hard tiles -> list 1
-    launch(2, q2, c);
-    list(1, true, ctl + 7, d);   // ... one workgroup each, all their rounds
-    launch(3, ctl + 6, d);
+    list(1, false, ctl + FLOODER_FINISH_CTL_REST_HARD_LEN, r_out);  // the other samples: hard tiles -> list 1
+    launch(2, q2, r_out);
+    list(1, true, ctl + FLOODER_FINISH_CTL_REST_HARD_LEN, r_in);    // ... one workgroup each, all their rounds
+    launch(3, ctl + FLOODER_FINISH_CTL_REST_HARD_HEAD, r_in);
     return check_launch("finish_faces");
     }
   }
 };
 
 }  // namespace
+
+// The finish on its parameter block (flood_common.hpp)
+int flooder::fused_finish(const flooder_fused_sweep_t& a, void* stream) {
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.flag_list || !a.flag_count || !a.finish_ctl || !a.top ||
+      !a.top_list || !a.d2_scratch || !a.memb || !a.face_bits || a.n_pts < 1 || a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS ||
+      a.R < 1 || a.n_faces < 1 || a.n_faces > 32 || a.hard_cap < 0)
+    return fail(FLOODER_E_ARG, "flooder_finish_faces_f32: bad argument");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<FinishOp>(a.dim, a, lv, FaceAcc{a.memb, a.face_bits, a.n_faces, nullptr, nullptr, nullptr, a.face_slot},
+                                (hipStream_t)stream);
+}
 
 extern "C" {
 
@@ -1000,17 +1002,14 @@ int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, co
                              uint64_t* top, int32_t* top_list, int probed, uint32_t* d2_scratch,
                              const uint32_t* memb, int n_faces, uint32_t* face_bits, const int32_t* face_slot,
                              uint64_t* hard_scratch, int hard_cap, uint64_t* stats, void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !weights || !flag_list || !flag_count || !ctl || !top || !top_list || !d2_scratch ||
-      !memb || !face_bits || n_pts < 1 || k1 < 1 || k1 > FLOODER_MAX_VERTS || R < 1 || n_faces < 1 || n_faces > 32 ||
-      hard_cap < 0)
-    return fail(FLOODER_E_ARG, "flooder_finish_faces_f32: bad argument");
-  const Levels lv = make_levels(n_pts);
-  return dispatch_dim<FinishOp>(dim, pts_sorted, nodes, lv, verts, weights, k1, R, n_simplices, flag_list,
-                                flag_count, flag_key, flag_hist, flag_sorted, ctl, d2_scratch, FaceAcc{memb, face_bits, n_faces, nullptr, nullptr, nullptr, face_slot},
-                                reinterpret_cast<unsigned long long*>(top), top_list, probed,
-                                reinterpret_cast<unsigned long long*>(hard_scratch), hard_cap,
-                                reinterpret_cast<unsigned long long*>(stats), (hipStream_t)stream);
+  flooder_fused_sweep_t a{};   // (the block's list pointers are not const: the sweeps write what the finish reads)
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.flag_list = const_cast<int32_t*>(flag_list);
+  a.flag_count = const_cast<int32_t*>(flag_count); a.flag_key = const_cast<uint32_t*>(flag_key); a.flag_hist = flag_hist;
+  a.flag_sorted = flag_sorted; a.finish_ctl = ctl; a.top = top; a.top_list = top_list; a.probed = probed;
+  a.d2_scratch = d2_scratch; a.memb = memb; a.n_faces = n_faces; a.face_bits = face_bits; a.face_slot = face_slot;
+  a.hard_scratch = hard_scratch; a.hard_cap = hard_cap; a.finish_stats = stats;
+  return fused_finish(a, stream);
 }
 
 int flooder_face_values_f32(const uint32_t* face_bits, int64_t n, float* out_face, void* stream) {

@@ -709,9 +709,14 @@ int64_t batched_blocks(int64_t n) {
 inline int batched_rpl(int64_t n) { return g_fps_rpl ? g_fps_rpl : (n >= (4 << 20) ? 4 : 1); }
 
 template <int DIM, int RPL>
-int run_batched(const float* pts, int64_t n, int ld, const float* pts_sorted, const int32_t* order, int n_lms,
-                int64_t start, int k0, int64_t* out_idx, float* minsq, float* box, u64* keys, float* bcoord, u64* best,
-                uint32_t* rec, int32_t* ctr, int32_t* launches_out, hipStream_t st) {
+int run_batched(const flooder_fps_batched_t& a, int k0, hipStream_t st) {
+  const float *pts = a.pts, *pts_sorted = a.pts_sorted;   // (the names the launches below use)
+  const int32_t* order = a.order;
+  const int64_t n = a.n_pts, start = a.start;
+  const int ld = a.ld, n_lms = a.n_lms;
+  float *minsq = a.minsq, *box = a.bucket_box, *bcoord = a.bucket_coord;
+  u64 *keys = reinterpret_cast<u64*>(a.bucket_keys), *best = reinterpret_cast<u64*>(a.work_best);
+  int64_t* out_idx = a.out_idx; uint32_t* rec = a.work_rec; int32_t *ctr = a.work_ctr, *launches_out = a.launches_out;
   const int64_t n_buckets = (n + RPL * 64 - 1) / (RPL * 64);
   const unsigned grid = (unsigned)batched_blocks<RPL>(n);
   if (grid > 64 * NREC) return fail(FLOODER_E_ARG, "flooder_fps_batched_f32: cloud too large (use flooder_fps_indexed_f32)");
@@ -827,25 +832,28 @@ int run_batched(const float* pts, int64_t n, int ld, const float* pts_sorted, co
 
 template <int DIM>
 struct FpsBatchedOp {
-  static int run(const float* pts, int64_t n, int ld, const float* pts_sorted, const int32_t* order, int n_lms,
-                 int64_t start, int64_t* out_idx, float* minsq, float* box, u64* keys, float* bcoord, u64* best,
-                 uint32_t* rec, int32_t* ctr, int32_t* launches_out, hipStream_t st) {
+  static int run(const flooder_fps_batched_t& a, hipStream_t st) {
     // small clouds: 64-row buckets (more waves to spread a landmark's neighbourhood over) and a late switch (a
     // brute step over an L2-resident cloud costs about as much as a launch); large clouds: 256-row buckets
-    const int rpl = batched_rpl(n);
+    const int rpl = batched_rpl(a.n_pts);
     // (measured: 1 M / 1 k 2.44 ms at 64, 2.46 at 32, 2.52 at 96 and 128, 2.63 at 4; 16 M / 4 k 13.1 ms at 4, 13.2 at 8,
     // 14.3 at 32, 19.7 at 128)
-    int k0 = g_fps_switch ? g_fps_switch : (n >= (4 << 20) ? 8 : 64);
+    int k0 = g_fps_switch ? g_fps_switch : (a.n_pts >= (4 << 20) ? 8 : 64);
     if (k0 < 2) k0 = 2;  // (the start point is applied by a brute-force step)
-    if (rpl == 4)
-      return run_batched<DIM, 4>(pts, n, ld, pts_sorted, order, n_lms, start, k0, out_idx, minsq, box, keys, bcoord, best,
-                                 rec, ctr, launches_out, st);
-    return run_batched<DIM, 1>(pts, n, ld, pts_sorted, order, n_lms, start, k0, out_idx, minsq, box, keys, bcoord, best,
-                               rec, ctr, launches_out, st);
+    return rpl == 4 ? run_batched<DIM, 4>(a, k0, st) : run_batched<DIM, 1>(a, k0, st);
   }
 };
 
 }  // namespace
+
+// The batched landmark selection on its parameter block (flood_common.hpp)
+int flooder::fps_batched(const flooder_fps_batched_t& a, void* stream) {
+  if (!a.pts || !a.pts_sorted || !a.order || !a.out_idx || !a.minsq || !a.bucket_box || !a.bucket_keys || !a.bucket_coord ||
+      !a.work_best || !a.work_rec || !a.work_ctr || a.n_pts < 1 || a.n_lms < 1 || a.n_lms > a.n_pts || a.start < 0 ||
+      a.start >= a.n_pts || a.ld < a.dim || a.dim < 1 || a.dim > FLOODER_MAX_DIM || a.n_pts > 0xfffffffeLL)
+    return fail(FLOODER_E_ARG, "flooder_fps_batched_f32: bad argument");
+  return dispatch_dim<FpsBatchedOp>(a.dim, a, (hipStream_t)stream);
+}
 
 extern "C" {
 
@@ -862,13 +870,12 @@ int flooder_fps_batched_f32(const float* pts, int64_t n_pts, int dim, int ld, co
                             const int32_t* order, int n_lms, int64_t start, int64_t* out_idx, float* minsq,
                             float* bucket_box, uint64_t* bucket_keys, float* bucket_coord, uint64_t* work_best,
                             uint32_t* work_rec, int32_t* work_ctr, int32_t* launches_out, void* stream) {
-  if (!pts || !pts_sorted || !order || !out_idx || !minsq || !bucket_box || !bucket_keys || !bucket_coord || !work_best ||
-      !work_rec || !work_ctr || n_pts < 1 || n_lms < 1 || n_lms > n_pts || start < 0 || start >= n_pts || ld < dim ||
-      dim < 1 || dim > FLOODER_MAX_DIM || n_pts > 0xfffffffeLL)
-    return fail(FLOODER_E_ARG, "flooder_fps_batched_f32: bad argument");
-  return dispatch_dim<FpsBatchedOp>(dim, pts, n_pts, ld, pts_sorted, order, n_lms, start, out_idx, minsq, bucket_box,
-                                    reinterpret_cast<u64*>(bucket_keys), bucket_coord, reinterpret_cast<u64*>(work_best),
-                                    work_rec, work_ctr, launches_out, (hipStream_t)stream);
+  flooder_fps_batched_t a{};
+  a.pts = pts; a.n_pts = n_pts; a.dim = dim; a.ld = ld; a.pts_sorted = pts_sorted; a.order = order; a.n_lms = n_lms;
+  a.start = start; a.out_idx = out_idx; a.minsq = minsq; a.bucket_box = bucket_box; a.bucket_keys = bucket_keys;
+  a.bucket_coord = bucket_coord; a.work_best = work_best; a.work_rec = work_rec; a.work_ctr = work_ctr;
+  a.launches_out = launches_out;
+  return fps_batched(a, stream);
 }
 
 }  // extern "C"

@@ -692,9 +692,7 @@ struct SampleKeysOp {
 template <int DIM>
 struct SweepSortedOp {
   template <int KS, bool FUSED>
-  static int launch(const float* pts, const float* nodes, const Levels& lv, const float* verts, const float* weights,
-                    int k1, int R, int64_t n_samples, const uint32_t* order, int32_t* queue, uint32_t* out,
-                    unsigned long long* stats, SortedFaces sf, TileShard ts, hipStream_t st) {
+  static int launch(const flooder_sorted_sweep_t& a, const Levels& lv, SortedFaces sf, TileShard ts, hipStream_t st) {
     // persistent blocks of 4 independent waves, as many as the registers let a CU hold (asked once per instantiation)
     static int blocks_per_cu = 0;
     if (blocks_per_cu == 0) {
@@ -702,6 +700,7 @@ struct SweepSortedOp {
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sweep_sorted_kernel<DIM, KS, FUSED>, 256, 0) != hipSuccess || nb < 1) nb = 4;
       blocks_per_cu = nb > 8 ? 8 : nb;
     }
+    const int64_t n_samples = a.n_simplices * (int64_t)a.R;
     int64_t n_tiles = (n_samples + 64 * KS - 1) / (64 * KS);
     if (ts.world > 1) {
       n_tiles = n_tiles * (ts.rank + 1) / ts.world - n_tiles * ts.rank / ts.world;
@@ -710,18 +709,16 @@ struct SweepSortedOp {
     // (option "sorted_blocks": fewer resident blocks per CU than fit - a diagnostic for how much of the kernel is latency)
     int64_t grid = (int64_t)(g_sorted_blocks > 0 && g_sorted_blocks < blocks_per_cu ? g_sorted_blocks : blocks_per_cu) * 256;
     if (grid * 4 > n_tiles) grid = (n_tiles + 3) / 4;
-    hipLaunchKernelGGL((sweep_sorted_kernel<DIM, KS, FUSED>), dim3((unsigned)grid), dim3(256), 0, st, pts, nodes, lv, verts,
-                       weights, k1, R, n_samples, order, queue, out, stats, g_bvh_refine_pct,
+    hipLaunchKernelGGL((sweep_sorted_kernel<DIM, KS, FUSED>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, lv,
+                       a.verts, a.weights, a.k1, a.R, n_samples, reinterpret_cast<const uint32_t*>(a.sample_order), a.queue,
+                       FUSED ? nullptr : a.out_d2, reinterpret_cast<unsigned long long*>(a.stats), g_bvh_refine_pct,
                        (float)(g_sorted_batch_pct < 100 ? 100 : g_sorted_batch_pct) * 0.01f, sf, ts);
     return check_launch("sweep_sorted");
   }
-  static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, const float* weights,
-                 int k1, int R, int64_t n_samples, const uint32_t* order, int32_t* queue, uint32_t* out,
-                 unsigned long long* stats, SortedFaces sf, TileShard ts, hipStream_t st) {
-    if (sf.face_bits != nullptr)
-      return launch<1, true>(pts, nodes, lv, verts, weights, k1, R, n_samples, order, queue, out, stats, sf, ts, st);
-    if (g_sorted_ks == 2) return launch<2, false>(pts, nodes, lv, verts, weights, k1, R, n_samples, order, queue, out, stats, sf, ts, st);
-    return launch<1, false>(pts, nodes, lv, verts, weights, k1, R, n_samples, order, queue, out, stats, sf, ts, st);
+  static int run(const flooder_sorted_sweep_t& a, const Levels& lv, SortedFaces sf, TileShard ts, hipStream_t st) {
+    if (sf.face_bits != nullptr) return launch<1, true>(a, lv, sf, ts, st);
+    if (g_sorted_ks == 2) return launch<2, false>(a, lv, sf, ts, st);
+    return launch<1, false>(a, lv, sf, ts, st);
   }
 };
 
@@ -757,50 +754,59 @@ int flooder_sample_keys_late_f32(const float* verts, const float* weights, int k
                                     (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// The sorted sweep on its parameter block (flood_common.hpp).  minima: into out_d2, every tile; shard: into out_d2, the
+// tiles of shard_rank of shard_world; faces: fused with the face maxima, no out_d2.
+int flooder::sorted_sweep(const flooder_sorted_sweep_t& a, SortedMode mode, void* stream) {
+  const bool faces = mode == SortedMode::faces, shard = mode == SortedMode::shard;
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.sample_order || !a.queue || a.n_pts < 1 || a.k1 < 1 ||
+      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices * (int64_t)a.R > 0xfffffffeLL ||
+      (faces ? (!a.memb || !a.face_bits || a.n_faces < 1 || a.n_faces > 32) : !a.out_d2) ||
+      (shard && (a.shard_world < 1 || a.shard_rank < 0 || a.shard_rank >= a.shard_world)))
+    return fail(FLOODER_E_ARG, "sorted sweep: bad argument");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<SweepSortedOp>(
+      a.dim, a, lv,
+      faces ? SortedFaces{a.memb, a.face_bits, a.face_slot, a.n_faces, g_sorted_refresh} : SortedFaces{nullptr, nullptr, nullptr, 0, 0},
+      shard ? TileShard{a.shard_rank, a.shard_world} : TileShard{0, 1}, (hipStream_t)stream);
+}
+
+extern "C" {
+
+// the three positional forms: one body, three modes
 int flooder_sweep_bvh_sorted_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                                  const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
                                  const int32_t* sample_order, int32_t* queue, uint32_t* out_d2, uint64_t* stats,
                                  void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !weights || !sample_order || !queue || !out_d2 || n_pts < 1 || k1 < 1 ||
-      k1 > FLOODER_MAX_VERTS || R < 0 || n_simplices * (int64_t)R > 0xfffffffeLL)
-    return fail(FLOODER_E_ARG, "flooder_sweep_bvh_sorted_f32: bad argument");
-  const Levels lv = make_levels(n_pts);
-  return dispatch_dim<SweepSortedOp>(dim, pts_sorted, nodes, lv, verts, weights, k1, R, n_simplices * (int64_t)R,
-                                     reinterpret_cast<const uint32_t*>(sample_order), queue, out_d2,
-                                     reinterpret_cast<unsigned long long*>(stats), SortedFaces{nullptr, nullptr, nullptr, 0, 0},
-                                     TileShard{0, 1}, (hipStream_t)stream);
+  flooder_sorted_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.sample_order = sample_order; a.queue = queue; a.stats = stats;
+  a.out_d2 = out_d2;
+  return sorted_sweep(a, SortedMode::minima, stream);
 }
 
 int flooder_sweep_bvh_sorted_shard_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                                        const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
                                        const int32_t* sample_order, int shard_rank, int shard_world, int32_t* queue,
                                        uint32_t* out_d2, uint64_t* stats, void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !weights || !sample_order || !queue || !out_d2 || n_pts < 1 || k1 < 1 ||
-      k1 > FLOODER_MAX_VERTS || R < 0 || n_simplices * (int64_t)R > 0xfffffffeLL || shard_world < 1 || shard_rank < 0 ||
-      shard_rank >= shard_world)
-    return fail(FLOODER_E_ARG, "flooder_sweep_bvh_sorted_shard_f32: bad argument");
-  const Levels lv = make_levels(n_pts);
-  return dispatch_dim<SweepSortedOp>(dim, pts_sorted, nodes, lv, verts, weights, k1, R, n_simplices * (int64_t)R,
-                                     reinterpret_cast<const uint32_t*>(sample_order), queue, out_d2,
-                                     reinterpret_cast<unsigned long long*>(stats), SortedFaces{nullptr, nullptr, nullptr, 0, 0},
-                                     TileShard{shard_rank, shard_world}, (hipStream_t)stream);
+  flooder_sorted_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.sample_order = sample_order; a.queue = queue; a.stats = stats;
+  a.out_d2 = out_d2; a.shard_rank = shard_rank; a.shard_world = shard_world;
+  return sorted_sweep(a, SortedMode::shard, stream);
 }
 
 int flooder_sweep_bvh_sorted_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes,
                                        const float* verts, const float* weights, int k1, int R, int64_t n_simplices,
                                        const int32_t* sample_order, int32_t* queue, const uint32_t* memb, int n_faces,
                                        uint32_t* face_bits, const int32_t* face_slot, uint64_t* stats, void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !weights || !sample_order || !queue || !memb || !face_bits || n_pts < 1 || k1 < 1 ||
-      k1 > FLOODER_MAX_VERTS || R < 0 || n_faces < 1 || n_faces > 32 || n_simplices * (int64_t)R > 0xfffffffeLL)
-    return fail(FLOODER_E_ARG, "flooder_sweep_bvh_sorted_faces_f32: bad argument");
-  const Levels lv = make_levels(n_pts);
-  return dispatch_dim<SweepSortedOp>(dim, pts_sorted, nodes, lv, verts, weights, k1, R, n_simplices * (int64_t)R,
-                                     reinterpret_cast<const uint32_t*>(sample_order), queue, (uint32_t*)nullptr,
-                                     reinterpret_cast<unsigned long long*>(stats),
-                                     SortedFaces{memb, face_bits, face_slot, n_faces, g_sorted_refresh}, TileShard{0, 1}, (hipStream_t)stream);
+  flooder_sorted_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.sample_order = sample_order; a.queue = queue; a.stats = stats;
+  a.memb = memb; a.n_faces = n_faces; a.face_bits = face_bits; a.face_slot = face_slot;
+  return sorted_sweep(a, SortedMode::faces, stream);
 }
 
 }  // extern "C"

@@ -1353,21 +1353,22 @@ __global__ __launch_bounds__(1024) void wit_list_kernel(const float* __restrict_
 
 template <int DIM>
 struct WitOp {
-  static int run(const float* pts, const float* nodes, const Levels& lv, const float* verts, float* plane_tab,
-                 const float* weights, int k1, int R, int64_t ns, WitPlan plan, int32_t* queue, int32_t* item_list,
-                 int32_t* item_count, WitOut out, FaceAcc acc, unsigned long long* stats, const int32_t* kind,
-                 bool planes_ready, hipStream_t st) {
+  static int run(const flooder_fused_sweep_t& a, const Levels& lv, WitPlan plan, WitOut out, FaceAcc acc,
+                 const int32_t* kind, hipStream_t st) {
     if constexpr (DIM == 2 || DIM == 3) {
-      if (!planes_ready) {   // (flooder_simplex_prepare_f32 may have written the rows already)
-        const int rc = launch_simplex_planes(DIM, verts, k1, ns, plane_tab, st);
+      const int64_t ns = a.n_simplices;
+      int32_t* item_count = a.wit_queue + FLOODER_WIT_QUEUE_ITEM_COUNT;
+      if (!a.planes_ready) {   // (flooder_simplex_prepare_f32 may have written the rows already)
+        const int rc = launch_simplex_planes(DIM, a.verts, a.k1, ns, a.plane_scratch, st);
         if (rc != FLOODER_OK) return rc;
       }
-      hipLaunchKernelGGL(wit_list_kernel, dim3(1), dim3(1024), 0, st, out.weight, (int)ns, (float)g_wit_weight, item_list,
+      hipLaunchKernelGGL(wit_list_kernel, dim3(1), dim3(1024), 0, st, out.weight, (int)ns, (float)g_wit_weight, a.wit_item_list,
                          item_count, g_wit_surface_pct > 0 ? kind : nullptr, g_wit_surface_pct);
       const int grid = (int)(ns < g_wit_grid ? ns : g_wit_grid);
-      hipLaunchKernelGGL((wit_sweep_kernel<DIM>), dim3(grid), dim3(WTHREADS), 0, st, pts, nodes, lv, verts, plane_tab, weights, k1,
-                         R, ns, (float)g_wit_weight, 0.01f * (float)g_wit_cmax_pct, 0.01f * (float)g_wit_cmax_ext_pct, g_wit_min_bins, g_wit_flags, g_wit_max_open, (int)((int64_t)R * g_wit_max_live_pct / 100), (int)((int64_t)R * g_wit_max_in_pct / 100), g_wit_adaptive, g_wit_max_leaves < WLEAF ? g_wit_max_leaves : WLEAF, g_wit_max_eval, g_wit_sorted_stage, item_list, item_count, plan, queue, out, acc,
-                         stats);
+      const int R = a.R;
+      hipLaunchKernelGGL((wit_sweep_kernel<DIM>), dim3(grid), dim3(WTHREADS), 0, st, a.pts_sorted, a.nodes, lv, a.verts, a.plane_scratch, a.weights, a.k1,
+                         R, ns, (float)g_wit_weight, 0.01f * (float)g_wit_cmax_pct, 0.01f * (float)g_wit_cmax_ext_pct, g_wit_min_bins, g_wit_flags, g_wit_max_open, (int)((int64_t)R * g_wit_max_live_pct / 100), (int)((int64_t)R * g_wit_max_in_pct / 100), g_wit_adaptive, g_wit_max_leaves < WLEAF ? g_wit_max_leaves : WLEAF, g_wit_max_eval, g_wit_sorted_stage, a.wit_item_list, item_count, plan, a.wit_queue, out, acc,
+                         reinterpret_cast<unsigned long long*>(a.wit_stats));
       return check_launch("wit_sweep");
     } else {
       return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: only dim 2 and 3");
@@ -1377,58 +1378,51 @@ struct WitOp {
 
 }  // namespace
 
-namespace flooder {
-
-// flooder_sweep_witness_f32 plus the density grid of the index (NULL: none): with it the sweep stands back on a cloud
-// that lies on a surface ("wit_surface_pct").  The parameter-block form passes the grid it holds anyway.
-int sweep_witness(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
-                  const float* weights, int k1, int R, int64_t n_simplices, const int32_t* coarse_rows, int n_coarse,
-                  const uint32_t* parents, int32_t* queue, uint32_t* d2_scratch, const uint32_t* memb, int n_faces,
-                  uint32_t* face_bits, const int32_t* face_slot, int32_t* flag_list, int32_t* flag_count,
-                  uint32_t* flag_key, int32_t* flag_hist, uint64_t* top, int32_t* top_list, int32_t* top_count,
-                  float* simplex_weight, int32_t* item_list, float* plane_scratch, uint64_t* stats,
-                  const int32_t* density_grid, const uint32_t* runs, int run_len, int n_runs, bool planes_ready,
-                  void* stream) {
-  if (n_simplices == 0 || R == 0) return FLOODER_OK;
-  if (!pts_sorted || !nodes || !verts || !weights || !coarse_rows || !parents || !queue || !d2_scratch || !memb ||
-      !face_bits || !flag_list || !flag_count || !simplex_weight || !item_list || !plane_scratch || n_pts < 1 || k1 < 1 ||
-      k1 > FLOODER_MAX_VERTS || R < 1 || R > WROWS || n_coarse < 1 || n_coarse > WCOARSE || n_faces < 1 || n_faces > 32 ||
-      (top && (!top_list || !top_count)) || (flag_key && !flag_hist) || n_simplices > 0x7fffffffLL)
+// The witness sweep on its parameter block (flood_common.hpp): checks, then the kernels' structs straight from the
+// fields.  density_grid (NULL: none): with it the sweep stands back on a cloud that lies on a surface
+// ("wit_surface_pct"); wit_runs (NULL / wit_n_runs 0: no run test); planes_ready: no plane launch.
+int flooder::fused_witness(const flooder_fused_sweep_t& a, void* stream) {
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.coarse_rows || !a.parents || !a.wit_queue || !a.d2_scratch ||
+      !a.memb || !a.face_bits || !a.flag_list || !a.flag_count || !a.simplex_weight || !a.wit_item_list || !a.plane_scratch ||
+      a.n_pts < 1 || a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS || a.R < 1 || a.R > WROWS || a.n_coarse < 1 || a.n_coarse > WCOARSE ||
+      a.n_faces < 1 || a.n_faces > 32 || (a.top && (!a.top_list || !a.top_count)) || (a.flag_key && !a.flag_hist) ||
+      a.n_simplices > 0x7fffffffLL)
     return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: bad argument");
-  if (dim != 2 && dim != 3) return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: only dim 2 and 3");
-  if (n_simplices * (int64_t)((R + 63) / 64) > 0x7fffffffLL)
+  if (a.dim != 2 && a.dim != 3) return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: only dim 2 and 3");
+  if (a.n_simplices * (int64_t)((a.R + 63) / 64) > 0x7fffffffLL)
     return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: too many (simplex, tile) pairs");
-  const Levels lv = make_levels(n_pts);
-  if ((n_pts + FLOODER_BVH_LEAF) * (int64_t)(padded_dim(dim) * sizeof(float)) >= (1LL << 32) ||
-      total_nodes(lv) * (int64_t)(2 * padded_dim(dim) * sizeof(float)) >= (1LL << 32))
+  const Levels lv = make_levels(a.n_pts);
+  if ((a.n_pts + FLOODER_BVH_LEAF) * (int64_t)(padded_dim(a.dim) * sizeof(float)) >= (1LL << 32) ||
+      total_nodes(lv) * (int64_t)(2 * padded_dim(a.dim) * sizeof(float)) >= (1LL << 32))
     return fail(FLOODER_E_ARG, "flooder_sweep_witness_f32: cloud too large");
-  FaceAcc acc{memb, face_bits, n_faces, reinterpret_cast<unsigned long long*>(top), top_list, top_count, face_slot,
-              flag_key, flag_hist};
   // run table: whole runs of a power of two >= 8 rows (the run list is 16 bit and shares the leaf list's storage),
   // centre weights for at most four vertices; anything else is a bad argument, no table is no run test
+  const bool have_runs = a.wit_runs && a.wit_n_runs > 0;
   int run_shift = 0;
-  if (runs && n_runs > 0) {
-    if (run_len < 8 || run_len > R || (run_len & (run_len - 1)) != 0 || (int64_t)n_runs * run_len > R || k1 > 4)
+  if (have_runs) {
+    const int run_len = a.wit_run_len;
+    if (run_len < 8 || run_len > a.R || (run_len & (run_len - 1)) != 0 || (int64_t)a.wit_n_runs * run_len > a.R || a.k1 > 4)
       return fail(FLOODER_E_ARG, "flooder_fused_witness: bad run table");
     while ((1 << run_shift) < run_len) ++run_shift;
   }
-  const bool use_runs = runs && n_runs > 0 && g_wit_runs != 0;
-  return dispatch_dim<WitOp>(dim, pts_sorted, nodes, lv, verts, plane_scratch, weights, k1, R, n_simplices,
-                             WitPlan{coarse_rows, parents, n_coarse, use_runs ? reinterpret_cast<const uint4*>(runs) : nullptr,
-                                     run_shift, use_runs ? n_runs : 0}, queue, item_list, queue + FLOODER_QUEUE_WORDS - 1,
-                             WitOut{d2_scratch, flag_list, flag_count, simplex_weight}, acc,
-                             reinterpret_cast<unsigned long long*>(stats),
-                             density_grid ? density_grid + (flooder_density_grid_words(dim) - KIND_WORDS) : nullptr,
-                             planes_ready, (hipStream_t)stream);
+  const bool use_runs = have_runs && g_wit_runs != 0;
+  return dispatch_dim<WitOp>(
+      a.dim, a, lv,
+      WitPlan{a.coarse_rows, a.parents, a.n_coarse, use_runs ? reinterpret_cast<const uint4*>(a.wit_runs) : nullptr,
+              run_shift, use_runs ? a.wit_n_runs : 0},
+      WitOut{a.d2_scratch, a.flag_list, a.flag_count, a.simplex_weight},
+      FaceAcc{a.memb, a.face_bits, a.n_faces, reinterpret_cast<unsigned long long*>(a.top), a.top_list, a.top_count,
+              a.face_slot, a.flag_key, a.flag_hist},
+      a.density_grid ? a.density_grid + (flooder_density_grid_words(a.dim) - KIND_WORDS) : nullptr, (hipStream_t)stream);
 }
-
-}  // namespace flooder
 
 extern "C" {
 
 int flooder_wit_max_rows(void) { return WROWS; }
 int flooder_wit_max_coarse(void) { return WCOARSE; }
 
+// (no density grid, no run table, planes_ready never set: include/flooder_hip.h)
 int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, const float* nodes, const float* verts,
                               const float* weights, int k1, int R, int64_t n_simplices, const int32_t* coarse_rows,
                               int n_coarse, const uint32_t* parents, int32_t* queue, uint32_t* d2_scratch,
@@ -1436,10 +1430,14 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
                               int32_t* flag_list, int32_t* flag_count, uint32_t* flag_key, int32_t* flag_hist,
                               uint64_t* top, int32_t* top_list, int32_t* top_count, float* simplex_weight,
                               int32_t* item_list, float* plane_scratch, uint64_t* stats, void* stream) {
-  return sweep_witness(pts_sorted, n_pts, dim, nodes, verts, weights, k1, R, n_simplices, coarse_rows, n_coarse, parents,
-                       queue, d2_scratch, memb, n_faces, face_bits, face_slot, flag_list, flag_count, flag_key, flag_hist,
-                       top, top_list, top_count, simplex_weight, item_list, plane_scratch, stats, nullptr, nullptr, 0, 0,
-                       false, stream);
+  flooder_fused_sweep_t a{};
+  a.pts_sorted = pts_sorted; a.n_pts = n_pts; a.dim = dim; a.nodes = nodes; a.verts = verts; a.weights = weights;
+  a.k1 = k1; a.R = R; a.n_simplices = n_simplices; a.coarse_rows = coarse_rows; a.n_coarse = n_coarse;
+  a.parents = parents; a.wit_queue = queue; a.d2_scratch = d2_scratch; a.memb = memb; a.n_faces = n_faces;
+  a.face_bits = face_bits; a.face_slot = face_slot; a.flag_list = flag_list; a.flag_count = flag_count;
+  a.flag_key = flag_key; a.flag_hist = flag_hist; a.top = top; a.top_list = top_list; a.top_count = top_count;
+  a.simplex_weight = simplex_weight; a.wit_item_list = item_list; a.plane_scratch = plane_scratch; a.wit_stats = stats;
+  return fused_witness(a, stream);
 }
 
 }  // extern "C"

@@ -472,6 +472,35 @@ int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, co
                              const uint32_t* memb, int n_faces, uint32_t* face_bits, const int32_t* face_slot,
                              uint64_t* hard_scratch, int hard_cap, uint64_t* stats, void* stream);
 
+/*
+ * Control words of the fused sweep, by name (int32 word offsets; what the prose above calls ctl[3], defer_ctl + 2, ...).
+ * `ctl` of flooder_finish_faces_f32 (flooder_fused_sweep_t: finish_ctl), FLOODER_FINISH_CTL_WORDS zeroed words:
+ */
+#define FLOODER_FINISH_CTL_PASS_HEADS 0     /* [0..2] a word per pass (probe / top / rest) kept for its head    */
+#define FLOODER_FINISH_CTL_TOP_COUNT 3      /* entries of top_list (what top_count of the sweeps points at)      */
+#define FLOODER_FINISH_CTL_TOP_HARD_HEAD 4  /* top pass: queue head of its hard entries ...                      */
+#define FLOODER_FINISH_CTL_TOP_HARD_LEN 5   /* ... and how many it listed                                        */
+#define FLOODER_FINISH_CTL_REST_HARD_HEAD 6 /* rest pass: the same two                                           */
+#define FLOODER_FINISH_CTL_REST_HARD_LEN 7
+#define FLOODER_FINISH_CTL_SINGLE_LEFT 8    /* samples the short-list launch left over                           */
+#define FLOODER_FINISH_CTL_QUEUES 24        /* sharded heads of pass p: + p * FLOODER_QUEUE_WORDS (p = 0, 1, 2)  */
+#define FLOODER_FINISH_CTL_WORDS (FLOODER_FINISH_CTL_QUEUES + 3 * FLOODER_QUEUE_WORDS)
+/* defer_ctl of flooder_sweep_cell_faces_f32, FLOODER_DEFER_CTL_WORDS zeroed words: */
+#define FLOODER_DEFER_CTL_COUNT 0           /* chunks on defer_list ...                                          */
+#define FLOODER_DEFER_CTL_QUEUE 1           /* ... and a word kept for their queue head (popped from `queue`)    */
+#define FLOODER_DEFER_CTL_LIGHT 2           /* simplices on light_list,                                          */
+#define FLOODER_DEFER_CTL_HEAVY 3           /* on heavy_list,                                                    */
+#define FLOODER_DEFER_CTL_SPLIT_DONE 4      /* 1 once both lists are filled                                      */
+#define FLOODER_DEFER_CTL_TILE_COUNT 6      /* tiles handed to the third launch (option "cell_tiles")            */
+#define FLOODER_DEFER_CTL_WORDS 8
+/* queue areas: `queue` of the cell sweeps holds the heads of its three launches, FLOODER_QUEUE_WORDS each; the last word
+ * of the witness sweep's one queue is the length of its item list */
+#define FLOODER_CELL_QUEUE_RUNS 0
+#define FLOODER_CELL_QUEUE_CHUNKS FLOODER_QUEUE_WORDS
+#define FLOODER_CELL_QUEUE_TILES (2 * FLOODER_QUEUE_WORDS)
+#define FLOODER_CELL_QUEUE_WORDS (3 * FLOODER_QUEUE_WORDS)
+#define FLOODER_WIT_QUEUE_ITEM_COUNT (FLOODER_QUEUE_WORDS - 1)
+
 /* out_face[i] = sqrt(float(face_bits[i])), i < n: the filtration values (core.py:257, 272: distances, not squares). */
 int flooder_face_values_f32(const uint32_t* face_bits, int64_t n, float* out_face, void* stream);
 
@@ -580,8 +609,11 @@ int flooder_fps_batched_f32(const float* pts, int64_t n_pts, int dim, int ld, co
  * `size` (sizeof of the struct as the caller compiled it) and `abi` (FLOODER_PARAMS_ABI): a library that knows a longer
  * struct reads the fields the caller has and takes the documented default (NULL / 0) for the rest; a caller newer than
  * the library is refused (FLOODER_E_ARG).  Pointers are device pointers unless said otherwise; what every field
- * means, and which may be NULL, is documented at the positional function it is forwarded to - those stay exported as
- * they were (same symbols, same behaviour; flooder_amd's own default path no longer calls them).
+ * means, and which may be NULL, is documented at the positional function of the same launch.  Inside the library the
+ * block IS the argument list: every launch is one function on the block, which checks the fields and fills the kernels'
+ * own structs from them by name.  The forwarding runs from the positional functions to it - each copies its arguments
+ * into a zeroed block, field by field, and makes the same call; they stay exported as they were (same symbols, same
+ * behaviour; flooder_amd's own default path does not call them).
  */
 #define FLOODER_PARAMS_ABI 1
 

@@ -19,7 +19,7 @@ from helpers import assert_close_filtration, get_options, set_options
 pytestmark = pytest.mark.gpu
 
 INF_BITS = 0x7F800000
-LEFT_WORD = 8   # ctl word that counts the samples the short-list launch left over (include/flooder_hip.h)
+LEFT_WORD = _native.FINISH_CTL_SINGLE_LEFT   # ctl word that counts the samples the short-list launch left over
 
 
 @pytest.fixture(scope="module")
@@ -72,12 +72,12 @@ def finish(su, verts, flag_tiles, subs):
     lib, dev = _native.load(), verts.device
     st = _native.current_stream_ptr(dev)
     S, k1, _ = verts.shape
-    R, F, QW = su.R, su.faces.n_faces, core.QUEUE_WORDS
+    R, F = su.R, su.faces.n_faces
     flag_list = torch.as_tensor(np.asarray(flag_tiles, dtype=np.int32), device=dev)
     flag_count = torch.tensor([flag_list.numel()], dtype=torch.int32, device=dev)
     d2 = torch.full((S, R), INF_BITS, dtype=torch.int32, device=dev)
     face_bits = torch.zeros(S * F, dtype=torch.int32, device=dev)
-    ctl = torch.zeros(24 + 3 * QW, dtype=torch.int32, device=dev)
+    ctl = torch.zeros(_native.FINISH_CTL_WORDS, dtype=torch.int32, device=dev)
     top = torch.zeros(S, dtype=torch.int64, device=dev)
     top_list = torch.empty(S, dtype=torch.int32, device=dev)
     hard = torch.empty(4 * core.FINISH_HARD_CAP, dtype=torch.int64, device=dev)

@@ -181,6 +181,31 @@ def test_parameter_blocks_have_the_layout_of_the_header(tmp_path):
         _native.FusedSweep(no_such_field=1)
 
 
+def test_control_words_have_the_values_of_the_header(tmp_path):
+    """The control-word constants of ``_native`` (finish_ctl, defer_ctl, the queue areas) against the FLOODER_* names
+    of include/flooder_hip.h, compiled with the host C compiler: every name of the header is mirrored, same value."""
+    import shutil
+    import subprocess
+
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    header = open(os.path.join(ROOT, "include", "flooder_hip.h")).read()
+    names = re.findall(r"#define FLOODER_((?:FINISH_CTL|DEFER_CTL|CELL_QUEUE|WIT_QUEUE)_[A-Z_]+|QUEUE_WORDS)\b", header)
+    assert len(names) == len(set(names)) == 22, names
+    src = tmp_path / "words.c"
+    src.write_text("\n".join(['#include <stdio.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
+                              'int main(void) {'] + [f'printf("{n} %d\\n", (int)(FLOODER_{n}));' for n in names] +
+                             ['return 0; }']))
+    exe = tmp_path / "words"
+    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
+    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert set(out) == set(names)
+    for name in names:
+        assert getattr(_native, name) == int(out[name]), name
+    assert core.QUEUE_WORDS == _native.QUEUE_WORDS
+
+
 def test_host_libraries_export_header_symbols():
     """include/flooder_host.h: the host-side entry points (Delaunay of the landmarks, persistence, dict hand-off) are
     exported by libflooder_host.so / libflooder_py.so."""
