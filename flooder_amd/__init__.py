@@ -11,6 +11,7 @@ from .core import (flood_complex, generate_landmarks, generate_grid, generate_un
 from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
 from .grad import FloodFiltration, flood_filtration
+from .profile import FloodProfile, flood_profile
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -24,6 +25,8 @@ __all__ = [
     "flood_complex",
     "flood_filtration",
     "FloodFiltration",
+    "flood_profile",
+    "FloodProfile",
     "generate_landmarks",
     "generate_grid",
     "generate_uniform_weights",

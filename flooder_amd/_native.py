@@ -90,6 +90,29 @@ class KnnSweep(_Block):
         i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats""")
 
 
+KNN_COLS_MAX = 64   # FLOODER_KNN_COLS_MAX: every (k, stat) pair with k <= 32 and two statistics
+
+
+class KnnProfile(_Block):
+    """``flooder_knn_profile_t``: one k-nearest sweep at the largest k that writes a plane per (k, stat) column.
+    ``columns``: the (k, stat index) pairs in the caller's order (fills ``n_cols``, ``col_k`` and ``col_stat``)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
+        i32 n_cols; i64 n_simplices; p queue; p out_bits; p stats""") + [("col_k", c_int32 * KNN_COLS_MAX),
+                                                                        ("col_stat", c_int32 * KNN_COLS_MAX)]
+
+    def __init__(self, columns=(), **fields):
+        super().__init__(**fields)
+        columns = list(columns)
+        if columns:
+            if len(columns) > KNN_COLS_MAX:
+                raise ValueError(f"KnnProfile holds at most {KNN_COLS_MAX} columns, got {len(columns)}")
+            self.n_cols = len(columns)
+            for c, (k, stat) in enumerate(columns):
+                self.col_k[c] = int(k)
+                self.col_stat[c] = int(stat)
+
+
 class WitnessKnn(_Block):
     """``flooder_witness_knn_t``: the k points that realise a robust value (flooder_amd.grad, neighbors > 1)."""
 
@@ -202,6 +225,8 @@ SIGNATURES = {
     "flooder_segment_sum_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     # the k nearest points of every sample (flood_complex(neighbors=k))
     "flooder_sweep_knn_f32": (c_int, [ctypes.POINTER(KnnSweep), c_void_p]),
+    # ... every (k, stat) column of a list from one sweep at the largest k (flood_profile)
+    "flooder_sweep_knn_profile_f32": (c_int, [ctypes.POINTER(KnnProfile), c_void_p]),
     # ... and which k points realise the statistic of a witness sample (flood_filtration(neighbors=k))
     "flooder_witness_knn": (c_int, [ctypes.POINTER(WitnessKnn), c_void_p]),
 }

@@ -8,7 +8,8 @@ Mirrors the reference's console script (``flooder/cli.py``: options :185-297, st
 
 Differences, all on the device side: ``cuda:N`` means ROCm device N and is accepted only when it is a gfx950
 (MI355X) whose HIP library loads - the reference's compute-capability gate (:313-317) has no meaning here;
-``--no-triton`` is accepted and ignored (there is one device path); the tables are plain text (``rich`` is not a
+``--no-triton`` is accepted and ignored (there is one device path); ``--neighbors K`` / ``--neighbor-stat`` (not in
+the reference) select the robust filtration of ``flood_complex(neighbors=K, neighbor_stat=...)``; the tables are plain text (``rich`` is not a
 dependency).  Persistence comes from gudhi when it is importable and from the package's own Z/2 reduction
 otherwise (``flooder_amd/simplex_tree.py``).
 """
@@ -61,6 +62,8 @@ class RunMeta:
     use_triton: bool
     n_points: int
     ambient_dim: int
+    neighbors: int = 1              # the robust filtration's k and statistic (1 / "kth": the plain filtration)
+    neighbor_stat: str = "kth"
 
 
 class StepTimer:
@@ -149,6 +152,12 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--device", type=device_type, default="cuda:0", help='Device: "cpu", or "cuda:N" (default: %(default)s)')
     g.add_argument("--seed", metavar="INT", type=int, default=None, help="Random seed (only used when --num-rand is set)")
     g.add_argument("--no-triton", action="store_true", help="Accepted for compatibility (one device path here)")
+    g.add_argument("--neighbors", metavar="K", type=int, default=1,
+                   help="Robust filtration: the K nearest points of every sample instead of the nearest "
+                        "(1..32; default: %(default)s, the plain filtration)")
+    g.add_argument("--neighbor-stat", choices=("kth", "dtm"), default="kth",
+                   help="Statistic of the K nearest: kth (K-distance) or dtm (distance to the empirical measure) "
+                        "(default: %(default)s)")
     mex = g.add_mutually_exclusive_group(required=False)
     mex.add_argument("--points-per-edge", metavar="INT", type=int, default=None,
                      help="Points per edge for Flood PH (default: 30 if neither option given)")
@@ -267,7 +276,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         stree = flood_complex(cloud, args.num_landmarks, max_dimension=max_dim, points_per_edge=points_per_edge,
                               batch_size=args.batch_size, fps_h=args.fps_height,
                               use_triton=use_triton if device.type == "cuda" else None,
-                              return_simplex_tree=True, num_rand=num_rand)
+                              return_simplex_tree=True, num_rand=num_rand, neighbors=args.neighbors,
+                              neighbor_stat=args.neighbor_stat)
     steps.append(t.stats)
     print(f"Building Flood complex with {stree.num_simplices()} simplices done")
 
@@ -282,7 +292,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                        max_dimension=max_dim, fps_height=args.fps_height, batch_size=args.batch_size,
                        device=str(device), points_per_edge=points_per_edge, num_rand=num_rand,
                        seed=args.seed if num_rand is not None else None, use_triton=use_triton,
-                       n_points=n_pts, ambient_dim=dim)
+                       n_points=n_pts, ambient_dim=dim, neighbors=args.neighbors, neighbor_stat=args.neighbor_stat)
         save_output(Path(args.output_file), diagrams, meta)
 
     print(format_stats_table(steps))

@@ -1375,9 +1375,51 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     return out_face, None
 
 
+def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                                 columns, plan: Optional["SamplePlan"] = None,
+                                 stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None):
+    """All simplices of one dimension against an indexed point set for every ``(k, stat)`` of ``columns`` at once ->
+    one (S, F) tensor of face maxima per column, in the order of ``columns``; tensor c holds the bits
+    ``_sweep_dimension_knn(..., k, stat)`` returns for column c.
+
+    ONE sweep_knn at the largest k (``flooder_sweep_knn_profile_f32``: a plane of squared-statistic bits per column,
+    (n_cols, S, R)) -> ``flooder_face_max_f32`` once per plane.  The plane buffer is bounded by
+    ``PROFILE_WORKSPACE_BYTES``: above it the simplices are swept in groups of consecutive rows (a simplex's words do
+    not depend on which others are swept with it).  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, k1, _ = verts.shape
+    R = weights.shape[0]
+    columns = [(int(k), NEIGHBOR_STATS.index(stat)) for k, stat in columns]
+    n_cols = len(columns)
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    F = faces.n_faces
+    out_faces = [torch.empty((S, F), dtype=torch.float32, device=dev) for _ in range(n_cols)]
+    per_group = max(1, min(S, int(PROFILE_WORKSPACE_BYTES) // max(1, 4 * n_cols * R)))
+    for a in range(0, S, per_group):
+        b = min(S, a + per_group)
+        queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
+        planes = torch.empty((n_cols, b - a, R), dtype=torch.int32, device=dev)
+        v_g = verts[a:b]
+        blk = _native.KnnProfile(columns, pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes,
+                                 verts=v_g, weights=plan.w_perm, R=R, n_simplices=b - a, queue=queue, out_bits=planes,
+                                 stats=stats)
+        with _span(timer, "sweep"):
+            _native.check(lib.flooder_sweep_knn_profile_f32(ctypes.byref(blk), st), "flooder_sweep_knn_profile_f32")
+        with _span(timer, "face_max"):
+            for c in range(n_cols):
+                _native.check(lib.flooder_face_max_f32(_native.ptr(planes[c]), b - a, R, _native.ptr(faces.ptr),
+                                                       _native.ptr(plan.rows_perm), F, _native.ptr(out_faces[c][a:b]),
+                                                       None, st), "flooder_face_max_f32")
+    return out_faces
+
+
 # tree sweep over spatially sorted samples (csrc/flood_sorted.hip): None = above 3 dimensions, True / False = always / never
 BVH_SORTED_SAMPLES: Optional[bool] = None
 SORTED_WORKSPACE_BYTES = 16 << 30   # scratch the sorted-sample sweep may take (288 GB of HBM per GPU)
+PROFILE_WORKSPACE_BYTES = SORTED_WORKSPACE_BYTES   # plane buffer of one profile sweep (4 B x columns x S x R); above it: groups of simplices
 SORTED_FUSED_FACES = False  # the sorted sweep delivers the face maxima itself and drops what cannot raise one (measured SLOWER at cfg 4: 116 vs 87 ms - in 6-D the distances of a triangle's samples concentrate, 83 % of the leaves are still evaluated; kept as an option)
 BVH_SORTED_MIN_SAMPLES = 64 * 1024   # below this the sort costs more than it saves
 EMPTY_CACHE_ABOVE_BYTES = 1 << 30   # flood_complex releases the allocator's cache when more than this is cached unused

@@ -25,6 +25,12 @@
 // values as it is.  The lists at the end are therefore the k smallest d2 of ALL points, value for value, whatever the
 // tree looks like; the mean adds them in ascending order, smallest first, in float32, and divides by (float)k with the
 // correctly rounded division - a function of those k values alone.
+//
+// flooder_sweep_knn_profile_f32 is the same sweep at k_max = the largest k of a list of (k, stat) columns with another
+// epilogue (PROFILE): the first t live registers of a lane ARE its t smallest d2, and the running ascending sum
+// over them is the sum the single sweep forms at k = t, so one walk of the K slots stores the word of every listed
+// column into that column's (S, R) plane - the words flooder_sweep_knn_f32 writes for that (k, stat), bit for bit.
+// One kernel body serves both; the epilogue is selected at compile time.
 
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
@@ -37,11 +43,18 @@ namespace {
 
 constexpr float SAFE = 0.99999f;   // the margin of the other tree sweeps (flood_bvh.hip)
 
-template <int DIM, int K>
+struct KnnProfileCols {   // column of (statistic, rank - 1), -1: not asked for (kernarg segment: scalar look-ups)
+  int32_t col_of[2][FLOODER_KNN_MAX];
+};
+
+// PROFILE = false: flooder_sweep_knn_f32, one word per sample (`stat` of its k values; `cols` is not read).
+// PROFILE = true: flooder_sweep_knn_profile_f32, k = the largest k of the columns, out_bits holds a plane per column.
+template <int DIM, int K, bool PROFILE>
 __global__ __launch_bounds__(256) void sweep_knn_kernel(
     const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
     const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int k, int stat,
-    int32_t* __restrict__ queue, uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats) {
+    int32_t* __restrict__ queue, uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats,
+    KnnProfileCols cols) {
   constexpr int DP = padded_dim(DIM);
   __shared__ float s_lb[4][MAXL][FAN];
   __shared__ int64_t s_grp[4][MAXL];
@@ -197,7 +210,25 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
       M = wave_max_f32(__int_as_float(list[K - 1]));
     }
 
-    if (live) {
+    if constexpr (PROFILE) {
+      // every listed (k', stat) with k' <= k from the one list: its first t live slots are the t smallest d2, and the
+      // running ascending sum after slot i is the sum the other branch forms at k = i - first + 1
+      if (live) {
+        const int64_t plane = n_simplices * (int64_t)R, cell = s * (int64_t)R + r;
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          if (i >= first) {   // live slot of rank t + 1 (wave-uniform; the register index i is a constant)
+            const int t = i - first;
+            const float v = __int_as_float(list[i]);
+            acc = t == 0 ? v : acc + v;
+            const int c_kth = cols.col_of[0][t], c_dtm = cols.col_of[1][t];
+            if (c_kth >= 0) out_bits[c_kth * plane + cell] = __float_as_uint(v);
+            if (c_dtm >= 0) out_bits[c_dtm * plane + cell] = __float_as_uint(acc / (float)(t + 1));
+          }
+        }
+      }
+    } else if (live) {
       float v = __int_as_float(list[K - 1]);
       if (stat != 0) {   // mean of the k smallest: ascending, smallest first, sequential float32 adds
         float acc = 0.f;
@@ -228,9 +259,9 @@ struct SweepKnnOp {
     int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
     if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
 #define FLOODER_LAUNCH_KNN(K_)                                                                                       \
-  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, lv, \
-                     a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat, a.queue, a.out_bits,                 \
-                     reinterpret_cast<unsigned long long*>(a.stats))
+  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_, false>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, \
+                     lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat, a.queue, a.out_bits,             \
+                     reinterpret_cast<unsigned long long*>(a.stats), KnnProfileCols{})
     if (a.k <= 2) FLOODER_LAUNCH_KNN(2);
     else if (a.k <= 4) FLOODER_LAUNCH_KNN(4);
     else if (a.k <= 8) FLOODER_LAUNCH_KNN(8);
@@ -245,6 +276,39 @@ template <>
 struct SweepKnnOp<1> {
   static int run(const flooder_knn_sweep_t&, const Levels&, hipStream_t) {
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
+  }
+};
+
+struct KnnProfileLaunch {   // the checked block and what the host derives from it
+  flooder_knn_profile_t a;
+  int k_max;
+  KnnProfileCols cols;
+};
+
+template <int DIM>
+struct SweepKnnProfileOp {
+  static int run(const KnnProfileLaunch& p, const Levels& lv, hipStream_t st) {
+    const flooder_knn_profile_t& a = p.a;
+    const int64_t n_items = a.n_simplices * ((a.R + 63) / 64);
+    int64_t grid = g_bvh_grid;  // as the single sweep: persistent blocks, 4 independent waves each
+    if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+#define FLOODER_LAUNCH_KNN_PROFILE(K_)                                                                               \
+  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_, true>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, \
+                     lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, p.k_max, 0, a.queue, a.out_bits,             \
+                     reinterpret_cast<unsigned long long*>(a.stats), p.cols)
+    if (p.k_max <= 2) FLOODER_LAUNCH_KNN_PROFILE(2);
+    else if (p.k_max <= 4) FLOODER_LAUNCH_KNN_PROFILE(4);
+    else if (p.k_max <= 8) FLOODER_LAUNCH_KNN_PROFILE(8);
+    else if (p.k_max <= 16) FLOODER_LAUNCH_KNN_PROFILE(16);
+    else FLOODER_LAUNCH_KNN_PROFILE(32);
+#undef FLOODER_LAUNCH_KNN_PROFILE
+    return check_launch("sweep_knn_profile");
+  }
+};
+template <>
+struct SweepKnnProfileOp<1> {
+  static int run(const KnnProfileLaunch&, const Levels&, hipStream_t) {
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: dim must be in 2..8");
   }
 };
 
@@ -265,4 +329,38 @@ extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream)
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad argument (null pointer, fewer points than k, k1, R)");
   const Levels lv = make_levels(a.n_pts);
   return dispatch_dim<SweepKnnOp>(a.dim, a, lv, (hipStream_t)stream);
+}
+
+extern "C" int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream) {
+  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_knn_profile_t))
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: bad parameter block (abi / size)");
+  KnnProfileLaunch L;
+  flooder_knn_profile_t& a = L.a;
+  std::memset(&a, 0, sizeof(a));
+  std::memcpy(&a, p, p->size);
+  if (a.n_cols < 1 || a.n_cols > FLOODER_KNN_COLS_MAX)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: n_cols must be in 1..64");
+  for (int s = 0; s < 2; ++s)
+    for (int t = 0; t < FLOODER_KNN_MAX; ++t) L.cols.col_of[s][t] = -1;
+  L.k_max = 0;
+  for (int c = 0; c < a.n_cols; ++c) {
+    const int k = a.col_k[c], s = a.col_stat[c];
+    if (k < 1 || k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: col_k must be in 1..32");
+    if (s != 0 && s != 1)
+      return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: col_stat must be 0 (kth) or 1 (dtm)");
+    if (L.cols.col_of[s][k - 1] >= 0)
+      return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: a (k, stat) column is listed twice");
+    L.cols.col_of[s][k - 1] = c;
+    if (k > L.k_max) L.k_max = k;
+  }
+  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: dim must be in 2..8");
+  if (a.n_pts < L.k_max)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: fewer points than the largest k");
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.k1 < 1 ||
+      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: bad argument (null pointer, k1, R)");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<SweepKnnProfileOp>(a.dim, L, lv, (hipStream_t)stream);
 }

@@ -118,7 +118,12 @@ def flood_complex_sharded(points: torch.Tensor, landmarks: torch.Tensor, *args, 
 
     With ``num_rand`` the sample weights come from the global CPU generator; rank 0's generator state is
     broadcast first (``sync_cpu_rng``), so seeding rank 0 is enough and the result equals the unsharded
-    one under that seed.  ``always_reduce``: run the collectives on a one-rank group too (``min_reduce_hook``)."""
+    one under that seed.  ``always_reduce``: run the collectives on a one-rank group too (``min_reduce_hook``).
+
+    ``neighbors`` / ``neighbor_stat`` (the robust filtration) are forwarded like every other keyword.  With k > 1
+    ``mode="simplices"`` works - every rank sweeps its simplices against the full cloud and the result is the unsharded
+    one; ``mode="points"`` and ``mode="blocks"`` raise ``flood_complex``'s own refusals (a MIN over point shards is not
+    the k-th nearest of their union; a block's bounding balls bound the nearest point only)."""
     if not isinstance(landmarks, torch.Tensor):
         raise TypeError("flood_complex_sharded needs explicit landmark coordinates (identical on every "
                         "rank); run generate_landmarks on the full cloud first")

@@ -830,6 +830,38 @@ typedef struct flooder_knn_sweep_s {        /* flooder_sweep_knn_f32 */
 int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream);
 
 /*
+ * flooder_sweep_knn_profile_f32: ONE sweep at k_max = max(col_k) that writes a plane of flooder_sweep_knn_f32's words
+ * for every listed (k, stat) column (flooder_amd.flood_profile).  A lane ends a tile with its k_max smallest d2
+ * ascending in registers; the first t of them are its t smallest, and the running ascending float32 sum over them is
+ * the sum flooder_sweep_knn_f32 forms at k = t - so out_bits[c, s, r] equals, word for word, what
+ * flooder_sweep_knn_f32 with k = col_k[c], stat = col_stat[c] writes to out_bits[s, r].  Plane c belongs to column c in
+ * the caller's order; plane offsets are 64-bit.  n_cols in 1..FLOODER_KNN_COLS_MAX, col_k in 1..FLOODER_KNN_MAX,
+ * col_stat 0 or 1, no (k, stat) pair twice, k_max <= n_pts, dim in 2..8.  queue and stats as flooder_sweep_knn_f32
+ * (the traversal, and so the counters, are those of the single sweep at k_max).
+ */
+#define FLOODER_KNN_COLS_MAX 64
+
+typedef struct flooder_knn_profile_s {      /* flooder_sweep_knn_profile_f32 */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) */
+  int32_t R;
+  int32_t n_cols;             /* columns, 1..FLOODER_KNN_COLS_MAX */
+  int64_t n_simplices;
+  int32_t* queue;
+  uint32_t* out_bits;         /* (n_cols, n_simplices, R) */
+  uint64_t* stats;            /* may be NULL */
+  int32_t col_k[FLOODER_KNN_COLS_MAX];      /* neighbours of column c, 1..FLOODER_KNN_MAX */
+  int32_t col_stat[FLOODER_KNN_COLS_MAX];   /* 0 = kth, 1 = dtm */
+} flooder_knn_profile_t;
+int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream);
+
+/*
  * flooder_witness_knn (csrc/flood_grad.hip; flooder_amd.grad with neighbors > 1): the witness of a robust value.  Per
  * query q, p* = sum_j weights[q_row[q], j] * verts[q_simplex[q], j, :] (fma in vertex order, as the sweeps), then the
  * k smallest keys (d2 word, original id = order[row]) over ALL n_pts points - d2 = t0*t0, then fma(t, t, d2), a point
