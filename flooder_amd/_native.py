@@ -121,6 +121,13 @@ class WitnessKnn(_Block):
         i32 stat; i32 reserved""")
 
 
+class KnnMerge(_Block):
+    """``flooder_knn_merge_t``: the exact k-best merge of the point shards' lists (robust filtration, ``mode="points"``)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p lists; i64 n_cells; i32 n_lists; i32 k; i32 stat; i32 reserved;
+        p out_bits""")
+
+
 # The control words of the fused sweep (include/flooder_hip.h, FLOODER_<name>: int32 word offsets into finish_ctl,
 # defer_ctl and the queue areas); tests/test_host.py compiles the header and compares
 QUEUE_WORDS = 512
@@ -229,6 +236,8 @@ SIGNATURES = {
     "flooder_sweep_knn_profile_f32": (c_int, [ctypes.POINTER(KnnProfile), c_void_p]),
     # ... and which k points realise the statistic of a witness sample (flood_filtration(neighbors=k))
     "flooder_witness_knn": (c_int, [ctypes.POINTER(WitnessKnn), c_void_p]),
+    # ... and the k best of the union of the point shards' k best (flood_complex(neighbor_reduce_hook=...))
+    "flooder_knn_merge_f32": (c_int, [ctypes.POINTER(KnnMerge), c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -1309,9 +1309,12 @@ KNN_MAX = 32
 NEIGHBOR_STATS = ("kth", "dtm")
 
 
-def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, reduce_hook=None, shard_blocks=False):
+def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, reduce_hook=None, shard_blocks=False,
+                     neighbor_reduce_hook=None):
     """The robust filtration's arguments as ``flood_complex`` and ``flood_filtration`` judge them, before any work is
-    done -> (neighbors as int, method: ``"bvh"`` in place of None / "auto" when neighbors > 1)."""
+    done -> (neighbors as int, method: ``"bvh"`` in place of None / "auto" when neighbors > 1).  With a
+    ``neighbor_reduce_hook`` ``points`` is one shard of the cloud: it may hold fewer than ``neighbors`` points (the
+    shards together must hold them, which only the caller of the hook can see)."""
     if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
         raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
     neighbors = int(neighbors)
@@ -1320,8 +1323,24 @@ def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, red
                          f"kernel), got {neighbors}")
     if neighbor_stat not in NEIGHBOR_STATS:
         raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
-    if points.dim() == 2 and neighbors > max(points.shape[0], 1):
+    if neighbor_reduce_hook is None and points.dim() == 2 and neighbors > max(points.shape[0], 1):
         raise ValueError(f"neighbors={neighbors} exceeds the number of points ({points.shape[0]})")
+    if neighbor_reduce_hook is not None:
+        if neighbors == 1:
+            raise ValueError("neighbor_reduce_hook needs neighbors > 1: with one neighbour the reduction over point "
+                             "shards is a MIN, which is what reduce_hook is for")
+        if reduce_hook is not None:
+            raise ValueError("neighbor_reduce_hook cannot be combined with reduce_hook: the k-best merge of the shards' "
+                             "lists replaces the MIN of their minima")
+        if shard_blocks:
+            raise ValueError("neighbor_reduce_hook cannot be combined with shard_blocks=True: a block's sub-cloud "
+                             "holds the points inside its simplices' bounding balls, which bound the nearest point only")
+        if not points.is_cuda:
+            raise ValueError("neighbor_reduce_hook needs ROCm tensors: the k-best merge of the point shards' lists "
+                             "is a device kernel and CPU tensors have no sharded k-nearest path")
+        if points.dtype is torch.float64:
+            raise ValueError("neighbor_reduce_hook needs float32 ROCm tensors: the k-nearest sweep and the merge of "
+                             "its lists have no float64 kernel")
     if neighbors > 1:
         if method in ("cell", "ball"):
             raise ValueError(f"neighbors > 1 needs the tree sweep: method {method!r} evaluates the nearest point only "
@@ -1416,10 +1435,71 @@ def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights
     return out_faces
 
 
+def _sweep_dimension_knn_sharded(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                                 k: int, stat: str, hook: Callable[[torch.Tensor], torch.Tensor],
+                                 plan: Optional["SamplePlan"] = None, timer: Optional[_KernelTimer] = None):
+    """All simplices of one dimension against THIS RANK'S SHARD of the cloud, ``k`` nearest points per sample over the
+    union of the shards -> (S, F) face maxima, the bits ``_sweep_dimension_knn`` returns on the whole cloud.
+
+    local list sweep (``flooder_sweep_knn_profile_f32`` with the columns (1, "kth") .. (k', "kth"), k' = min(k, points
+    of the shard): the shard's k' smallest squared distances of every sample, ascending, as the first planes of a
+    (k, S_g, R) int32 buffer; the planes beyond k' hold +inf words) -> ``hook(lists)``: the (W, k, S_g, R) int32 tensor
+    of every rank's lists on this device, this rank's included, in any order -> ``flooder_knn_merge_f32`` (the k
+    smallest of the W * k words of a cell and their statistic: exact) ->
+    ``flooder_face_max_f32``.  No host synchronisation here (a hook may need one).  The simplices are swept in groups of
+    consecutive rows so that the list buffer and the gathered one, 4 * k * R * S_g * (W + 1) bytes with W =
+    ``hook.world_size`` (1 if the hook has none), stay within ``KNN_MERGE_WORKSPACE_BYTES``; a simplex's words do not
+    depend on its group, and the groups are the same on every rank (they follow from S, R, k and W alone)."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, k1, _ = verts.shape
+    R = weights.shape[0]
+    k = int(k)
+    k_local = min(k, int(index.n))
+    world = max(1, int(getattr(hook, "world_size", 1)))
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    F = faces.n_faces
+    out_face = torch.empty((S, F), dtype=torch.float32, device=dev)
+    per_group = max(1, min(S, int(KNN_MERGE_WORKSPACE_BYTES) // max(1, 4 * k * R * (world + 1))))
+    for a in range(0, S, per_group):
+        b = min(S, a + per_group)
+        queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
+        lists = torch.empty((k, b - a, R), dtype=torch.int32, device=dev)
+        if k_local < k:   # a shard with fewer than k points: its lists end in +inf words
+            _native.check(lib.flooder_fill_u32(_native.ptr(lists[k_local:]), (k - k_local) * (b - a) * R, INF_BITS,
+                                               st), "flooder_fill_u32")
+        blk = _native.KnnProfile([(t, 0) for t in range(1, k_local + 1)], pts_sorted=index.pts, n_pts=index.n,
+                                 dim=index.dim, k1=k1, nodes=index.nodes, verts=verts[a:b], weights=plan.w_perm, R=R,
+                                 n_simplices=b - a, queue=queue, out_bits=lists, stats=None)
+        with _span(timer, "sweep"):
+            _native.check(lib.flooder_sweep_knn_profile_f32(ctypes.byref(blk), st), "flooder_sweep_knn_profile_f32")
+        with _span(timer, "gather"):
+            gathered = hook(lists)
+        if (not isinstance(gathered, torch.Tensor) or gathered.dtype != torch.int32 or gathered.device != dev
+                or gathered.dim() != 4 or gathered.shape[0] < 1 or tuple(gathered.shape[1:]) != (k, b - a, R)):
+            raise ValueError("neighbor_reduce_hook must return every rank's lists as a (W, k, S, R) int32 tensor on the "
+                             f"device of the points (W >= 1, (k, S, R) = {(k, b - a, R)}), got "
+                             f"{tuple(gathered.shape) if isinstance(gathered, torch.Tensor) else type(gathered).__name__}")
+        gathered = gathered.contiguous()
+        d2 = torch.empty((b - a, R), dtype=torch.int32, device=dev)
+        mrg = _native.KnnMerge(lists=gathered, n_cells=(b - a) * R, n_lists=int(gathered.shape[0]), k=k,
+                               stat=NEIGHBOR_STATS.index(stat), out_bits=d2)
+        with _span(timer, "merge"):
+            _native.check(lib.flooder_knn_merge_f32(ctypes.byref(mrg), st), "flooder_knn_merge_f32")
+        with _span(timer, "face_max"):
+            _native.check(lib.flooder_face_max_f32(_native.ptr(d2), b - a, R, _native.ptr(faces.ptr),
+                                                   _native.ptr(plan.rows_perm), F, _native.ptr(out_face[a:b]), None, st),
+                          "flooder_face_max_f32")
+    return out_face, None
+
+
 # tree sweep over spatially sorted samples (csrc/flood_sorted.hip): None = above 3 dimensions, True / False = always / never
 BVH_SORTED_SAMPLES: Optional[bool] = None
 SORTED_WORKSPACE_BYTES = 16 << 30   # scratch the sorted-sample sweep may take (288 GB of HBM per GPU)
 PROFILE_WORKSPACE_BYTES = SORTED_WORKSPACE_BYTES   # plane buffer of one profile sweep (4 B x columns x S x R); above it: groups of simplices
+KNN_MERGE_WORKSPACE_BYTES = PROFILE_WORKSPACE_BYTES   # a shard's list buffer and the gathered lists of a point-sharded k-nearest pass (4 B x k x S x R x (ranks + 1)); above it: groups of simplices
 SORTED_FUSED_FACES = False  # the sorted sweep delivers the face maxima itself and drops what cannot raise one (measured SLOWER at cfg 4: 116 vs 87 ms - in 6-D the distances of a triangle's samples concentrate, 83 % of the leaves are still evaluated; kept as an option)
 BVH_SORTED_MIN_SAMPLES = 64 * 1024   # below this the sort costs more than it saves
 EMPTY_CACHE_ABOVE_BYTES = 1 << 30   # flood_complex releases the allocator's cache when more than this is cached unused
@@ -1646,6 +1726,7 @@ def flood_complex(
     landmarks_in_cloud: Optional[bool] = None,
     neighbors: int = 1,
     neighbor_stat: str = "kth",
+    neighbor_reduce_hook: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
 ):
     """Flood complex of ``points`` over the Delaunay triangulation of ``landmarks``.
 
@@ -1703,9 +1784,23 @@ def flood_complex(
     nearest point only and are refused), CPU tensors query the kd-tree with ``k=neighbors``; ``reduce_hook`` (a MIN
     over point shards is not the k-th of their union), ``shard_blocks=True`` (the bounding balls of a block bound the
     NEAREST point only) and ROCm float64 tensors are refused; ``simplex_shard`` without blocks works as before.
+
+    ``neighbor_reduce_hook`` (keyword-only; ROCm float32 tensors, ``neighbors`` > 1): ``points`` is one SHARD of the
+    cloud and the result is that of the whole cloud, bit for bit.  Per dimension pass the shard's k smallest squared
+    distances of every sample are written as a (k, S, R) int32 buffer of float32 bit patterns (ascending over the first
+    axis; +inf words where the shard holds fewer than k points), ``hook(lists)`` returns the (W, k, S, R) int32 tensor
+    of every shard's lists on the same device (this one's included, any order;
+    ``flooder_amd.distributed.knn_gather_hook`` is the all-gather), and the k smallest of the W * k words of a sample
+    are the k smallest over the whole cloud (``_sweep_dimension_knn_sharded``).  ``neighbors`` may exceed the number of
+    points of the shard, not of the cloud (``flood_complex_sharded`` checks the sum).  A hook may carry
+    ``world_size`` (W), which bounds the workspace: the simplices are swept in groups against
+    ``KNN_MERGE_WORKSPACE_BYTES``.  Refused with ``neighbors=1`` (``reduce_hook`` is the tool), together with
+    ``reduce_hook`` or ``shard_blocks=True``, on CPU and float64 tensors and with ``method`` ``"cell"`` / ``"ball"``;
+    every rank must pass the same ``sort_axis``; ``simplex_shard`` without blocks composes with it.
     """
     # ---- the robust filtration's arguments, before any work is done
-    neighbors, method = _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks)
+    neighbors, method = _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks,
+                                         neighbor_reduce_hook)
     if use_triton is None:
         use_triton = HAS_HIP_KERNELS
     if use_triton and not _has_hip_kernels():
@@ -1903,6 +1998,9 @@ def flood_complex(
         if on_gpu and sv.shape[0] == 0 and (blocks or slots is not None):   # (more ranks than simplices)
             face_dev = (torch.full((slots[1],), float("inf"), dtype=torch.float32, device=device) if slots is not None
                         else torch.empty((0, faces.n_faces), dtype=torch.float32, device=device))
+        elif on_gpu and neighbors > 1 and neighbor_reduce_hook is not None:
+            face_dev, _ = _sweep_dimension_knn_sharded(index, sv, weights, faces, neighbors, neighbor_stat,
+                                                       neighbor_reduce_hook, plan=plan)
         elif on_gpu and neighbors > 1:
             face_dev, _ = _sweep_dimension_knn(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu:

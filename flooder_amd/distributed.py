@@ -34,12 +34,21 @@ cloud, shrinks with the share; the values are produced whole by one rank each an
 matrix completes them - BASELINE.json's "the point cloud shards ... all-reduce(min) on the per-simplex filtration
 values".  Blocks are not work-balanced (a slab through the dense core of a Gaussian holds the expensive simplices).
 
+With ``neighbors=k > 1`` (the robust filtration) MIN is the wrong reduction - the k-th nearest point of the union is
+not the nearest of the shards' k-th nearest - but the right one is as exact: the k smallest squared distances of a
+sample over the whole cloud are the k smallest of the union of every shard's own k smallest.  On ROCm float32 tensors
+every rank writes its lists as a (k, S, R) buffer of bit patterns, one ``all_gather`` brings the W buffers to every rank
+(``knn_gather_hook``; W * k times the bytes of the k = 1 path's (S, R) buffer per group of simplices) and
+``flooder_knn_merge_f32`` takes the k best of the W * k words of every sample (``neighbor_reduce_hook`` of
+``flood_complex``).  CPU tensors and float64 stay refused.
+
 Shards are interleaved (rank r takes sorted rows r, r+W, r+2W, ...): every rank then sees 1/W of
 each simplex's candidates, so the heavy-tailed per-simplex work balances without any planning.
 """
 
 from __future__ import annotations
 
+from numbers import Integral
 from typing import Optional
 
 import torch
@@ -47,7 +56,7 @@ import torch.distributed as dist
 
 from .core import flood_complex
 
-__all__ = ["shard_points", "min_reduce_hook", "global_widest_axis", "sync_cpu_rng", "flood_complex_sharded"]
+__all__ = ["shard_points", "min_reduce_hook", "knn_gather_hook", "global_widest_axis", "sync_cpu_rng", "flood_complex_sharded"]
 
 
 def shard_points(points: torch.Tensor, rank: int, world_size: int) -> torch.Tensor:
@@ -74,6 +83,58 @@ def min_reduce_hook(group: Optional[dist.ProcessGroup] = None, always: bool = Fa
 
     # a real collective: flood_complex first lets the ranks compare the shape of what they are about to reduce (a
     # six-word MIN through this same hook) and raises on every rank instead of hanging in a mismatched all-reduce
+    hook.checks_ranks = True
+    return hook
+
+
+def knn_gather_hook(group: Optional[dist.ProcessGroup] = None, always: bool = False):
+    """``neighbor_reduce_hook`` for ``flood_complex``: all-gather of the ranks' k-nearest lists over the process group.
+
+    The hook receives this rank's (k, S, R) int32 buffer (float32 bit patterns, ascending over the first axis) and
+    returns the (W, k, S, R) int32 tensor of all ranks' buffers on the same device, in rank order:
+    ``all_gather_into_tensor`` over RCCL (backend ``nccl``); a backend that does not gather device tensors (gloo)
+    is served through pinned host memory.  On a group of ONE rank - or without an initialised process group - it
+    returns ``lists[None]`` without a collective unless ``always`` (the way the RCCL path is exercised on a single GPU).
+    ``hook.world_size`` is W (``flood_complex`` sizes its workspace with it).
+
+    Before the first gather of a call the ranks compare the shape words (k, S, R) of what they are about to gather -
+    six words, MIN of (c, -c) through the same group, as ``core._assert_ranks_agree`` does for the face collectives -
+    and raise on every rank instead of hanging in a mismatched all-gather."""
+    active = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if active else 1
+    collective = active and (always or world > 1)
+    on_device = collective and "nccl" in str(dist.get_backend(group))
+    checked = [False]
+
+    def hook(lists: torch.Tensor) -> torch.Tensor:
+        if not collective:
+            return lists[None]
+        if not checked[0]:
+            from .core import CHECK_RANK_CONSISTENCY
+
+            checked[0] = True
+            if CHECK_RANK_CONSISTENCY:
+                c = torch.tensor([x for v in lists.shape for x in (int(v), -int(v))], dtype=torch.int64,
+                                 device=lists.device)
+                dist.all_reduce(c, op=dist.ReduceOp.MIN, group=group)
+                got = c.cpu().tolist()
+                if any(got[i] != -got[i + 1] for i in range(0, len(got), 2)):
+                    raise RuntimeError("flood_complex: the ranks of this point-sharded run are not about to gather the "
+                                       f"same lists ((k, S, R): min {got[0::2]}, max {[-x for x in got[1::2]]}) - "
+                                       "different landmarks, neighbors or sample tables on some rank")
+        lists = lists.contiguous()
+        if on_device:
+            out = torch.empty((world,) + tuple(lists.shape), dtype=lists.dtype, device=lists.device)
+            dist.all_gather_into_tensor(out, lists, group=group)
+            return out
+        # host-staged: device -> pinned -> the backend's all-gather on host memory -> device
+        mine = torch.empty(lists.shape, dtype=lists.dtype, pin_memory=True)
+        mine.copy_(lists)   # (synchronises with the stream: the backend reads host memory)
+        out = torch.empty((world,) + tuple(lists.shape), dtype=lists.dtype, pin_memory=True)
+        dist.all_gather([out[w] for w in range(world)], mine, group=group)
+        return out.to(lists.device, non_blocking=True)
+
+    hook.world_size = world
     hook.checks_ranks = True
     return hook
 
@@ -122,8 +183,14 @@ def flood_complex_sharded(points: torch.Tensor, landmarks: torch.Tensor, *args, 
 
     ``neighbors`` / ``neighbor_stat`` (the robust filtration) are forwarded like every other keyword.  With k > 1
     ``mode="simplices"`` works - every rank sweeps its simplices against the full cloud and the result is the unsharded
-    one; ``mode="points"`` and ``mode="blocks"`` raise ``flood_complex``'s own refusals (a MIN over point shards is not
-    the k-th nearest of their union; a block's bounding balls bound the nearest point only)."""
+    one.  ``mode="points"`` with k > 1 works on ROCm float32 tensors: instead of the MIN of the shards' minima (which is
+    not the k-th nearest of their union) the ranks all-gather their k smallest squared distances of every sample and
+    each takes the k smallest of the union (``knn_gather_hook``, ``flooder_knn_merge_f32``) - exact, the unsharded
+    result bit for bit, W * k times the bytes of the k = 1 exchange.  A shard may hold fewer than k points; the shards
+    together must hold k (one small all-reduce sums their sizes, and every rank raises ``flood_complex``'s "neighbors
+    exceeds the number of points" otherwise).  On CPU tensors and ROCm float64 tensors ``mode="points"`` with k > 1
+    raises ``flood_complex``'s refusal of ``reduce_hook`` as before, and ``mode="blocks"`` its refusal of
+    ``shard_blocks`` (a block's bounding balls bound the nearest point only)."""
     if not isinstance(landmarks, torch.Tensor):
         raise TypeError("flood_complex_sharded needs explicit landmark coordinates (identical on every "
                         "rank); run generate_landmarks on the full cloud first")
@@ -132,6 +199,18 @@ def flood_complex_sharded(points: torch.Tensor, landmarks: torch.Tensor, *args, 
         sync_cpu_rng(points.device, group, always=always_reduce)
     if mode == "points":
         axis = global_widest_axis(points, group, always_reduce)
+        k = kwargs.get("neighbors", 1)
+        if (isinstance(k, Integral) and not isinstance(k, bool) and k > 1 and points.is_cuda
+                and points.dtype is torch.float32):
+            # the k-best merge of the shards' lists in place of the MIN of their minima
+            total = torch.tensor([points.shape[0]], dtype=torch.int64, device=points.device)
+            if dist.is_available() and dist.is_initialized() and (always_reduce or dist.get_world_size(group) > 1):
+                dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+            total = int(total.item())
+            if k > total:
+                raise ValueError(f"neighbors={int(k)} exceeds the number of points ({total})")
+            return flood_complex(points, landmarks, *args, neighbor_reduce_hook=knn_gather_hook(group, always_reduce),
+                                 sort_axis=axis, **kwargs)
         return flood_complex(points, landmarks, *args, reduce_hook=min_reduce_hook(group, always_reduce),
                              sort_axis=axis, **kwargs)
     if mode not in ("simplices", "blocks"):

@@ -896,6 +896,34 @@ typedef struct flooder_witness_knn_s {      /* flooder_witness_knn */
 } flooder_witness_knn_t;
 int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream);
 
+/*
+ * flooder_knn_merge_f32 (csrc/flood_knn_merge.hip; flood_complex(neighbor_reduce_hook=...), the robust filtration over
+ * point shards): the exact k-best merge.  lists holds, for each of n_cells = S * R cells, n_lists ascending lists of k
+ * float32 bit patterns - (n_lists, k, n_cells) int32, cell index contiguous: list w is the (k, S, R) plane buffer that
+ * flooder_sweep_knn_profile_f32 with the columns (1, "kth") .. (k, "kth") writes for shard w, a list of a shard with
+ * fewer than k points ending in +inf words (0x7f800000).  out_bits[cell] = the word flooder_sweep_knn_f32 writes for
+ * the union of the shards:
+ *   stat 0 ("kth")  the k-th smallest of the n_lists * k words of the cell;
+ *   stat 1 ("dtm")  the k smallest added in ascending order, smallest first, by sequential float32 additions, divided
+ *                   by (float)k (correctly rounded) - the arithmetic of the sweep's own epilogue.
+ * Exact: a point among the k nearest of a sample over the whole cloud is among the k nearest of its shard, so the
+ * union of the lists contains the global list as a multiset; only values are merged, so ties and doubled points need
+ * no rule and the order of the lists does not matter.  One lane per cell, the running list in K registers (K = k
+ * rounded up to 2, 4, 8, 16 or 32) as the sweep keeps it; no atomics, no LDS, every output word written once; plane
+ * offsets are 64-bit.  n_lists >= 1, k in 1..FLOODER_KNN_MAX, 0 <= n_cells <= 2^32 - 256.
+ */
+typedef struct flooder_knn_merge_s {        /* flooder_knn_merge_f32 */
+  uint32_t size, abi;
+  const int32_t* lists;       /* (n_lists, k, n_cells) */
+  int64_t n_cells;            /* S * R */
+  int32_t n_lists;            /* W: shards, >= 1 */
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_MAX */
+  int32_t stat;               /* 0 = kth, 1 = dtm */
+  int32_t reserved;
+  uint32_t* out_bits;         /* (n_cells,) */
+} flooder_knn_merge_t;
+int flooder_knn_merge_f32(const flooder_knn_merge_t* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
