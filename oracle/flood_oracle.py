@@ -27,7 +27,8 @@ path named in BASELINE.json (citations are into the reference repository):
                                    its own value and its facets' values, by increasing dimension.
 
 Pinning: ``tests/golden/*.npz`` are outputs of the *imported reference itself* run in the build
-container (generator: ``oracle/make_goldens.py``), and ``tests/golden/docs_animation_*.csv`` are
+container (generator: ``oracle/make_goldens.py``; the four ``top_rand_*.npz`` are the exception: recorded results
+of ``flood_complex_oracle`` itself, ``oracle/make_top_simplices_goldens.py``), and ``tests/golden/docs_animation_*.csv`` are
 the reference's own committed known-answer values; ``tests/test_oracle.py`` checks this module
 against all of them.
 """

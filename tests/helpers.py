@@ -138,6 +138,65 @@ def assert_tree_matches_kdtree(st, points, landmarks, points_per_edge, top, what
     return n
 
 
+def _kdtree_reference(fc, P, L, k, ppe=None, weights_by_dim=None, top=None):
+    """{stat: {simplex: value}} of every simplex of the dict ``fc`` from ``cKDTree.query(k=k)`` over all points in
+    float64: the samples of the simplex's own lattice (float32 weights and vertices, as the sweep sees them) or of the
+    drawn weights, the maximum over them, then the monotone pass over the facets.  Simplices above ``top``
+    (``max_dimension``) have no samples of their own: the monotone pass alone gives them their facets' maximum."""
+    import itertools
+
+    from scipy.spatial import cKDTree
+
+    from flooder_amd import core
+
+    tree = cKDTree(P.astype(np.float64))
+    by_dim = {}
+    for key in fc:
+        by_dim.setdefault(len(key) - 1, []).append(key)
+    ref = {"kth": {}, "dtm": {}}
+    for d in sorted(by_dim):
+        keys = by_dim[d]
+        if top is not None and d > top:
+            for stat in ("kth", "dtm"):
+                for key in keys:
+                    ref[stat][key] = max(ref[stat][face] for face in itertools.combinations(key, d))
+            continue
+        if weights_by_dim is not None:
+            w = weights_by_dim[d].numpy()
+        elif d == 0:
+            w = np.ones((1, 1), dtype=np.float32)
+        else:
+            w = core.generate_grid(ppe, d, "cpu", torch.float32)[0].numpy()
+        for b in range(0, len(keys), max(1, 2_000_000 // w.shape[0])):
+            part = keys[b:b + max(1, 2_000_000 // w.shape[0])]
+            verts = L[np.array(part)]
+            samples = np.matmul(w[None], verts).astype(np.float32).reshape(-1, P.shape[1])
+            dist, _ = tree.query(samples.astype(np.float64), k=k, workers=-1)
+            dist = dist.reshape(len(part), w.shape[0], k)
+            vals = {"kth": dist[..., -1].max(axis=1), "dtm": np.sqrt((dist ** 2).mean(axis=-1)).max(axis=1)}
+            for stat in ("kth", "dtm"):
+                for key, v in zip(part, vals[stat].tolist()):
+                    for face in itertools.combinations(key, d) if d > 0 else ():
+                        v = max(v, ref[stat][face])
+                    ref[stat][key] = v
+    return ref
+
+
+def smallest32(P: torch.Tensor, Q: torch.Tensor, chunk_elems: int = 1 << 26) -> np.ndarray:
+    """float64 brute force on the device of ``P``: per row of Q the 32 smallest squared distances to ALL rows of P, ascending
+    (d2 added axis by axis in float64 - exact on these inputs)."""
+    n, dim = P.shape
+    per = max(1, chunk_elems // n)
+    out = []
+    for a in range(0, Q.shape[0], per):
+        q = Q[a:a + per]
+        d2 = (q[:, 0:1] - P[:, 0].unsqueeze(0)) ** 2
+        for c in range(1, dim):
+            d2 += (q[:, c:c + 1] - P[:, c].unsqueeze(0)) ** 2
+        out.append(torch.topk(d2, min(32, n), dim=1, largest=False, sorted=True).values.cpu())
+    return torch.cat(out).numpy()
+
+
 def run_on_mkl_compatible_branch(code, tmp_path):
     """Run ``code`` (which fills the dict ``out`` with numpy arrays) in a fresh CPU-only Python process started with
     ``MKL_CBWR=COMPATIBLE``, and return ``out``.
