@@ -829,7 +829,8 @@ struct SweepBvhOp {
     if (ks == 0) ks = R <= 64 ? 1 : 2;  // (measured at cfg 2: 1: 10.7 ms, 2: 10.1, 4: 10.3, 8: 12.1)
     // the transposed refine pays at its cost model's threshold when finishing flagged tiles and at 3x the
     // threshold in the full sweep (cfg 3 finish 12.5 ms vs 17.0 without it; cfg 2 full tree sweep 6.4 vs 8.6 ms)
-    const int refine_pct = item_list ? g_bvh_refine_pct : 3 * g_bvh_refine_pct;
+    // (the option goes up to INT_MAX = never: three times that must stay INT_MAX, not wrap)
+    const int refine_pct = item_list ? g_bvh_refine_pct : (g_bvh_refine_pct > 0x7fffffff / 3 ? 0x7fffffff : 3 * g_bvh_refine_pct);
     const bool batch = item_list != nullptr && ks == 1 && g_bvh_leaf_batch > 1;
 #define FLOODER_LAUNCH_BVH(KS_, LB_)                                                                              \
   hipLaunchKernelGGL((sweep_bvh_kernel<DIM, KS_, LB_>), dim3(grid), dim3(256), 0, st, pts, nodes, lv, verts, weights, \

@@ -456,7 +456,10 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
       // (TEAM: every wave of the workgroup computes the same focus set from the same minima and face maxima.  An
       // entry of the top pass asks for one sample only: its first round takes the lanes recorded with the entry.)
       bool focus = (TEAM && stop_after && first_round) ? (live && ((fmask >> lane) & 1ull) != 0ull)
-                                                       : (live && best >= focus_frac * M);
+                                                       : (live && (focus_frac <= 0.f || best >= focus_frac * M));
+      // (focus_frac 0 - option "finish_focus_pct" 0 - is every live sample, said outright: while the tile's bounds are
+      // still +inf, 0 * M is a NaN, no sample compares above it, and a round without a focus sample settles nothing -
+      // the rounds never ended)
       first_round = false;
       float Mf;
       auto rebound = [&]() {
@@ -942,8 +945,10 @@ struct FinishOp {
                            g_finish_items_cap, g_bvh_refine_pct, (float)g_finish_focus_pct * 0.01f, g_finish_refresh, queue,
                            a.d2_scratch, acc, top, a.top_list, ctl + FLOODER_FINISH_CTL_TOP_COUNT, hl, stats);
       };
-      if (mode == 3) go(finish_faces_kernel<DIM, true>, g_bvh_grid / 4, 64 * TEAM_WAVES);   // a workgroup of 16 waves per hard tile, one per CU
-      else if (wide) go(finish_faces_kernel<DIM, false, 8>, grid * 3 / 4, 512);   // (deep tree: eight waves per workgroup, three per CU)
+      // (both kernels are persistent - any number of workgroups works the list off - but a launch of none is an error,
+      // or hard tiles nobody finishes: option "bvh_grid" goes down to 1, so the two shares are rounded up to one)
+      if (mode == 3) go(finish_faces_kernel<DIM, true>, grid / 4 > 0 ? grid / 4 : 1, 64 * TEAM_WAVES);   // a workgroup of 16 waves per hard tile, one per CU
+      else if (wide) go(finish_faces_kernel<DIM, false, 8>, grid * 3 / 4 > 0 ? grid * 3 / 4 : 1, 512);   // (deep tree: eight waves per workgroup, three per CU)
       else go(finish_faces_kernel<DIM, false>, grid, 256);
     };
     HardLists none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hard_cap, 0};

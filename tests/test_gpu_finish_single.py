@@ -15,11 +15,9 @@ import flooder_amd as fa
 import index_reference as ir
 from flooder_amd import _native, core
 from helpers import assert_close_filtration, get_options, set_options
+from variant_cases import Setup, all_tiles, finish, single_tiles   # the harness, shared with test_gpu_finish_variants
 
 pytestmark = pytest.mark.gpu
-
-INF_BITS = 0x7F800000
-LEFT_WORD = _native.FINISH_CTL_SINGLE_LEFT   # ctl word that counts the samples the short-list launch left over
 
 
 @pytest.fixture(scope="module")
@@ -27,80 +25,6 @@ def dev():
     assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
     _native.load()
     return torch.device("cuda:0")
-
-
-def single_tiles():
-    return int(_native.load().flooder_finish_single_tiles())
-
-
-class Setup:
-    """A cloud, its index, the top simplices of a landmark complex and the lattice of one dimension."""
-
-    def __init__(self, pts, dev, n_landmarks, ppe, verts=None):
-        self.pts = pts.to(dev).contiguous()
-        self.dim = d = pts.shape[1]
-        self.ppe = ppe
-        self.index = core.PointIndex(self.pts)
-        if verts is None:
-            self.lms = fa.generate_landmarks(self.pts, n_landmarks, start_idx=0)
-            self.rows = np.asarray(core._build_complex(self.lms, d)[1][d])
-            verts = self.lms[torch.as_tensor(self.rows, device=dev)]
-        self.verts = verts.to(dev).float().contiguous()
-        self.weights, _, face_idxs = core.generate_grid(ppe, d, dev, torch.float32)
-        self.faces = core._FaceTable(face_idxs, self.weights.shape[0], dev)
-        self.plan = core.SamplePlan(self.weights, self.faces)
-        assert self.plan.memb_all is not None
-        self.R = self.weights.shape[0]
-        self.tiles = (self.R + 63) // 64
-
-    def kdtree_top(self, verts):
-        """value of every simplex of `verts` (maximum over all lattice samples) by the kd-tree, as helpers does it"""
-        from scipy.spatial import cKDTree
-        from oracle import flood_oracle as fo
-
-        tree = cKDTree(self.pts.cpu().numpy(), balanced_tree=False, compact_nodes=False)
-        w, _, _ = fo.generate_grid(self.ppe, self.dim, np.float32)
-        samples = np.matmul(w[None], verts.cpu().numpy()).astype(np.float32)
-        dist, _ = tree.query(samples, workers=-1)
-        return dist.max(axis=1)
-
-
-def finish(su, verts, flag_tiles, subs):
-    """flooder_finish_faces_f32 + flooder_face_values_f32 on the tiles `flag_tiles` (simplex * tiles + tile) of `verts`,
-    every sample unsettled with seed +inf, under option bvh_subs = subs.
-    Returns (face value bits (S, F) int32, the 7 counters, samples left over by the short-list launch)."""
-    lib, dev = _native.load(), verts.device
-    st = _native.current_stream_ptr(dev)
-    S, k1, _ = verts.shape
-    R, F = su.R, su.faces.n_faces
-    flag_list = torch.as_tensor(np.asarray(flag_tiles, dtype=np.int32), device=dev)
-    flag_count = torch.tensor([flag_list.numel()], dtype=torch.int32, device=dev)
-    d2 = torch.full((S, R), INF_BITS, dtype=torch.int32, device=dev)
-    face_bits = torch.zeros(S * F, dtype=torch.int32, device=dev)
-    ctl = torch.zeros(_native.FINISH_CTL_WORDS, dtype=torch.int32, device=dev)
-    top = torch.zeros(S, dtype=torch.int64, device=dev)
-    top_list = torch.empty(S, dtype=torch.int32, device=dev)
-    hard = torch.empty(4 * core.FINISH_HARD_CAP, dtype=torch.int64, device=dev)
-    stats = torch.zeros(7, dtype=torch.int64, device=dev)
-    out = torch.empty((S, F), dtype=torch.float32, device=dev)
-    keep = get_options(lib, b"bvh_subs")
-    try:
-        set_options(lib, {b"bvh_subs": subs})
-        _native.check(lib.flooder_finish_faces_f32(
-            _native.ptr(su.index.pts), su.index.n, su.dim, _native.ptr(su.index.nodes), _native.ptr(verts),
-            _native.ptr(su.plan.w_perm), k1, R, S, _native.ptr(flag_list), _native.ptr(flag_count), None, None, None,
-            _native.ptr(ctl), _native.ptr(top), _native.ptr(top_list), 1, _native.ptr(d2), _native.ptr(su.plan.memb_all), F,
-            _native.ptr(face_bits), None, _native.ptr(hard), core.FINISH_HARD_CAP, _native.ptr(stats), st),
-            "flooder_finish_faces_f32")
-        _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), S * F, _native.ptr(out), st), "flooder_face_values_f32")
-        torch.cuda.synchronize()
-    finally:
-        set_options(lib, keep)
-    return out.view(torch.int32).cpu().numpy(), stats.cpu().numpy(), int(ctl[LEFT_WORD].item())
-
-
-def all_tiles(n_simplices, tiles):
-    return np.arange(n_simplices * tiles, dtype=np.int32)
 
 
 def check_whole_simplices(su, verts, what, want_left=False):
