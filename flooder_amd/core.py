@@ -35,7 +35,7 @@ import os
 import weakref
 import warnings
 from numbers import Integral
-from typing import Callable, Dict, List, Optional, Tuple, Union
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -279,10 +279,14 @@ def _build_complex(landmarks: torch.Tensor, max_dimension: int):
                 buckets[len(simplex) - 1].append(tuple(simplex))
         simplices = [np.array(b, dtype=np.int64).reshape(-1, d + 1) for d, b in enumerate(buckets)]
         return stree, simplices
-    # Qhull cells; the face tables up to max_dimension now, the higher ones when somebody asks for them
-    stree = SimplexTree.from_cells(delaunay_cells(lm), lm.shape[0], eager=max_dimension, trusted=True)
-    simplices = [stree.simplices_of_dimension(d) for d in range(max_dimension + 1)]
-    return stree, simplices
+    return _cell_complex(delaunay_cells(lm), lm.shape[0], max_dimension)
+
+
+def _cell_complex(cells: np.ndarray, n_points: int, max_dimension: int):
+    """Delaunay cells (Qhull or the native triangulations) -> (array-backed ``SimplexTree``, its simplices bucketed by
+    dimension): the face tables up to ``max_dimension`` now, the higher ones when somebody asks for them."""
+    stree = SimplexTree.from_cells(cells, n_points, eager=max_dimension, trusted=True)
+    return stree, [stree.simplices_of_dimension(d) for d in range(max_dimension + 1)]
 
 
 def _ball_prep(simplex_vertices: torch.Tensor, d: int):
@@ -1704,6 +1708,164 @@ def _face_max_cpu(dist: torch.Tensor, faces: _FaceTable) -> torch.Tensor:
     return torch.as_tensor(out)
 
 
+def _robust_stat(dist_k: np.ndarray, k: int, stat: str) -> np.ndarray:
+    """The robust filtration's statistic of the (..., k) ascending distances a kd-tree query with ``k=`` returns:
+    the k-th (``"kth"``) or the root mean square (``"dtm"``)."""
+    if stat == "kth":
+        return dist_k[..., -1]
+    return np.sqrt(np.square(dist_k.astype(np.float64)).sum(axis=-1) / k)
+
+
+def _widest_axis(points: torch.Tensor, box: Optional[torch.Tensor] = None) -> int:
+    """Widest axis of the cloud (core.py:140-144): sort key of the reference, work order of the simplices here.  From
+    ``box`` (16 floats on the device, ``cloud_box`` / ``PointIndex.box``) for ROCm tensors, else from CPU ``points``."""
+    if box is None:
+        return int(torch.argmax(points.max(dim=0).values - points.min(dim=0).values).item())
+    box, dim = box.cpu(), points.shape[1]
+    return int(torch.argmax(box[8:8 + dim] - box[:dim]).item())
+
+
+def _check_index(index, points: torch.Tensor, applies: bool, applies_to: str) -> None:
+    """``index=``: a PointIndex of these very points, not written to since (``applies``: whether this call can use
+    one at all; ``applies_to`` words the refusal)."""
+    if not applies:
+        raise ValueError(f"index= applies to {applies_to}")
+    if not isinstance(index, PointIndex) or (index.n, index.dim) != tuple(points.shape) or index.pts.device != points.device:
+        raise ValueError("index= is not a PointIndex of these points (shape or device differ)")
+    src = getattr(index, "source", None)
+    ver = _tensor_version(points)
+    if src is not None and src[0] == points.data_ptr() and src[1] is not None and ver is not None and src[1] != ver:
+        raise ValueError("index= was built from an earlier state of `points` (the tensor has been modified in "
+                         "place since): rebuild the PointIndex")
+
+
+def _check_landmarks(landmarks: torch.Tensor, points: torch.Tensor) -> None:
+    if landmarks.device != points.device:
+        raise RuntimeError(f"landmarks.device ({landmarks.device}) != points.device ({points.device})")
+    if landmarks.dtype != points.dtype:
+        raise RuntimeError(f"landmarks.dtype ({landmarks.dtype}) != points.dtype ({points.dtype})")
+
+
+# ------------------------------------------------------------------------------ dimension passes and hand-off
+class DimensionPass(NamedTuple):
+    """One swept dimension of a call: the simplex queue and the sample tables."""
+    d: int
+    order_np: np.ndarray                     # (S,) queue position -> row of the dimension-d table
+    simp_h: np.ndarray                       # (S, d+1) the table rows in queue order
+    verts: torch.Tensor                      # (S, d+1, dim) their vertices, on the landmarks' device
+    weights: torch.Tensor                    # (R, d+1) barycentric samples, in the landmarks' dtype
+    faces: _FaceTable
+    plan: Optional["SamplePlan"]             # grid tables on ROCm float32; None: the sweep makes its own, or needs none
+    v_idx_np: Optional[List[np.ndarray]]     # per codimension the (nf, k) vertex positions of the faces; None: random
+    centers: Optional[torch.Tensor] = None   # ball queue only: the bounding balls, in queue order
+    radii: Optional[torch.Tensor] = None
+
+
+def _dimension_passes(simplices: List[np.ndarray], lm: torch.Tensor, axis: int, points_per_edge, num_rand, queue: str):
+    """The dimension passes of a call, ascending: every dimension with ``num_rand``, the top one of a grid; empty
+    tables are skipped before a weight is drawn (``generate_uniform_weights`` consumes the global CPU generator: one
+    draw per pass, in this order).  ``lm``: the landmarks in the dtype of the sweep (weights and vertices take it).
+    ``queue="tree"`` (the culled device sweeps need no bounding balls): along the widest axis by the vertex sum, on a
+    host copy of the landmarks, so that nothing waits for the device and the vertices are uploaded once;
+    ``queue="ball"`` (CPU tensors, ``method="ball"``): by the centre of the reference's bounding ball."""
+    top = len(simplices) - 1
+    device, dtype = lm.device, lm.dtype
+    lm_np = lm.cpu().numpy() if queue == "tree" else None
+    for d, table in enumerate(simplices):
+        if (num_rand is None and d < top) or table.shape[0] == 0:
+            continue
+        centers = radii = None
+        if queue == "tree":
+            v_np = lm_np[table]
+            # (by the vertex sum along that axis alone: the mean over all axes first was 0.4 ms of a 6.8 ms call at cfg 2)
+            order_np = np.argsort(v_np[:, :, axis].sum(axis=1), kind="stable")
+            verts = torch.as_tensor(np.ascontiguousarray(v_np[order_np]), device=device)
+        else:
+            verts = lm[torch.as_tensor(table, device=device)]
+            centers, radii = _ball_prep(verts, d)
+            by_centre = torch.argsort(centers[:, axis])
+            verts, centers, radii = verts[by_centre], centers[by_centre], radii[by_centre]
+            order_np = by_centre.cpu().numpy()
+        if num_rand is None:
+            weights, _, _, faces, plan, v_idx_np = _grid_tables(points_per_edge, top, device, dtype)
+            if dtype is torch.float64:   # (the float64 device sweep takes no plan)
+                plan = None
+        else:
+            weights = generate_uniform_weights(num_rand, d, device, dtype)
+            faces, plan, v_idx_np = _FaceTable(None, weights.shape[0], device), None, None
+        yield DimensionPass(d, order_np, table[order_np], verts, weights, faces, plan, v_idx_np, centers, radii)
+
+
+def _face_rows(stree, p: DimensionPass, v_idx: np.ndarray):
+    """Where face j (vertex positions ``v_idx[j]``; ``v_idx`` (nf, k)) of queue simplex s sits in the dimension k-1
+    table, by the cheapest means the tree has: ``("cells", columns of cell_face_index(k - 1))`` when the swept simplices
+    are the top cells of the complex (no search); ``("rows", (S * nf,) rows)`` where the rows are known outright - the
+    swept simplices themselves, the vertices of a complex built from cells (row = vertex id); else
+    ``("bulk", (S * nf, k) vertex ids)``, to be located by key (any gudhi tree)."""
+    nf, k = v_idx.shape
+    own = isinstance(stree, SimplexTree)
+    if own and stree._cells is not None and stree._cells.shape[1] == p.d + 1 and stree.cell_face_index(k - 1) is not None:
+        combos = list(itertools.combinations(range(p.d + 1), k))
+        return "cells", [combos.index(tuple(int(x) for x in row)) for row in v_idx]
+    if own and k == p.d + 1 and nf == 1:
+        return "rows", p.order_np
+    if own and k == 1 and stree._cells is not None:
+        return "rows", p.simp_h[:, v_idx].reshape(-1)
+    return "bulk", p.simp_h[:, v_idx].reshape(-1, k)
+
+
+def _face_table_rows(stree: SimplexTree, p: DimensionPass, v_idx: np.ndarray) -> np.ndarray:
+    """``_face_rows`` resolved: the (S, nf) rows of the dimension k-1 table (-1: not in the complex)."""
+    nf, k = v_idx.shape
+    kind, where = _face_rows(stree, p, v_idx)
+    if kind == "cells":
+        return stree.cell_face_index(k - 1)[p.order_np][:, where]
+    return (stree._locate(k - 1, where) if kind == "bulk" else where).reshape(-1, nf)
+
+
+def _handoff_items(stree, p: DimensionPass, face_vals: np.ndarray, slot_offsets=None) -> List[tuple]:
+    """The face values of one dimension pass as assignments ``(kind, dimension, where, values)``, in update order
+    (later rows win, as a dict update does; core.py:258-270).  ``face_vals``: (S, F), a column per face of the face
+    table - or, with ``slot_offsets`` (``shared_face_slots``), one value per distinct face of the complex, which go
+    straight into the tables: ``"table"`` (``where`` None).  The others are ``_face_rows``'s: ``"cells"`` (``where`` =
+    (cell rows, face columns)), ``"rows"`` (table rows) and ``"bulk"`` (vertex ids; random samples: one face, the
+    simplex itself)."""
+    if slot_offsets is not None:
+        return [("table", v_idx.shape[1] - 1, None,
+                 face_vals[off:off + stree.simplices_of_dimension(v_idx.shape[1] - 1).shape[0]])
+                for v_idx, off in zip(p.v_idx_np, slot_offsets)]
+    if p.v_idx_np is None:
+        return [("bulk", p.d, p.simp_h, face_vals[:, 0])]
+    items, col = [], 0
+    for v_idx in p.v_idx_np:
+        nf, k = v_idx.shape
+        kind, where = _face_rows(stree, p, v_idx)
+        vals_k = face_vals[:, col:col + nf]
+        col += nf
+        items.append((kind, k - 1, (p.order_np, where), vals_k) if kind == "cells"
+                     else (kind, k - 1, where, vals_k.reshape(-1)))
+    return items
+
+
+def _apply_items(stree, items: List[tuple]) -> None:
+    """Hand-off (core.py:278-288): the assignments of ``_handoff_items`` onto a simplex tree, in their order."""
+    if not isinstance(stree, SimplexTree):  # a gudhi tree (core.py:278-280 of the reference): every item is "bulk"
+        for _, _, simp, vals in items:
+            for s, v in zip(simp.tolist(), vals.tolist()):
+                stree.assign_filtration(s, v)
+        return
+    for kind, dim, where, vals in items:
+        if kind == "table":
+            stree.filtrations_of_dimension(dim)[:] = vals
+        elif kind == "rows":
+            stree.filtrations_of_dimension(dim)[where] = vals
+        elif kind == "cells":
+            stree.assign_cell_faces(dim, where[0], where[1], vals)
+        else:
+            stree.assign_filtration_bulk(where, vals)
+    stree._persistence = None
+
+
 def flood_complex(
     points: torch.Tensor,
     landmarks: Union[int, torch.Tensor],
@@ -1822,15 +1984,7 @@ def flood_complex(
         max_dimension = points.shape[1]
     shared_index = None  # one curve-sorted copy of the cloud serves the landmark selection and the sweep
     if index is not None:
-        if not points.is_cuda or method == "ball":
-            raise ValueError("index= applies to ROCm tensors with method 'cell' or 'bvh'")
-        if not isinstance(index, PointIndex) or (index.n, index.dim) != tuple(points.shape) or index.pts.device != points.device:
-            raise ValueError("index= is not a PointIndex of these points (shape or device differ)")
-        src = getattr(index, "source", None)
-        ver = _tensor_version(points)
-        if src is not None and src[0] == points.data_ptr() and src[1] is not None and ver is not None and src[1] != ver:
-            raise ValueError("index= was built from an earlier state of `points` (the tensor has been modified in "
-                             "place since): rebuild the PointIndex")
+        _check_index(index, points, points.is_cuda and method != "ball", "ROCm tensors with method 'cell' or 'bvh'")
         shared_index = index
     if isinstance(landmarks, Integral):
         if (shared_index is None and points.is_cuda and method != "ball" and points.shape[1] <= FPS_BUCKET_MAX_DIM and points.dtype in SUPPORTED_DTYPES
@@ -1841,10 +1995,7 @@ def flood_complex(
                 _remember_index(points, shared_index)
         landmarks = generate_landmarks(points, min(landmarks, points.shape[0]), fps_h, start_idx=start_idx,
                                        index=shared_index)
-    if landmarks.device != points.device:
-        raise RuntimeError(f"landmarks.device ({landmarks.device}) != points.device ({points.device})")
-    if landmarks.dtype != points.dtype:
-        raise RuntimeError(f"landmarks.dtype ({landmarks.dtype}) != points.dtype ({points.dtype})")
+    _check_landmarks(landmarks, points)
     device = points.device
     dtype = points.dtype
     if dtype not in SUPPORTED_DTYPES:
@@ -1906,63 +2057,24 @@ def flood_complex(
     LAST_STATS.reset()
     LAST_STATS.n_points = points.shape[0]
 
-    # widest axis of the cloud (core.py:140-144): sort key of the reference, work order of the simplices here
     if sort_axis is not None:
         axis = int(sort_axis)
-    elif on_gpu:
-        box = (block_box if block_box is not None else (index.box if index is not None else cloud_box(points))).cpu()
-        axis = int(torch.argmax(box[8:8 + dim] - box[:dim]).item())
     else:
-        axis = int(torch.argmax(points.max(dim=0).values - points.min(dim=0).values).item())
+        axis = _widest_axis(points, None if not on_gpu else block_box if block_box is not None
+                            else index.box if index is not None else cloud_box(points))
     if on_gpu:
         pts32 = points.to(torch.float32)
-        dp = _native.load().flooder_padded_dim(dim)
-        lm32 = landmarks.to(torch.float32)
         if method == "ball":  # the reference's formulation: cloud sorted along the widest axis (core.py:140-144)
-            pts_pad = _pad_rows(pts32[torch.argsort(pts32[:, axis])], dp)
+            pts_pad = _pad_rows(pts32[torch.argsort(pts32[:, axis])], _native.load().flooder_padded_dim(dim))
             search = pts_pad[:, axis].contiguous()
-    lm_np = landmarks.detach().to(torch.float64 if use_f64 else (torch.float32 if on_gpu else dtype)).cpu().numpy()
+    lm = landmarks.detach().to(torch.float64 if use_f64 else (torch.float32 if on_gpu else dtype))
 
-    results: List[tuple] = []  # (simplices (n,k), values (n,)) or indexed cell-face assignments, in update order
+    results: List[tuple] = []  # hand-off items of every pass, in update order
     peak_ws = 0
-    for d in range(max_dimension + 1):
-        if num_rand is None and d < max_dimension:
-            continue
-        num_simplices = simplices[d].shape[0]
-        if num_simplices == 0:
-            continue
-        plan = None
-        centers = radii = None
-        if on_gpu and method != "ball":
-            # the culled sweeps need no bounding balls; the simplices are queued along the widest axis (any order
-            # gives the same values), prepared on the host so that nothing here waits for the device
-            v_np = lm_np[simplices[d]]
-            # (by the vertex sum along that axis alone: the mean over all axes first was 0.4 ms of a 6.8 ms call at cfg 2)
-            order_np = np.argsort(v_np[:, :, axis].sum(axis=1), kind="stable")
-            simp_h = simplices[d][order_np]
-            simplex_vertices = torch.as_tensor(np.ascontiguousarray(v_np[order_np]), device=device)
-        else:
-            d_simplices = torch.as_tensor(simplices[d], device=device)
-            lm = lm32 if on_gpu else landmarks
-            simplex_vertices = lm[d_simplices]
-            centers, radii = _ball_prep(simplex_vertices, d)
-            splx_idx = torch.argsort(centers[:, axis])
-            simplex_vertices = simplex_vertices[splx_idx]
-            centers = centers[splx_idx]
-            radii = radii[splx_idx]
-            order_np = splx_idx.cpu().numpy()
-            simp_h = simplices[d][order_np]
-
-        w_dtype = torch.float64 if use_f64 else (torch.float32 if on_gpu else dtype)
-        if num_rand is None:
-            weights, vertex_idxs, face_idxs, faces, plan, v_idx_np = _grid_tables(
-                points_per_edge, max_dimension, device, w_dtype)
-            if use_f64:
-                plan = None
-        else:
-            weights = generate_uniform_weights(num_rand, d, device, w_dtype)
-            vertex_idxs = face_idxs = v_idx_np = None
-            faces = _FaceTable(None, weights.shape[0], device)
+    for p in _dimension_passes(simplices, lm, axis, points_per_edge, num_rand,
+                               "tree" if on_gpu and method != "ball" else "ball"):
+        d, order_np, weights, faces, plan = p.d, p.order_np, p.weights, p.faces, p.plan
+        num_simplices = order_np.shape[0]
         LAST_STATS.top_simplices = num_simplices
         LAST_STATS.samples_per_simplex = weights.shape[0]
         # (rough device workspace of this pass: 4 B per sample, 24 with the sorted-sample sweep's keys and orders)
@@ -1980,10 +2092,10 @@ def flood_complex(
                 mine = None          # all simplices, a contiguous run of the TILES of the sorted sample order
                 tile_shard = (sh_rank, sh_world)
             else:
-                mine = torch.as_tensor(simplex_share(simplex_vertices, sh_rank, sh_world), device=device)
+                mine = torch.as_tensor(simplex_share(p.verts, sh_rank, sh_world), device=device)
         else:
             mine = None
-        sv = simplex_vertices if mine is None else simplex_vertices[mine]
+        sv = p.verts if mine is None else p.verts[mine]
         if blocks and sv.shape[0] > 0:
             index = PointIndex(block_subcloud(pts32, sv, d, box=block_box))
         # one running maximum per DISTINCT face of the complex (the simplices that share a triangle / an edge / a vertex
@@ -1993,7 +2105,7 @@ def flood_complex(
         slots = None
         if (on_gpu and method == "cell" and not use_f64 and SHARED_FACE_SLOTS and FUSED_FACES and num_rand is None
                 and reduce_hook is None and faces.n_faces <= 32):
-            slots = shared_face_slots(stree, d, order_np if mine is None else order_np[mine.cpu().numpy()], v_idx_np,
+            slots = shared_face_slots(stree, d, order_np if mine is None else order_np[mine.cpu().numpy()], p.v_idx_np,
                                       device)
         if on_gpu and sv.shape[0] == 0 and (blocks or slots is not None):   # (more ranks than simplices)
             face_dev = (torch.full((slots[1],), float("inf"), dtype=torch.float32, device=device) if slots is not None
@@ -2006,8 +2118,8 @@ def flood_complex(
         elif on_gpu:
             if method == "ball":
                 face_dev, _ = _sweep_dimension_hip(pts_pad, search, axis, dim, sv,
-                                                   centers if mine is None else centers[mine],
-                                                   radii if mine is None else radii[mine], weights, faces,
+                                                   p.centers if mine is None else p.centers[mine],
+                                                   p.radii if mine is None else p.radii[mine], weights, faces,
                                                    reduce_hook)
             elif use_f64:
                 face_dev, _ = _sweep_dimension_f64(index, pts64_sorted, sv, weights, faces, reduce_hook)
@@ -2019,11 +2131,8 @@ def flood_complex(
         elif neighbors > 1:
             samples = weights.unsqueeze(0) @ sv
             dist, _ = kdtree.query(np.asarray(samples), k=neighbors, workers=CPU_WORKERS)   # (S, R, k), ascending
-            if neighbor_stat == "kth":
-                dist = dist[..., -1]
-            else:
-                dist = np.sqrt(np.square(dist.astype(np.float64)).sum(axis=-1) / neighbors)
-            face_dev = _face_max_cpu(torch.as_tensor(np.ascontiguousarray(dist)), faces)
+            face_dev = _face_max_cpu(torch.as_tensor(np.ascontiguousarray(_robust_stat(dist, neighbors, neighbor_stat))),
+                                     faces)
         else:
             samples = weights.unsqueeze(0) @ sv
             # (the reference queries with scipy's default of ONE worker, core.py:198; the distances do not depend on
@@ -2059,53 +2168,9 @@ def flood_complex(
             face_dev = -neg
         face_vals = face_dev.cpu().numpy().astype(np.float64)
 
-        if on_gpu and method == "cell" and slots is not None:
-            # one value per distinct face: straight into the tables
-            for v_idx, off in zip(v_idx_np, slots[2]):
-                k = v_idx.shape[1]
-                n_rows = stree.simplices_of_dimension(k - 1).shape[0]
-                results.append(("table", k - 1, face_vals[off:off + n_rows]))
-        elif num_rand is None:
-            # faces of the swept simplices.  When those are the top cells of the complex, the rows of the face tables
-            # are known from the enumeration of the faces (no search); else located by key.
-            top_cells = isinstance(stree, SimplexTree) and stree._cells is not None and stree._cells.shape[1] == d + 1
-            col = 0
-            for v_idx in v_idx_np:
-                nf, k = v_idx.shape
-                vals_k = face_vals[:, col:col + nf]
-                col += nf
-                if top_cells and stree.cell_face_index(k - 1) is not None:
-                    combos = list(itertools.combinations(range(d + 1), k))
-                    results.append(("cells", k - 1, order_np, [combos.index(tuple(int(x) for x in row)) for row in v_idx],
-                                    vals_k))
-                elif isinstance(stree, SimplexTree) and k == d + 1 and nf == 1:
-                    # the swept simplices themselves: simp_h is the dimension-d table in queue order
-                    results.append(("rows", d, order_np, vals_k.reshape(-1)))
-                elif isinstance(stree, SimplexTree) and k == 1 and stree._cells is not None:
-                    # vertices of a complex built from cells: row = vertex id (later rows win, as a dict update does)
-                    results.append(("rows", 0, simp_h[:, v_idx].reshape(-1), vals_k.reshape(-1)))
-                else:
-                    results.append((simp_h[:, v_idx].reshape(-1, k), vals_k.reshape(-1)))
-        else:
-            results.append((simp_h, face_vals[:, 0]))
+        results += _handoff_items(stree, p, face_vals, None if slots is None else slots[2])
 
-    # hand-off (core.py:278-288)
-    if isinstance(stree, SimplexTree):
-        for item in results:
-            if isinstance(item[0], str) and item[0] == "table":
-                stree._vals[item[1]][:] = item[2]
-                stree._persistence = None
-            elif isinstance(item[0], str) and item[0] == "rows":
-                stree.filtrations_of_dimension(item[1])[item[2]] = item[3]
-                stree._persistence = None
-            elif isinstance(item[0], str):
-                stree.assign_cell_faces(item[1], item[2], item[3], item[4])
-            else:
-                stree.assign_filtration_bulk(item[0], item[1])
-    else:  # a gudhi tree (core.py:278-280 of the reference)
-        for simp, vals in results:
-            for s, v in zip(simp.tolist(), vals.tolist()):
-                stree.assign_filtration(s, v)
+    _apply_items(stree, results)
     stree.make_filtration_non_decreasing()
     # (asking the allocator costs 0.2 ms of a 10 ms call: only after a call that can have left that much behind)
     if (on_gpu and peak_ws > EMPTY_CACHE_ABOVE_BYTES // 4

@@ -20,7 +20,6 @@ df/dpoints[id_(i)] = -(p* - x_(i)) / (k f), df/dL_j = w*_j (p* - mean x) / f.
 from __future__ import annotations
 
 import ctypes
-import itertools
 from numbers import Integral
 from typing import Dict, List, Optional
 
@@ -117,20 +116,6 @@ def _check_args(points: torch.Tensor, method: Optional[str]):
     return method
 
 
-def _check_index(index: "core.PointIndex", points: torch.Tensor) -> None:
-    """The checks ``flood_complex(index=...)`` makes: a PointIndex of these very points, not written to since."""
-    if not points.is_cuda:
-        raise ValueError("index= applies to ROCm tensors")
-    if (not isinstance(index, core.PointIndex) or (index.n, index.dim) != tuple(points.shape)
-            or index.pts.device != points.device):
-        raise ValueError("index= is not a PointIndex of these points (shape or device differ)")
-    src = getattr(index, "source", None)
-    ver = core._tensor_version(points)
-    if src is not None and src[0] == points.data_ptr() and src[1] is not None and ver is not None and src[1] != ver:
-        raise ValueError("index= was built from an earlier state of `points` (the tensor has been modified in "
-                         "place since): rebuild the PointIndex")
-
-
 def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[int] = None, points_per_edge: int = 30,
                      num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, method: Optional[str] = None,
                      index: Optional["core.PointIndex"] = None, neighbors: int = 1,
@@ -154,7 +139,7 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
     neighbors, method = core._check_neighbors(points, neighbors, neighbor_stat, method)
     method = _check_args(points, method)
     if index is not None:
-        _check_index(index, points)
+        core._check_index(index, points, points.is_cuda, "ROCm tensors")
     dim = points.shape[1]
     if max_dimension is None:
         max_dimension = dim
@@ -172,17 +157,13 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
                 index = core.PointIndex(points.detach().to(torch.float32))
             landmark_ids = core.fps_indices(points.detach(), min(n_l, points.shape[0]), start_idx, index=index)
         landmarks = points.index_select(0, landmark_ids)
-    if landmarks.device != points.device:
-        raise RuntimeError(f"landmarks.device ({landmarks.device}) != points.device ({points.device})")
-    if landmarks.dtype != points.dtype:
-        raise RuntimeError(f"landmarks.dtype ({landmarks.dtype}) != points.dtype ({points.dtype})")
+    core._check_landmarks(landmarks, points)
 
     with torch.no_grad():
         pts = points.detach()
         lms = landmarks.detach()
         lm_np = lms.cpu().numpy()
-        tree = SimplexTree.from_cells(delaunay_cells(lm_np), lm_np.shape[0], eager=max_dimension, trusted=True)
-        simplices = [tree.simplices_of_dimension(d) for d in range(max_dimension + 1)]
+        tree, simplices = core._cell_complex(delaunay_cells(lm_np), lm_np.shape[0], max_dimension)
         n_dims = max_dimension + 1
         own_val = [np.full(s.shape[0], np.nan) for s in simplices]
         own_pt = [np.full(s.shape[0], -1, dtype=np.int64) for s in simplices]
@@ -192,10 +173,10 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
         knn = (neighbors, neighbor_stat, own_nb) if neighbors > 1 else None
         not_found = 0
         if points.is_cuda:
-            not_found = _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index,
+            not_found = _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, index,
                                    own_val, own_pt, own_w, knn)
         else:
-            _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w, knn)
+            _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn)
         for d in range(n_dims):
             vals = tree.filtrations_of_dimension(d)
             if vals.shape[0]:
@@ -221,27 +202,12 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
 
 
 # ---------------------------------------------------------------------------------------------------- the sweeps
-def _table_rows(tree: SimplexTree, d: int, order_np: np.ndarray, simp_h: np.ndarray, v_idx: np.ndarray) -> np.ndarray:
-    """(S, nf) rows of the dimension k-1 table holding face j (vertex positions ``v_idx[j]``) of queue simplex s."""
-    nf, k = v_idx.shape
-    top = tree._cells is not None and tree._cells.shape[1] == d + 1
-    index = tree.cell_face_index(k - 1) if top else None
-    if index is not None:
-        combos = list(itertools.combinations(range(d + 1), k))
-        pick = [combos.index(tuple(int(x) for x in row)) for row in v_idx]
-        return index[order_np][:, pick]
-    if k == d + 1 and nf == 1:
-        return order_np.reshape(-1, 1)
-    rows = tree._locate(k - 1, simp_h[:, v_idx].reshape(-1, k))
-    return rows.reshape(-1, nf)
-
-
-def _face_groups(v_idx_np):
-    """[(first column of the group in the face table, v_idx)] of a grid table; None = random samples (one face)."""
-    if v_idx_np is None:
-        return None
+def _face_groups(p: "core.DimensionPass"):
+    """[(first column of the group in the face table, v_idx)] of a pass; random samples: one face, the simplex itself."""
+    if p.v_idx_np is None:
+        return [(0, np.arange(p.d + 1, dtype=np.int64).reshape(1, -1))]
     out, col = [], 0
-    for v_idx in v_idx_np:
+    for v_idx in p.v_idx_np:
         out.append((col, v_idx))
         col += v_idx.shape[0]
     return out
@@ -280,37 +246,21 @@ def _grad_face_rows(plan: "core.SamplePlan"):
     return got
 
 
-def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, method, index, own_val, own_pt, own_w,
-               knn=None):
+def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, index, own_val, own_pt, own_w, knn=None):
     lib = _native.load()
     dev = pts.device
     torch.cuda.set_device(dev)
     pts32 = pts.to(torch.float32).contiguous()
     if index is None:
         index = core.PointIndex(pts32)
-    box = index.box.cpu()
     dim = pts.shape[1]
-    axis = int(torch.argmax(box[8:8 + dim] - box[:dim]).item())
-    lm_np = lms.to(torch.float32).cpu().numpy()
+    axis = core._widest_axis(pts, index.box)
     st = _native.current_stream_ptr(dev)
     not_found = torch.zeros(1, dtype=torch.int32, device=dev)
-    for d in range(max_dimension + 1):
-        if num_rand is None and d < max_dimension:
-            continue
-        S = simplices[d].shape[0]
-        if S == 0:
-            continue
-        v_np = lm_np[simplices[d]]
-        order_np = np.argsort(v_np[:, :, axis].sum(axis=1), kind="stable")
-        simp_h = simplices[d][order_np]
-        sv = torch.as_tensor(np.ascontiguousarray(v_np[order_np]), device=dev)
-        if num_rand is None:
-            weights, _, _, faces, plan, v_idx_np = core._grid_tables(points_per_edge, max_dimension, dev, torch.float32)
-        else:
-            weights = core.generate_uniform_weights(num_rand, d, dev, torch.float32)
-            faces = core._FaceTable(None, weights.shape[0], dev)
-            plan, v_idx_np = core.SamplePlan(weights, faces), None
-        R = weights.shape[0]
+    for p in core._dimension_passes(simplices, lms.to(torch.float32), axis, points_per_edge, num_rand, "tree"):
+        d, sv, weights, faces = p.d, p.verts, p.weights, p.faces
+        plan = p.plan if p.plan is not None else core.SamplePlan(weights, faces)   # (random samples: the gather below needs it)
+        S, R = sv.shape[0], weights.shape[0]
         got = []
         if knn is not None:    # (S, R) bits of the squared statistic instead of the minimum d2
             face_dev, _ = core._sweep_dimension_knn(index, sv, weights, faces, knn[0], knn[1], plan=plan, keep=got.append)
@@ -324,10 +274,9 @@ def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
         _native.check(lib.flooder_face_argmax_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr), _native.ptr(face_rows),
                                                   _native.ptr(row_id), F, _native.ptr(keys), st),
                       "flooder_face_argmax_f32")
-        groups = _face_groups(v_idx_np) or [(0, np.arange(d + 1, dtype=np.int64).reshape(1, -1))]
-        for col, v_idx in groups:
+        for col, v_idx in _face_groups(p):
             nf, k = v_idx.shape
-            rows_np = _table_rows(tree, d, order_np, simp_h, v_idx)
+            rows_np = core._face_table_rows(tree, p, v_idx)
             n_rows = simplices[k - 1].shape[0]
             rows = torch.as_tensor(np.ascontiguousarray(rows_np, dtype=np.int64), device=dev).reshape(-1)
             key = keys[:, col:col + nf].reshape(-1)
@@ -379,48 +328,25 @@ def _sweep_gpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_ra
     return missing
 
 
-def _sweep_cpu(pts, lms, tree, simplices, max_dimension, points_per_edge, num_rand, own_val, own_pt, own_w, knn=None):
+def _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn=None):
     from scipy.spatial import KDTree
 
     kdtree = KDTree(np.asarray(pts))
-    axis = int(torch.argmax(pts.max(dim=0).values - pts.min(dim=0).values).item())
-    dtype = pts.dtype
-    for d in range(max_dimension + 1):
-        if num_rand is None and d < max_dimension:
-            continue
-        S = simplices[d].shape[0]
-        if S == 0:
-            continue
-        # the queue of flood_complex's CPU branch (same samples, bit for bit)
-        sv = lms[torch.as_tensor(simplices[d])]
-        centers, _ = core._ball_prep(sv, d)
-        splx_idx = torch.argsort(centers[:, axis])
-        sv = sv[splx_idx]
-        order_np = splx_idx.numpy()
-        simp_h = simplices[d][order_np]
-        if num_rand is None:
-            weights, _, _, faces, _, v_idx_np = core._grid_tables(points_per_edge, max_dimension, pts.device, dtype)
-        else:
-            weights = core.generate_uniform_weights(num_rand, d, pts.device, dtype)
-            faces = core._FaceTable(None, weights.shape[0], pts.device)
-            v_idx_np = None
-        samples = weights.unsqueeze(0) @ sv
-        if knn is not None:   # the statistic as flood_complex's CPU branch computes it
+    for p in core._dimension_passes(simplices, lms, core._widest_axis(pts), points_per_edge, num_rand, "ball"):
+        weights, faces, S = p.weights, p.faces, p.verts.shape[0]
+        samples = weights.unsqueeze(0) @ p.verts
+        if knn is not None:
             dist_k, idx_k = kdtree.query(np.asarray(samples), k=knn[0], workers=core.CPU_WORKERS)   # (S, R, k), ascending
-            if knn[1] == "kth":
-                dist = dist_k[..., -1]
-            else:
-                dist = np.sqrt(np.square(dist_k.astype(np.float64)).sum(axis=-1) / knn[0])
+            dist = core._robust_stat(dist_k, knn[0], knn[1])
             idx = idx_k[..., -1]
         else:
             dist, idx = kdtree.query(np.asarray(samples), workers=core.CPU_WORKERS)
         fptr = faces.ptr.numpy()
         frows = faces.rows.numpy()
         w_np = weights.numpy()
-        groups = _face_groups(v_idx_np) or [(0, np.arange(d + 1, dtype=np.int64).reshape(1, -1))]
-        for col, v_idx in groups:
+        for col, v_idx in _face_groups(p):
             nf, k = v_idx.shape
-            rows = _table_rows(tree, d, order_np, simp_h, v_idx).reshape(-1)
+            rows = core._face_table_rows(tree, p, v_idx).reshape(-1)
             arg = np.empty((S, nf), dtype=np.int64)
             val = np.empty((S, nf))
             for j in range(nf):

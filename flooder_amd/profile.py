@@ -15,7 +15,6 @@ not part of this function (``flood_complex`` / ``flood_filtration`` with one k h
 from __future__ import annotations
 
 import copy
-import itertools
 from numbers import Integral
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -23,7 +22,6 @@ import numpy as np
 import torch
 
 from . import _native, core
-from .grad import _check_index
 from .simplex_tree import SimplexTree, delaunay_cells
 
 Column = Tuple[int, str]
@@ -174,7 +172,7 @@ def flood_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], max
     if max_dimension is None:
         max_dimension = dim
     if index is not None:
-        _check_index(index, points)
+        core._check_index(index, points, on_gpu, "ROCm tensors")
     if on_gpu:
         _native.load()   # raises ImportError with the build hint: no fallback
         torch.cuda.set_device(points.device)
@@ -186,125 +184,37 @@ def flood_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], max
     if isinstance(landmarks, Integral):
         landmarks = core.generate_landmarks(points, min(int(landmarks), points.shape[0]), None, start_idx=start_idx,
                                             index=index)
-    if landmarks.device != points.device:
-        raise RuntimeError(f"landmarks.device ({landmarks.device}) != points.device ({points.device})")
-    if landmarks.dtype != points.dtype:
-        raise RuntimeError(f"landmarks.dtype ({landmarks.dtype}) != points.dtype ({points.dtype})")
+    core._check_landmarks(landmarks, points)
 
     lm_host = landmarks.detach().cpu().numpy()
-    tree = SimplexTree.from_cells(delaunay_cells(lm_host), lm_host.shape[0], eager=max_dimension, trusted=True)
-    simplices = [tree.simplices_of_dimension(d) for d in range(max_dimension + 1)]
-    sweep = _sweep_gpu if on_gpu else _sweep_cpu
-    # per dimension pass: (hand-off items of flood_complex, one list per column)
-    passes = sweep(points, landmarks, tree, simplices, max_dimension, points_per_edge, num_rand, index, columns)
+    tree, simplices = core._cell_complex(delaunay_cells(lm_host), lm_host.shape[0], max_dimension)
+    # per column: the hand-off items of flood_complex, pass after pass
+    items = [[] for _ in columns]
+    if on_gpu:
+        passes = core._dimension_passes(simplices, landmarks.detach().to(torch.float32), core._widest_axis(points, index.box),
+                                        points_per_edge, num_rand, "tree")
+    else:
+        from scipy.spatial import KDTree
+
+        kdtree = KDTree(np.asarray(points))
+        k_max = max(ks)
+        passes = core._dimension_passes(simplices, landmarks.detach(), core._widest_axis(points), points_per_edge,
+                                        num_rand, "ball")
+    for p in passes:
+        if on_gpu:
+            face_cols = core._sweep_dimension_knn_profile(index, p.verts, p.weights, p.faces, columns, plan=p.plan)
+        else:
+            samples = p.weights.unsqueeze(0) @ p.verts
+            dist_all, _ = kdtree.query(np.asarray(samples), k=k_max, workers=core.CPU_WORKERS)   # (S, R, k_max), ascending
+            # (scipy's k' nearest are the first k' of its k_max)
+            face_cols = [core._face_max_cpu(torch.as_tensor(np.ascontiguousarray(
+                dist_all[..., 0] if k == 1 else core._robust_stat(dist_all[..., :k], k, stat))), p.faces)
+                for k, stat in columns]
+        for c, face in enumerate(face_cols):
+            items[c] += core._handoff_items(tree, p, face.cpu().numpy().astype(np.float64))
     trees = []
     for c in range(len(columns)):
-        t = _clone_tree(tree)
-        for items in passes:
-            for item in items[c]:
-                if item[0] == "rows":
-                    t.filtrations_of_dimension(item[1])[item[2]] = item[3]
-                elif item[0] == "cells":
-                    t.assign_cell_faces(item[1], item[2], item[3], item[4])
-                else:
-                    t.assign_filtration_bulk(item[1], item[2])
-        t._persistence = None
-        t.make_filtration_non_decreasing()
-        trees.append(t)
+        trees.append(_clone_tree(tree))
+        core._apply_items(trees[c], items[c])
+        trees[c].make_filtration_non_decreasing()
     return FloodProfile(columns, trees, None, return_simplex_tree)
-
-
-def _handoff(tree: SimplexTree, d: int, num_rand, order_np, simp_h, v_idx_np, face_vals: np.ndarray) -> list:
-    """The (S, F) face values of one dimension pass as the assignments ``flood_complex`` makes from them, in its order."""
-    if num_rand is not None:
-        return [("bulk", simp_h, face_vals[:, 0])]
-    items = []
-    top_cells = tree._cells is not None and tree._cells.shape[1] == d + 1
-    col = 0
-    for v_idx in v_idx_np:
-        nf, k = v_idx.shape
-        vals_k = face_vals[:, col:col + nf]
-        col += nf
-        if top_cells and tree.cell_face_index(k - 1) is not None:
-            combos = list(itertools.combinations(range(d + 1), k))
-            items.append(("cells", k - 1, order_np, [combos.index(tuple(int(x) for x in row)) for row in v_idx], vals_k))
-        elif k == d + 1 and nf == 1:
-            items.append(("rows", d, order_np, vals_k.reshape(-1)))
-        elif k == 1 and tree._cells is not None:
-            items.append(("rows", 0, simp_h[:, v_idx].reshape(-1), vals_k.reshape(-1)))
-        else:
-            items.append(("bulk", simp_h[:, v_idx].reshape(-1, k), vals_k.reshape(-1)))
-    return items
-
-
-def _sweep_gpu(points, landmarks, tree, simplices, max_dimension, points_per_edge, num_rand, index, columns):
-    dev = points.device
-    dim = points.shape[1]
-    box = index.box.cpu()
-    axis = int(torch.argmax(box[8:8 + dim] - box[:dim]).item())
-    lm_np = landmarks.detach().to(torch.float32).cpu().numpy()
-    passes = []
-    for d in range(max_dimension + 1):
-        if num_rand is None and d < max_dimension:
-            continue
-        if simplices[d].shape[0] == 0:
-            continue
-        # the queue of flood_complex's tree sweep: along the widest axis, by the vertex sum
-        v_np = lm_np[simplices[d]]
-        order_np = np.argsort(v_np[:, :, axis].sum(axis=1), kind="stable")
-        simp_h = simplices[d][order_np]
-        sv = torch.as_tensor(np.ascontiguousarray(v_np[order_np]), device=dev)
-        if num_rand is None:
-            weights, _, _, faces, plan, v_idx_np = core._grid_tables(points_per_edge, max_dimension, dev, torch.float32)
-        else:
-            weights = core.generate_uniform_weights(num_rand, d, dev, torch.float32)
-            faces = core._FaceTable(None, weights.shape[0], dev)
-            plan, v_idx_np = None, None
-        face_devs = core._sweep_dimension_knn_profile(index, sv, weights, faces, columns, plan=plan)
-        passes.append([_handoff(tree, d, num_rand, order_np, simp_h, v_idx_np, f.cpu().numpy().astype(np.float64))
-                       for f in face_devs])
-    return passes
-
-
-def _sweep_cpu(points, landmarks, tree, simplices, max_dimension, points_per_edge, num_rand, index, columns):
-    from scipy.spatial import KDTree
-
-    kdtree = KDTree(np.asarray(points))
-    axis = int(torch.argmax(points.max(dim=0).values - points.min(dim=0).values).item())
-    dtype = points.dtype
-    k_max = max(k for k, _ in columns)
-    passes = []
-    for d in range(max_dimension + 1):
-        if num_rand is None and d < max_dimension:
-            continue
-        if simplices[d].shape[0] == 0:
-            continue
-        # the queue of flood_complex's CPU branch (same samples, bit for bit)
-        sv = landmarks[torch.as_tensor(simplices[d])]
-        centers, _ = core._ball_prep(sv, d)
-        splx_idx = torch.argsort(centers[:, axis])
-        sv = sv[splx_idx]
-        order_np = splx_idx.cpu().numpy()
-        simp_h = simplices[d][order_np]
-        if num_rand is None:
-            weights, _, _, faces, _, v_idx_np = core._grid_tables(points_per_edge, max_dimension, points.device, dtype)
-        else:
-            weights = core.generate_uniform_weights(num_rand, d, points.device, dtype)
-            faces = core._FaceTable(None, weights.shape[0], points.device)
-            v_idx_np = None
-        samples = weights.unsqueeze(0) @ sv
-        dist_all, _ = kdtree.query(np.asarray(samples), k=k_max, workers=core.CPU_WORKERS)   # (S, R, k_max), ascending
-        per_col = []
-        for k, stat in columns:
-            # flood_complex's own expressions on the first k distances (scipy's k' nearest are the first k' of k_max)
-            dist = np.ascontiguousarray(dist_all[..., :k])
-            if k == 1:
-                dist = dist[..., 0]
-            elif stat == "kth":
-                dist = dist[..., -1]
-            else:
-                dist = np.sqrt(np.square(dist.astype(np.float64)).sum(axis=-1) / k)
-            face = core._face_max_cpu(torch.as_tensor(np.ascontiguousarray(dist)), faces)
-            per_col.append(_handoff(tree, d, num_rand, order_np, simp_h, v_idx_np, face.cpu().numpy().astype(np.float64)))
-        passes.append(per_col)
-    return passes
