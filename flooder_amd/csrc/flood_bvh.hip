@@ -27,8 +27,6 @@ using namespace flooder;
 
 namespace {
 
-constexpr float SAFE = 0.99999f;
-
 // ------------------------------------------------------------------------------------ morton
 // bits per axis of the curve codes: option "curve_bits"; default 8 in 3D and 12 in 2D - 24-bit keys, written and
 // sorted as uint32 words in three 8-bit passes of the radix sort (a finer curve than the 256^3 grid does not make
@@ -441,25 +439,7 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
     // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound to the tile box
     float c_lo[DIM], c_hi[DIM];
     auto child_bounds = [&](int lvl, int64_t grp) -> float {
-      const int64_t idx = grp * FAN + lane;
-      float lb = __builtin_inff();
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) { c_lo[k] = __builtin_inff(); c_hi[k] = -__builtin_inff(); }
-      if (idx < lv.count[lvl]) {
-        float lo[DP], hi[DP];
-        const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
-        load_row<DP>(nb, lo);
-        load_row<DP>(nb + DP, hi);
-        lb = 0.f;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          c_lo[k] = lo[k];
-          c_hi[k] = hi[k];
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - thi[k], tlo[k] - hi[k]), 0.f);
-          lb = __builtin_fmaf(gap, gap, lb);
-        }
-      }
-      return lb;
+      return child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
     };
 
     // Inner levels keep their per-lane bounds in LDS (touched once per node expansion); the leaf level
@@ -511,7 +491,7 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
             for (int src = 0; src < per_sub; ++src) {
 #pragma unroll
               for (int i = 0; i < KSV; ++i) {
-                float lbp = 0.f;
+                float lbp = 0.f;  // (box_gap2 of flood_bvh.hpp written out: a call here moves this kernel's registers; keep in step)
 #pragma unroll
                 for (int k = 0; k < DIM; ++k) {
                   const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[i][k]), src));
@@ -558,21 +538,10 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
           if (js[u] >= 0) {
             bool need = false;
             float blo[DIM], bhi[DIM];
+            readlane_row<DIM>(c_lo, js[u], blo);
+            readlane_row<DIM>(c_hi, js[u], bhi);
 #pragma unroll
-            for (int k = 0; k < DIM; ++k) {
-              blo[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[k]), js[u]));
-              bhi[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[k]), js[u]));
-            }
-#pragma unroll
-            for (int i = 0; i < KSV; ++i) {
-              float lbp = 0.f;
-#pragma unroll
-              for (int k = 0; k < DIM; ++k) {
-                const float gap = __builtin_fmaxf(__builtin_fmaxf(blo[k] - p[i][k], p[i][k] - bhi[k]), 0.f);
-                lbp = __builtin_fmaf(gap, gap, lbp);
-              }
-              need |= (lbp * SAFE < best[i]);
-            }
+            for (int i = 0; i < KSV; ++i) need |= (box_gap2<DIM>(p[i], blo, bhi) * SAFE < best[i]);
             use[u] = __ballot(need) != 0ull;
             any_use = any_use || use[u];
           }
@@ -610,22 +579,8 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
               cb[k] = s_stage[wv][u * LEAF + h + 1][k];
             }
 #pragma unroll
-            for (int i = 0; i < KSV; ++i) {
-              float da, db;
-#pragma unroll
-              for (int k = 0; k < DIM; ++k) {
-                const float ta = p[i][k] - ca[k];
-                const float tb = p[i][k] - cb[k];
-                if (k == 0) {
-                  da = ta * ta;
-                  db = tb * tb;
-                } else {
-                  da = __builtin_fmaf(ta, ta, da);
-                  db = __builtin_fmaf(tb, tb, db);
-                }
-              }
-              best[i] = __builtin_fminf(best[i], __builtin_fminf(da, db));
-            }
+            for (int i = 0; i < KSV; ++i)
+              best[i] = __builtin_fminf(best[i], __builtin_fminf(dist2<DIM>(p[i], ca), dist2<DIM>(p[i], cb)));
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -656,7 +611,7 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
       bool need = false;
 #pragma unroll
       for (int i = 0; i < KSV; ++i) {
-        float lbp = 0.f;
+        float lbp = 0.f;  // (box_gap2 of flood_bvh.hpp written out: a call here moves this kernel's registers; keep in step)
 #pragma unroll
         for (int k = 0; k < DIM; ++k) {
           const float gap = __builtin_fmaxf(__builtin_fmaxf(blo[k] - p[i][k], p[i][k] - bhi[k]), 0.f);
@@ -671,6 +626,8 @@ __global__ __launch_bounds__(256) void sweep_bvh_kernel(
       BVH_PHASE(tb_skip);
       ++n_leaf_eval;
       const float* cp = pts + c * (int64_t)LEAF * DP;
+      // (dist2 of flood_bvh.hpp for two rows side by side, minima in pairs: the same loop in flood_finish.hip,
+      // flood_sorted.hip and flood_cell.hip; keep them in step)
 #pragma unroll
       for (int h = 0; h < LEAF; h += 8) {
         typename RowVec<DP>::type cc[8];

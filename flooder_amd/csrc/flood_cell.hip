@@ -756,7 +756,7 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
               const uint32_t nb_ = (uint32_t)((int)ARG(lv.off[lvl]) + (ok ? idx : 0)) * (uint32_t)(2 * DP * sizeof(float));
               load_row_at<DP>(nodes, nb_, lo);
               load_row_at<DP>(nodes, nb_ + (uint32_t)(DP * sizeof(float)), hi);
-              float lb = 0.f;
+              float lb = 0.f;  // (box_gap2 of flood_bvh.hpp written out: this kernel sits at its register limit)
 #pragma unroll
               for (int k = 0; k < DIM; ++k) {
                 const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - thi[k], tlo[k] - hi[k]), 0.f);

@@ -350,6 +350,18 @@ inline void launch_cloud_kind(int dim, int32_t* grid, hipStream_t st) {   // gri
   else if (dim == 3) hipLaunchKernelGGL((cloud_kind_kernel<3>), dim3(16), dim3(256), 0, st, grid, grid + 64 * 64 * 64);
 }
 
+// The size / abi rule of a parameter block (include/flooder_hip.h): the caller's struct (its `size` bytes) laid over a
+// zeroed struct of OUR size - fields the caller does not have read as NULL / 0, a caller that has fields we do not know
+// is refused with `who`.
+template <typename T>
+int take(const T* p, T& out, const char* who) {
+  if (!p) return fail(FLOODER_E_ARG, who);
+  if (p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(T)) return fail(FLOODER_E_ARG, who);
+  memset(&out, 0, sizeof(T));
+  memcpy(&out, p, p->size);
+  return 0;
+}
+
 // The launches that have a parameter block (include/flooder_hip.h), each ONE function on its block: it makes the checks
 // and fills the kernel's own structs from the named fields.  flood_params.hip calls them with the caller's block, the
 // positional exports with a zeroed block they have filled by name (so: no density grid, no run table and planes_ready 0

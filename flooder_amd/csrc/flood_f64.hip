@@ -81,6 +81,7 @@ __global__ __launch_bounds__(256) void sweep_bvh_f64_kernel(
     }
     double M = INF;  // largest running minimum of the tile
 
+    // (child_box_bound of flood_bvh.hpp in double, on float32 boxes widened outwards: shares no rounding with it)
     double c_lo[DIM], c_hi[DIM];
     auto child_bounds = [&](int lvl, int64_t grp) -> double {
       const int64_t idx = grp * FAN + lane;

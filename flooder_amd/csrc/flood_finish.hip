@@ -26,7 +26,6 @@ using namespace flooder;
 
 namespace {
 
-constexpr float SAFE = 0.99999f;
 constexpr int SHORT_LIST = 1024;
 #ifndef FLOODER_TOP_NODES
 #define FLOODER_TOP_NODES 1024
@@ -350,6 +349,8 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
     }
 
     // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound to the live box
+    // (child_box_bound of flood_bvh.hpp with two extras - rows of the staged tree top, the team's share of level 1 -
+    // written out: passing them in moves the team kernel's registers)
     float c_lo[DIM], c_hi[DIM];
     auto child_bounds = [&](int lvl, int64_t grp) -> float {
       const int64_t idx = grp * FAN + lane;
@@ -367,20 +368,16 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
           load_row<DP>(nb, lo);
           load_row<DP>(nb + DP, hi);
         }
-        lb = 0.f;
 #pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          c_lo[k] = lo[k];
-          c_hi[k] = hi[k];
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - thi[k], tlo[k] - hi[k]), 0.f);
-          lb = __builtin_fmaf(gap, gap, lb);
-        }
+        for (int k = 0; k < DIM; ++k) { c_lo[k] = lo[k]; c_hi[k] = hi[k]; }
+        lb = box_gap2<DIM>(lo, hi, tlo, thi);
         // one wave of several on a hard entry: only its share of the level-1 nodes
         if (TEAM && lvl == 1 && (int)(idx % TEAM_WAVES) != part) lb = __builtin_inff();
       }
       return lb;
     };
-    // all 16 points of leaf c against this lane's sample (points through the scalar cache)
+    // all 16 points of leaf c against this lane's sample (points through the scalar cache; the loop of
+    // sweep_bvh_kernel, flood_bvh.hip, for one sample: keep in step)
     auto eval_leaf = [&](int64_t c) {
       const float* cp = pts + c * (int64_t)LEAF * DP;
 #pragma unroll
@@ -512,7 +509,7 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
               while (lm) {  // (wave-uniform)
                 const int src = __builtin_ctzll(lm);
                 lm &= lm - 1ull;
-                float lbp = 0.f;
+                float lbp = 0.f;  // (box_gap2 of flood_bvh.hpp written out: the calls in this kernel cost cfg 2's finish time)
 #pragma unroll
                 for (int k = 0; k < DIM; ++k) {
                   const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[k]), src));
@@ -544,7 +541,7 @@ __global__ __launch_bounds__(TEAM ? 64 * TEAM_WAVES : 64 * WAVES, TEAM ? 4 : (WA
           blo[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[k]), j));
           bhi[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[k]), j));
         }
-        float lbp = 0.f;
+        float lbp = 0.f;  // (box_gap2 of flood_bvh.hpp written out, as in the refine above)
 #pragma unroll
         for (int k = 0; k < DIM; ++k) {
           const float gap = __builtin_fmaxf(__builtin_fmaxf(blo[k] - p[k], p[k] - bhi[k]), 0.f);
@@ -723,21 +720,7 @@ __global__ __launch_bounds__(64 * SINGLE_WAVES) void finish_single_kernel(
 
   // ---- search, nearest first; `grp` is the open group of level `lvl` (its parent's index: grp >> 6 one level up)
   auto child_lb = [&](int lvl, int64_t grp) -> float {
-    const int64_t idx = grp * FAN + lane;
-    float lb = __builtin_inff();
-    if (idx < lv.count[lvl]) {
-      float lo[DP], hi[DP];
-      const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
-      load_row<DP>(nb, lo);
-      load_row<DP>(nb + DP, hi);
-      lb = 0.f;
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) {
-        const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - p[k], p[k] - hi[k]), 0.f);
-        lb = __builtin_fmaf(gap, gap, lb);
-      }
-    }
-    return lb;
+    return child_point_bound<DIM>(nodes, lv, lvl, grp, lane, p);
   };
   const int topl = lv.n_levels - 1;
   unsigned long long n_leaf = 0, n_node = 1;
@@ -796,7 +779,7 @@ __global__ __launch_bounds__(64 * SINGLE_WAVES) void finish_single_kernel(
       float x[DP];
       load_row<DP>(pts + ((grp * FAN + jm) * (int64_t)LEAF + (lane & 15)) * DP, x);
 #pragma unroll
-      for (int k = 0; k < DIM; ++k) {
+      for (int k = 0; k < DIM; ++k) {   // (dist2 of flood_bvh.hpp written out)
         const float t = p[k] - x[k];
         d = k == 0 ? t * t : __builtin_fmaf(t, t, d);
       }

@@ -20,13 +20,9 @@
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
 
-#include <cstring>
-
 using namespace flooder;
 
 namespace {
-
-constexpr float GRAD_SAFE = 0.99999f;   // lower bounds are compared with the same margin as the sweeps' culling
 
 // ------------------------------------------------------------------------------------------------ face argmax
 // One wave per simplex (persistent, grid-stride).  The rows of a face are read in ascending column order (the caller
@@ -119,23 +115,18 @@ __global__ __launch_bounds__(256) void witness_search_kernel(const float* __rest
       const int64_t grp = e >> 3;
       const int64_t idx = grp * FAN + lane;
       bool ok = false;
-      if (idx < lv.count[lvl]) {
+      if (idx < lv.count[lvl]) {   // (child_point_bound of flood_bvh.hpp, its load written out: see witness_knn_kernel)
         float lo[DP], hi[DP];
         const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
         load_row<DP>(nb, lo);
         load_row<DP>(nb + DP, hi);
-        float lb = 0.f;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - p[k], p[k] - hi[k]), 0.f);
-          lb = __builtin_fmaf(gap, gap, lb);
-        }
-        ok = lb * GRAD_SAFE <= tf;
+        ok = box_gap2<DIM>(p, lo, hi) * SAFE <= tf;
       }
       unsigned long long mask = __ballot(ok);
       __builtin_amdgcn_wave_barrier();   // (every lane has read the popped entry before a push may overwrite it)
       if (lvl == 0) {
         while (mask) {
+          // (the pop above and the next four leaves, one point per lane: the same steps in witness_knn_kernel; keep in step)
           int64_t leaf[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -153,13 +144,7 @@ __global__ __launch_bounds__(256) void witness_search_kernel(const float* __rest
           if (lf >= 0 && rw < n_pts) {
             float x[DP];
             load_row<DP>(pts + rw * DP, x);
-            float d2;
-#pragma unroll
-            for (int k = 0; k < DIM; ++k) {
-              const float t = p[k] - x[k];
-              if (k == 0) d2 = t * t;
-              else d2 = __builtin_fmaf(t, t, d2);
-            }
+            const float d2 = dist2<DIM>(p, x);
             if (__float_as_uint(d2) == target) {
               const uint32_t id = (uint32_t)order[rw];
               best = id < best ? id : best;
@@ -203,7 +188,7 @@ struct WitnessOp {
 //
 // Exactness.  Keys are distinct (ids are), so "the k smallest keys of all points" is one set, and inserting any
 // superset of it in any order leaves exactly that set, sorted.  A subtree or leaf is skipped only when
-// lb * GRAD_SAFE > (k-th best d2) - every point in it then has d2 > the k-th best and hence a LARGER key, whatever its
+// lb * SAFE > (k-th best d2) - every point in it then has d2 > the k-th best and hence a LARGER key, whatever its
 // id.  A box at lb == k-th best is opened: a point at an equal d2 with a smaller id displaces the k-th entry.
 // Nothing is skipped before the list holds k points (its k-th d2 word is all ones: +inf here).
 template <int DIM>
@@ -256,23 +241,19 @@ __global__ __launch_bounds__(256) void witness_knn_kernel(const float* __restric
         const int64_t idx = grp * FAN + lane;
         bool ok = false;
         float lb = __builtin_inff();
-        if (idx < lv.count[lvl]) {
+        if (idx < lv.count[lvl]) {   // (child_point_bound of flood_bvh.hpp, its load written out: the call cost k = 32 3 %)
           float lo[DP], hi[DP];
           const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
           load_row<DP>(nb, lo);
           load_row<DP>(nb + DP, hi);
-          lb = 0.f;
-#pragma unroll
-          for (int c = 0; c < DIM; ++c) {
-            const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[c] - p[c], p[c] - hi[c]), 0.f);
-            lb = __builtin_fmaf(gap, gap, lb);
-          }
-          ok = !(lb * GRAD_SAFE > kth_f);
+          lb = box_gap2<DIM>(p, lo, hi);
+          ok = !(lb * SAFE > kth_f);
         }
         unsigned long long mask = __ballot(ok);
         __builtin_amdgcn_wave_barrier();   // (every lane has read the popped entry before a push may overwrite it)
         if (lvl == 0) {
           while (mask) {
+            // (the pop above and the next four leaves, one point per lane: the steps of witness_search_kernel)
             int64_t leaf[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -291,13 +272,7 @@ __global__ __launch_bounds__(256) void witness_knn_kernel(const float* __restric
             if (lf >= 0 && rw < n_pts) {   // (rows of the padded last leaf are never candidates)
               float x[DP];
               load_row<DP>(pts + rw * DP, x);
-              float d2;
-#pragma unroll
-              for (int c = 0; c < DIM; ++c) {
-                const float t = p[c] - x[c];
-                if (c == 0) d2 = t * t;
-                else d2 = __builtin_fmaf(t, t, d2);
-              }
+              const float d2 = dist2<DIM>(p, x);
               c_hi = __float_as_uint(d2);
               c_lo = (uint32_t)order[rw];
             }
@@ -319,7 +294,7 @@ __global__ __launch_bounds__(256) void witness_knn_kernel(const float* __restric
               kth_lo = (uint32_t)__builtin_amdgcn_readlane((int)l_lo, k - 1);
             }
             kth_f = kth_hi == 0xffffffffu ? __builtin_inff() : __uint_as_float(kth_hi);
-            mask &= __ballot(!(lb * GRAD_SAFE > kth_f));   // the leaves still waiting, against the new k-th best
+            mask &= __ballot(!(lb * SAFE > kth_f));   // the leaves still waiting, against the new k-th best
           }
         } else {
           if (mask) {
@@ -357,18 +332,16 @@ __global__ __launch_bounds__(256) void witness_knn_kernel(const float* __restric
 template <int DIM>
 struct WitnessKnnOp {
   static int run(const flooder_witness_knn_t& a, const Levels& lv, hipStream_t st) {
-    int64_t blocks = (a.n_queries + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(witness_knn_kernel<DIM>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
-                       a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
-                       a.n_queries, a.k, a.stat, a.q_simplex, a.q_row, a.q_stat, a.out_ids, a.out_d2, a.not_found);
-    return check_launch("witness_knn");
-  }
-};
-template <>
-struct WitnessKnnOp<1> {
-  static int run(const flooder_witness_knn_t&, const Levels&, hipStream_t) {
-    return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
+    if constexpr (DIM < 2) {
+      return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
+    } else {
+      int64_t blocks = (a.n_queries + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+      if (blocks > 256 * 16) blocks = 256 * 16;
+      hipLaunchKernelGGL(witness_knn_kernel<DIM>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
+                         a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
+                         a.n_queries, a.k, a.stat, a.q_simplex, a.q_row, a.q_stat, a.out_ids, a.out_d2, a.not_found);
+      return check_launch("witness_knn");
+    }
   }
 };
 
@@ -407,11 +380,8 @@ int flooder_face_argmax_f32(const uint32_t* d2, int64_t n_simplices, int R, cons
 }
 
 int flooder_witness_search(const flooder_witness_search_t* p, void* stream) {
-  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_witness_search_t))
-    return fail(FLOODER_E_ARG, "flooder_witness_search: bad parameter block (abi / size)");
   flooder_witness_search_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, p, p->size);
+  if (int rc = take(p, a, "flooder_witness_search: bad parameter block (abi / size)")) return rc;
   if (a.n_queries == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.order || !a.verts || !a.weights || !a.q_simplex || !a.q_row || !a.q_d2 ||
       !a.out_point || !a.not_found || a.n_pts < 1 || a.k1 < 1 || a.R < 1 || a.n_queries < 0 || a.dim < 2 || a.dim > 8 ||
@@ -424,11 +394,8 @@ int flooder_witness_search(const flooder_witness_search_t* p, void* stream) {
 }
 
 int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream) {
-  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_witness_knn_t))
-    return fail(FLOODER_E_ARG, "flooder_witness_knn: bad parameter block (abi / size)");
   flooder_witness_knn_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, p, p->size);
+  if (int rc = take(p, a, "flooder_witness_knn: bad parameter block (abi / size)")) return rc;
   if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_witness_knn: k must be in 1..32");
   if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
   if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_witness_knn: stat must be 0 (kth) or 1 (dtm)");

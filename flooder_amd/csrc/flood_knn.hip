@@ -35,13 +35,11 @@
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
 
-#include <cstring>
+#include <type_traits>
 
 using namespace flooder;
 
 namespace {
-
-constexpr float SAFE = 0.99999f;   // the margin of the other tree sweeps (flood_bvh.hip)
 
 struct KnnProfileCols {   // column of (statistic, rank - 1), -1: not asked for (kernarg segment: scalar look-ups)
   int32_t col_of[2][FLOODER_KNN_MAX];
@@ -105,25 +103,7 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
     // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound to the tile box
     float c_lo[DIM], c_hi[DIM];
     auto child_bounds = [&](int lvl, int64_t grp) -> float {
-      const int64_t idx = grp * FAN + lane;
-      float lb = __builtin_inff();
-#pragma unroll
-      for (int c = 0; c < DIM; ++c) { c_lo[c] = __builtin_inff(); c_hi[c] = -__builtin_inff(); }
-      if (idx < lv.count[lvl]) {
-        float lo[DP], hi[DP];
-        const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
-        load_row<DP>(nb, lo);
-        load_row<DP>(nb + DP, hi);
-        lb = 0.f;
-#pragma unroll
-        for (int c = 0; c < DIM; ++c) {
-          c_lo[c] = lo[c];
-          c_hi[c] = hi[c];
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[c] - thi[c], tlo[c] - hi[c]), 0.f);
-          lb = __builtin_fmaf(gap, gap, lb);
-        }
-      }
-      return lb;
+      return child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
     };
 
     // inner levels keep their per-lane bounds in LDS; the leaf level runs in registers (lb0, c_lo / c_hi)
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
       const int64_t c = grp0 * FAN + j;
       ++n_leaf_test;
       // can the k-th best of any lane still drop against leaf c?  (its box comes from lane j)
-      float lbp = 0.f;
+      float lbp = 0.f;  // (readlane_row + box_gap2 of flood_bvh.hpp, axis by axis: a call cost K = 32 0.4 % of its time; keep in step)
 #pragma unroll
       for (int a = 0; a < DIM; ++a) {
         const float blo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[a]), j));
@@ -188,7 +168,7 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
         for (int u = 0; u < NB; ++u) cc[u] = load_uniform_row<DP>(cp + (h + u) * DP);
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
-          float d;
+          float d;  // (dist2 of flood_bvh.hpp written out, as above)
 #pragma unroll
           for (int a = 0; a < DIM; ++a) {
             const float t = p[a] - cc[u][a];
@@ -252,30 +232,36 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
   }
 }
 
-template <int DIM>
-struct SweepKnnOp {
-  static int run(const flooder_knn_sweep_t& a, const Levels& lv, hipStream_t st) {
+// The launch of sweep_knn_kernel<DIM, K, PROFILE> at K = the smallest of 2, 4, 8, 16, 32 that holds k.
+// (the tree sweeps exist for one ambient dimension as well; the k-nearest sweep is defined for 2 .. 8: `who_dim`)
+template <int DIM, bool PROFILE, typename Args>
+int launch_sweep_knn(const Args& a, int k, int stat, const KnnProfileCols& cols, const Levels& lv, hipStream_t st,
+                     const char* what, const char* who_dim) {
+  if constexpr (DIM < 2) {
+    return fail(FLOODER_E_ARG, who_dim);
+  } else {
     const int64_t n_items = a.n_simplices * ((a.R + 63) / 64);
     int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
     if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
-#define FLOODER_LAUNCH_KNN(K_)                                                                                       \
-  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_, false>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, \
-                     lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat, a.queue, a.out_bits,             \
-                     reinterpret_cast<unsigned long long*>(a.stats), KnnProfileCols{})
-    if (a.k <= 2) FLOODER_LAUNCH_KNN(2);
-    else if (a.k <= 4) FLOODER_LAUNCH_KNN(4);
-    else if (a.k <= 8) FLOODER_LAUNCH_KNN(8);
-    else if (a.k <= 16) FLOODER_LAUNCH_KNN(16);
-    else FLOODER_LAUNCH_KNN(32);
-#undef FLOODER_LAUNCH_KNN
-    return check_launch("sweep_knn");
+    auto launch = [&](auto kc) {
+      hipLaunchKernelGGL((sweep_knn_kernel<DIM, decltype(kc)::value, PROFILE>), dim3((unsigned)grid), dim3(256), 0, st,
+                         a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, k, stat, a.queue,
+                         a.out_bits, reinterpret_cast<unsigned long long*>(a.stats), cols);
+    };
+    if (k <= 2) launch(std::integral_constant<int, 2>{});
+    else if (k <= 4) launch(std::integral_constant<int, 4>{});
+    else if (k <= 8) launch(std::integral_constant<int, 8>{});
+    else if (k <= 16) launch(std::integral_constant<int, 16>{});
+    else launch(std::integral_constant<int, 32>{});
+    return check_launch(what);
   }
-};
-// (the tree sweeps exist for one ambient dimension as well; the k-nearest sweep is defined for 2 .. 8)
-template <>
-struct SweepKnnOp<1> {
-  static int run(const flooder_knn_sweep_t&, const Levels&, hipStream_t) {
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
+}
+
+template <int DIM>
+struct SweepKnnOp {
+  static int run(const flooder_knn_sweep_t& a, const Levels& lv, hipStream_t st) {
+    return launch_sweep_knn<DIM, false>(a, a.k, a.stat, KnnProfileCols{}, lv, st, "sweep_knn",
+                                        "flooder_sweep_knn_f32: dim must be in 2..8");
   }
 };
 
@@ -288,38 +274,16 @@ struct KnnProfileLaunch {   // the checked block and what the host derives from 
 template <int DIM>
 struct SweepKnnProfileOp {
   static int run(const KnnProfileLaunch& p, const Levels& lv, hipStream_t st) {
-    const flooder_knn_profile_t& a = p.a;
-    const int64_t n_items = a.n_simplices * ((a.R + 63) / 64);
-    int64_t grid = g_bvh_grid;  // as the single sweep: persistent blocks, 4 independent waves each
-    if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
-#define FLOODER_LAUNCH_KNN_PROFILE(K_)                                                                               \
-  hipLaunchKernelGGL((sweep_knn_kernel<DIM, K_, true>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, \
-                     lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, p.k_max, 0, a.queue, a.out_bits,             \
-                     reinterpret_cast<unsigned long long*>(a.stats), p.cols)
-    if (p.k_max <= 2) FLOODER_LAUNCH_KNN_PROFILE(2);
-    else if (p.k_max <= 4) FLOODER_LAUNCH_KNN_PROFILE(4);
-    else if (p.k_max <= 8) FLOODER_LAUNCH_KNN_PROFILE(8);
-    else if (p.k_max <= 16) FLOODER_LAUNCH_KNN_PROFILE(16);
-    else FLOODER_LAUNCH_KNN_PROFILE(32);
-#undef FLOODER_LAUNCH_KNN_PROFILE
-    return check_launch("sweep_knn_profile");
-  }
-};
-template <>
-struct SweepKnnProfileOp<1> {
-  static int run(const KnnProfileLaunch&, const Levels&, hipStream_t) {
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: dim must be in 2..8");
+    return launch_sweep_knn<DIM, true>(p.a, p.k_max, 0, p.cols, lv, st, "sweep_knn_profile",
+                                       "flooder_sweep_knn_profile_f32: dim must be in 2..8");
   }
 };
 
 }  // namespace
 
 extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream) {
-  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_knn_sweep_t))
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad parameter block (abi / size)");
   flooder_knn_sweep_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, p, p->size);
+  if (int rc = take(p, a, "flooder_sweep_knn_f32: bad parameter block (abi / size)")) return rc;
   if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: k must be in 1..32");
   if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
   if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: stat must be 0 (kth) or 1 (dtm)");
@@ -332,12 +296,9 @@ extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream)
 }
 
 extern "C" int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream) {
-  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_knn_profile_t))
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: bad parameter block (abi / size)");
   KnnProfileLaunch L;
   flooder_knn_profile_t& a = L.a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, p, p->size);
+  if (int rc = take(p, a, "flooder_sweep_knn_profile_f32: bad parameter block (abi / size)")) return rc;
   if (a.n_cols < 1 || a.n_cols > FLOODER_KNN_COLS_MAX)
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: n_cols must be in 1..64");
   for (int s = 0; s < 2; ++s)

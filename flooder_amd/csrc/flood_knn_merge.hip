@@ -26,7 +26,6 @@
 
 #include "flood_common.hpp"
 
-#include <cstring>
 
 using namespace flooder;
 
@@ -81,11 +80,8 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const int32_t* __restric
 }  // namespace
 
 extern "C" int flooder_knn_merge_f32(const flooder_knn_merge_t* p, void* stream) {
-  if (!p || p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(flooder_knn_merge_t))
-    return fail(FLOODER_E_ARG, "flooder_knn_merge_f32: bad parameter block (abi / size)");
   flooder_knn_merge_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, p, p->size);
+  if (int rc = take(p, a, "flooder_knn_merge_f32: bad parameter block (abi / size)")) return rc;
   if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_knn_merge_f32: k must be in 1..32");
   if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_knn_merge_f32: stat must be 0 (kth) or 1 (dtm)");
   if (a.n_lists < 1) return fail(FLOODER_E_ARG, "flooder_knn_merge_f32: n_lists must be at least 1");

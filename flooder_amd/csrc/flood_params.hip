@@ -5,23 +5,7 @@
 #include "../../include/flooder_hip.h"
 #include "flood_common.hpp"
 
-#include <cstddef>
-#include <cstring>
-
-namespace {
 using namespace flooder;
-
-// The caller's struct (its `size` bytes) laid over a zeroed struct of OUR size: fields the caller does not have read as
-// NULL / 0, a caller that has fields we do not know is refused.
-template <typename T>
-int take(const T* p, T& out, const char* who) {
-  if (!p) return fail(FLOODER_E_ARG, who);
-  if (p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(T)) return fail(FLOODER_E_ARG, who);
-  std::memset(&out, 0, sizeof(T));
-  std::memcpy(&out, p, p->size);
-  return 0;
-}
-}  // namespace
 
 extern "C" int flooder_fused_witness(const flooder_fused_sweep_t* p, void* stream) {
   flooder_fused_sweep_t a;

@@ -22,8 +22,6 @@ using namespace flooder;
 
 namespace {
 
-constexpr float SAFE = 0.99999f;
-
 // SUB-TILES.  The tile's bounding box against a leaf box is a weak test in 6D (the gaps of six axes add up, and the box of
 // 64 samples is as wide as a leaf): three of four leaves that pass it fail the per-sample test that follows, and that
 // test - the leaf's box broadcast from its lane, every sample against it, a ballot - is a serial chain that took 45 % of
@@ -346,25 +344,7 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
 
     float c_lo[DIM], c_hi[DIM];
     auto child_bounds = [&](int lvl, int64_t grp) -> float {
-      const int64_t idx = grp * FAN + lane;
-      float lb = __builtin_inff();
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) { c_lo[k] = __builtin_inff(); c_hi[k] = -__builtin_inff(); }
-      if (idx < lv.count[lvl]) {
-        float lo[DP], hi[DP];
-        const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
-        load_row<DP>(nb, lo);
-        load_row<DP>(nb + DP, hi);
-        lb = 0.f;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          c_lo[k] = lo[k];
-          c_hi[k] = hi[k];
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(lo[k] - thi[k], tlo[k] - hi[k]), 0.f);
-          lb = __builtin_fmaf(gap, gap, lb);
-        }
-      }
-      return lb;
+      return child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
     };
 
     // this lane's leaf box (c_lo, c_hi) against every sub-tile's box; the smallest of them is the leaf's place in the
@@ -373,13 +353,8 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
       float nearest = __builtin_inff();
 #pragma unroll
       for (int q = 0; q < NSUB; ++q) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          const float gap = __builtin_fmaxf(__builtin_fmaxf(c_lo[k] - s_sub[wv][q][FLOODER_MAX_DIM + k],
-                                                            s_sub[wv][q][k] - c_hi[k]), 0.f);
-          a = __builtin_fmaf(gap, gap, a);
-        }
+        const float* sb = s_sub[wv][q];
+        const float a = box_gap2<DIM>(c_lo, c_hi, sb, sb + FLOODER_MAX_DIM);
         dst[q] = a;
         nearest = __builtin_fminf(nearest, a);
       }
@@ -460,15 +435,7 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
             const typename RowVec<DP>::type nlo = load_uniform_row<DP>(nb), nhi = load_uniform_row<DP>(nb + DP);
             bool nd = false;
 #pragma unroll
-            for (int i = 0; i < KS; ++i) {
-              float lbp = 0.f;
-#pragma unroll
-              for (int k = 0; k < DIM; ++k) {
-                const float gap = __builtin_fmaxf(__builtin_fmaxf(nlo[k] - p[i][k], p[i][k] - nhi[k]), 0.f);
-                lbp = __builtin_fmaf(gap, gap, lbp);
-              }
-              nd = nd || (alive[i] && lbp * SAFE < best[i]);
-            }
+            for (int i = 0; i < KS; ++i) nd = nd || (alive[i] && box_gap2<DIM>(p[i], nlo, nhi) * SAFE < best[i]);
             if (__ballot(nd) == 0ull) {
               lvl = 1;
               ++n_node_spared;
@@ -508,13 +475,9 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
             for (int src = 0; src < 64; ++src) {
 #pragma unroll
               for (int i = 0; i < KS; ++i) {
-                float lbp = 0.f;
-#pragma unroll
-                for (int k = 0; k < DIM; ++k) {
-                  const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[i][k]), src));
-                  const float gap = __builtin_fmaxf(__builtin_fmaxf(c_lo[k] - pk, pk - c_hi[k]), 0.f);
-                  lbp = __builtin_fmaf(gap, gap, lbp);
-                }
+                float ps[DIM];
+                readlane_row<DIM>(p[i], src, ps);
+                const float lbp = box_gap2<DIM>(ps, c_lo, c_hi);
                 const float bi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(alive[i] ? best[i] : -1.f), src));
                 need = need || (lbp * SAFE < bi);
               }
@@ -568,7 +531,7 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
       bool need = false;
 #pragma unroll
       for (int i = 0; i < KS; ++i) {
-        float lbp = 0.f;
+        float lbp = 0.f;  // (box_gap2 of flood_bvh.hpp written out: a call here moves this kernel's registers; keep in step)
 #pragma unroll
         for (int k = 0; k < DIM; ++k) {
           const float gap = __builtin_fmaxf(__builtin_fmaxf(blo[k] - p[i][k], p[i][k] - bhi[k]), 0.f);
@@ -583,7 +546,8 @@ __global__ __launch_bounds__(256, (KS == 1 && !FUSED && DIM <= 6) ? FLOODER_SORT
       ++evals_in_group;
 #endif
       const float* cp = pts + c * (int64_t)LEAF * DP;
-      // rows stream through SGPRs (scalar loads), UB at a time (FLOODER_SORTED_UB8 above)
+      // rows stream through SGPRs (scalar loads), UB at a time (FLOODER_SORTED_UB8 above); the loop of sweep_bvh_kernel
+      // (flood_bvh.hip), kept in step with it
       constexpr int UB = FLOODER_SORTED_UB8 ? 8 : (DP == 8 ? 4 : 8);
 #pragma unroll
       for (int h = 0; h < LEAF; h += UB) {
