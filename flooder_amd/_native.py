@@ -57,7 +57,7 @@ class FusedSweep(_Block):
         p top_list; p top_count; p simplex_weight; p plane_scratch; p wit_queue; p wit_item_list; p wit_stats;
         p cell_queue; p defer_list; p defer_c; p defer_ctl; p light_list; p heavy_list; p cell_stats; p finish_ctl;
         p hard_scratch; i32 hard_cap; i32 probed; p finish_stats; p wit_runs; i32 wit_run_len; i32 wit_n_runs;
-        i32 planes_ready; i32 reserved""")
+        i32 planes_ready; i32 reserved; p face_owner; p min_face; p chunk_faces; p tile_faces""")
 
 
 class SortedSweep(_Block):
@@ -201,6 +201,7 @@ SIGNATURES = {
     "flooder_finish_single_tiles": (c_int, []),
     "flooder_finish_single_batches": (c_int, []),
     "flooder_face_values_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "flooder_face_closure_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "flooder_simplex_weight_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "flooder_simplex_planes_forget": (None, []),
     "flooder_simplex_prepare_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,

@@ -309,7 +309,7 @@ _GRID_CACHE: Dict[tuple, tuple] = {}
 def _grid_tables(points_per_edge: int, dim: int, device, dtype):
     """``generate_grid`` + face table + sample plan of one (points_per_edge, dimension): identical from call to
     call, 2 - 3 ms of host work and a dozen small uploads each time - kept per device."""
-    key = (int(points_per_edge), int(dim), str(device), dtype, SAMPLE_UNITS)
+    key = (int(points_per_edge), int(dim), str(device), dtype, SAMPLE_UNITS, bool(FACE_OWNER), bool(FACE_OWNER_GROUPED))
     hit = _GRID_CACHE.get(key)
     if hit is None:
         weights, vertex_idxs, face_idxs = generate_grid(points_per_edge, dim, device, dtype)
@@ -936,6 +936,67 @@ def _sample_order_bisect(w: np.ndarray) -> np.ndarray:
     return np.concatenate(out)
 
 
+def sample_order_grouped(weights: np.ndarray, group: np.ndarray) -> np.ndarray:
+    """The order of ``sample_order`` for rows that come in GROUPS (face ownership: the minimal face of a row): the
+    groups in ascending order, and inside each the same recursive bisection along the widest axis - with the cuts at the
+    multiples of 1024 / 256 / 64 / 16 of the position in the WHOLE order, so that the chunks and tiles of the sweeps,
+    which are aligned runs of the whole order, stay compact patches where a group starts in the middle of one.  (A stable
+    partition of ``sample_order`` itself moves every cut of the interior rows off the chunk grid: total chunk box volume
+    on the regular simplex 7.7 against 0.68, tools/face_owner_count.py.)"""
+    w = np.asarray(weights, dtype=np.float64)
+    R, k1 = w.shape
+    corners = np.eye(k1) - 1.0 / k1
+    X = w @ (corners @ np.linalg.qr(corners.T)[0][:, :k1 - 1])
+    out: List[np.ndarray] = []
+    pos = 0
+    for g in np.unique(group):
+        stack = [(np.nonzero(group == g)[0].astype(np.int64), pos)]
+        while stack:
+            idx, a = stack.pop()
+            n = idx.shape[0]
+            if n <= SAMPLE_UNITS[-1]:
+                out.append(idx)
+                continue
+            P = X[idx]
+            ax = int(np.argmax(P.max(axis=0) - P.min(axis=0)))
+            idx = idx[np.argsort(P[:, ax], kind="stable")]
+            n_left = n // 2
+            for u in SAMPLE_UNITS:   # the middle one of the coarsest cuts that fall inside the run
+                k0, k1_ = a // u + 1, -(-(a + n) // u) - 1
+                if k1_ >= k0:
+                    n_left = (k0 + (k1_ - k0 + 2) // 2 - 1) * u - a
+                    break
+            stack.append((idx[n_left:], a + n_left))
+            stack.append((idx[:n_left], a))
+        pos += int((group == g).sum())
+    return np.concatenate(out) if out else np.arange(R, dtype=np.int64)
+
+
+def row_groups(min_face: np.ndarray, sub_faces: np.ndarray, n_per_codim: List[int]) -> np.ndarray:
+    """Group of every row for ``sample_order_grouped``: 0 for the interior rows, f for the rows whose minimal face is the
+    codimension-1 face f, and for a row on a smaller face (an edge or a vertex of a tetrahedron) the first
+    codimension-1 face that contains it - a group of their own would be one chunk that spans the whole simplex (30 points
+    per edge: 172 rows on six edges and four vertices), with a region to match; beside the rows of a facet they lie on
+    they sit in that facet's patches.  The groups partition the rows."""
+    n1 = n_per_codim[1] if len(n_per_codim) > 1 else 0
+    group = min_face.astype(np.int64).copy()
+    small = group > n1
+    if small.any():
+        inside = (sub_faces[1:n1 + 1, None].astype(np.int64) >> min_face[None, small].astype(np.int64)) & 1   # (n1, rows)
+        group[small] = 1 + inside.argmax(axis=0)
+    return group
+
+
+def _grouped_order_cached(w: np.ndarray, group: np.ndarray) -> np.ndarray:
+    key = (w.shape, hash(w.tobytes()), hash(group.tobytes()), SAMPLE_UNITS, "grouped")
+    hit = _SAMPLE_ORDER_CACHE.get(key)
+    if hit is None:
+        if len(_SAMPLE_ORDER_CACHE) >= 32:
+            _SAMPLE_ORDER_CACHE.clear()
+        hit = _SAMPLE_ORDER_CACHE[key] = sample_order_grouped(w, group)
+    return hit.copy()
+
+
 WIT_MAX_COARSE = 256     # FLOODER_WIT_MAX_COARSE
 WIT_MAX_ROWS = 8192      # FLOODER_WIT_MAX_ROWS
 WIT_MIN_ROWS = 512       # below this a simplex is too small for a coarse level to pay
@@ -1056,6 +1117,40 @@ def witness_runs(w_perm: np.ndarray, memb: np.ndarray, parents: np.ndarray,
     return out
 
 
+def face_lattice(weights: np.ndarray, f_ptr: np.ndarray, f_rows: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+    """Face lattice of one weight table and its face table (CSR ``f_ptr`` / ``f_rows`` in original row order):
+    ``(min_face (R,) uint8, sub_faces (F,) uint32)``.  A face's vertex set is the union of the supports of its rows;
+    ``min_face[r]`` is the face with the fewest vertices whose vertex set holds the support of row r (its MINIMAL face:
+    the full simplex for an interior row), ``sub_faces[f]`` has bit g set when face g's vertices all belong to face f
+    (f itself included).  None where a row lies on no face of the table or two faces have the same vertices."""
+    w = np.asarray(weights)
+    R, k1 = w.shape
+    F = len(f_ptr) - 1
+    if F > 32 or k1 > 31:
+        return None
+    supp = ((w != 0) * (1 << np.arange(k1))).sum(axis=1).astype(np.int64)
+    vset = np.array([np.bitwise_or.reduce(supp[f_rows[f_ptr[f]:f_ptr[f + 1]]]) if f_ptr[f + 1] > f_ptr[f] else 0
+                     for f in range(F)], dtype=np.int64)
+    if len(set(vset.tolist())) != F or (vset == 0).any():
+        return None
+    holds = (supp[:, None] & ~vset[None, :]) == 0                       # (R, F): face f holds row r
+    if not holds.any(axis=1).all():
+        return None
+    size = np.array([bin(int(v)).count("1") for v in vset])
+    min_face = np.where(holds, size[None, :], k1 + 1).argmin(axis=1).astype(np.uint8)
+    sub = (vset[None, :] & ~vset[:, None]) == 0                         # [f, g]: g inside f
+    sub_faces = (sub * (1 << np.arange(F, dtype=np.int64))[None, :]).sum(axis=1).astype(np.uint32)
+    return min_face, sub_faces
+
+
+def _or_runs(bits: np.ndarray, run: int) -> np.ndarray:
+    """OR of every aligned run of ``run`` words (the last one may be short)."""
+    n = (bits.shape[0] + run - 1) // run
+    pad = np.zeros(n * run, dtype=np.uint32)
+    pad[:bits.shape[0]] = bits
+    return np.bitwise_or.reduce(pad.reshape(n, run), axis=1)
+
+
 class SamplePlan:
     """Device-resident sample weights in sweep order (``sample_order``) plus the face table remapped to that order
     and, per row, the bit mask of the faces it lies on (the fused face maxima); built once per dimension pass,
@@ -1069,6 +1164,25 @@ class SamplePlan:
         f_ptr = faces.ptr.cpu().numpy().astype(np.int64)
         f_rows = faces.rows.cpu().numpy().astype(np.int64)
         n_faces = faces.n_faces
+        # face ownership (FACE_OWNER): the minimal face of every row, the faces present per chunk and tile, the sub-face
+        # table; FACE_OWNER_GROUPED: the rows grouped by facet, interior rows first (sample_order_grouped)
+        self.min_face = self.chunk_faces = self.tile_faces = self.sub_faces = self.row_group = None
+        self.owner_order = False
+        if FACE_OWNER and n_faces <= 32 and self.k1 <= 8:
+            w_np = weights.detach().cpu().numpy()
+            lat = face_lattice(w_np, f_ptr, f_rows)
+            if lat is not None:
+                min_face, sub_faces = lat
+                if FACE_OWNER_GROUPED and len(f_ptr) > 2:   # (one face: every row is interior and the patch order stands)
+                    group = row_groups(min_face, sub_faces, faces.n_per_codim)
+                    perm = _grouped_order_cached(w_np, group)
+                    self.row_group = group[perm]          # (numpy, sweep order: ascending)
+                bits = np.left_shift(np.uint32(1), min_face[perm].astype(np.uint32))
+                self.min_face = torch.as_tensor(np.ascontiguousarray(min_face[perm]), device=dev)
+                self.chunk_faces = torch.as_tensor(_or_runs(bits, 256).view(np.int32), device=dev)
+                self.tile_faces = torch.as_tensor(_or_runs(bits, 64).view(np.int32), device=dev)
+                self.sub_faces = torch.as_tensor(sub_faces.view(np.int32), device=dev)
+                self.owner_order = True
         inv = np.empty(R, dtype=np.int64)
         inv[perm] = np.arange(R)
         self.inv = torch.as_tensor(inv, device=dev)
@@ -1526,6 +1640,21 @@ WIT_MIN_SIMPLICES = 1536   # fewer simplices than this in a sweep: no witness sw
 WIT_MAX_POINTS_PER_SIMPLEX = 400
 CELL_WITNESS = True  # sparse simplices go to the witness sweep first (whole simplex per wave, coarse samples + bounds)
 WIT_RUNS = True      # ... and it gets the run table of the plan (witness_runs): whole runs of samples dropped with one bound
+# Face ownership (shared face slots only): a sample on the boundary of a top simplex lies on a face that several top
+# simplices share, and with ascending vertex ids it has the same float32 coordinates in each of them.  ONE incident
+# simplex - the owner of the sample's minimal face, chosen on the device - evaluates it in the cell sweep; the others
+# build it as an absent sample.  An owner delivers to the faces of its own simplex only, so the last launch takes, per
+# face, the maximum over the face's closure (flooder_face_closure_f32).  Read when the plan is built (SamplePlan carries
+# the row tables); values are the same bit for bit either way.  cfg 2 0.977 -> 0.934 ms per step, cfg 3 3.64 -> 3.34,
+# cfg 5 8.43 -> 7.87 (profiles/face_owner_bench_ab.txt).
+FACE_OWNER = True
+# The row order under ownership.  False (default): the patch order of sample_order as it is - an absent row idles its
+# lane, a chunk's region shrinks to its owned rows, and few chunks vanish whole.  True: SamplePlan groups the rows by
+# facet (sample_order_grouped), so that 71 % of the removed units vanish as whole chunks - measured SLOWER: the chunks
+# that hold the boundary rows span whole facets, their regions overflow the stage (cfg 2: 660 gather give-ups against
+# 22, 2681 flagged tiles against 206) and the finish pays for it - cfg 2 1.372 ms per step against the parent's 0.977;
+# kept as an option.
+FACE_OWNER_GROUPED = False
 
 
 def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
@@ -1589,6 +1718,13 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         # its way - flooder_simplex_prepare_f32 below -: one launch instead of three)
         n_zeroed = ((1 if use_wit else 0) * QUEUE_WORDS + _native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS + 2 * S
                     + CTL_HIST + 8192 + n_slots)
+        # face ownership: behind the face words one 64-bit owner word per slot (8-byte aligned) and the result vector -
+        # a slot none of this call's simplices touches (a rank's share) keeps the zero fill's 0.0
+        use_owner = (FACE_OWNER and face_slots is not None and plan.owner_order and CELL_SUPER and SWEEP_PREPARE_FUSED
+                     and plan.sub_faces.numel() == F)
+        n_plain = n_zeroed
+        if use_owner:
+            n_zeroed += (n_zeroed & 1) + 3 * n_slots
         zeroed = (torch.empty if CELL_SUPER and SWEEP_PREPARE_FUSED else torch.zeros)(n_zeroed, dtype=torch.int32, device=dev)
         zeroed_all = zeroed
         if use_wit:
@@ -1599,7 +1735,8 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         zeroed = zeroed[_native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS:]
         top = zeroed[:2 * S].view(torch.int64)
         ctl = zeroed[2 * S:2 * S + CTL_HIST + 8192]
-        face_bits = zeroed[2 * S + CTL_HIST + 8192:]
+        face_bits = zeroed[2 * S + CTL_HIST + 8192:2 * S + CTL_HIST + 8192 + n_slots]
+        owner = zeroed_all[n_plain + (n_plain & 1):n_plain + (n_plain & 1) + 2 * n_slots] if use_owner else None
         hard = torch.empty(4 * FINISH_HARD_CAP, dtype=torch.int64, device=dev)
         top_list = torch.empty(S, dtype=torch.int32, device=dev)
         d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
@@ -1637,6 +1774,9 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             blk.top_count = fctl[_native.FINISH_CTL_TOP_COUNT:].data_ptr()
         if CELL_SUPER:
             blk.defer_ctl, blk.light_list, blk.heavy_list = ctl[CTL_DEFER:].data_ptr(), split[0].data_ptr(), split[1].data_ptr()
+        if use_owner:   # (the cell sweep's entry chooses the owners; the witness sweep evaluates all rows of its simplices)
+            blk.face_owner, blk.min_face = owner.data_ptr(), plan.min_face.data_ptr()
+            blk.chunk_faces, blk.tile_faces = plan.chunk_faces.data_ptr(), plan.tile_faces.data_ptr()
         if use_wit:   # (split[0]: the witness sweep's item list - scratch until the cell sweep's entry fills it)
             blk.n_coarse, blk.coarse_rows, blk.parents = plan.wit[2], plan.wit[0].data_ptr(), plan.wit[1].data_ptr()
             blk.wit_queue, blk.wit_item_list, blk.wit_stats = qwit.data_ptr(), split[0].data_ptr(), _native.ptr(wst) or None
@@ -1660,6 +1800,12 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             c_h = fctl[:_native.FINISH_CTL_QUEUES].tolist()
             LAST_STATS.hard_entries = (int(c_h[_native.FINISH_CTL_TOP_HARD_LEN]), int(c_h[_native.FINISH_CTL_REST_HARD_LEN]))
             LAST_STATS.finish_single_left = int(c_h[_native.FINISH_CTL_SINGLE_LEFT])
+        if use_owner:   # an owner delivers to the faces of its own simplex: every face takes the maximum over its closure
+            out_face = zeroed_all[n_zeroed - n_slots:].view(torch.float32)
+            with _span(timer, "face_max"):
+                _native.check(lib.flooder_face_closure_f32(_native.ptr(face_bits), _native.ptr(slot_t), _native.ptr(plan.sub_faces),
+                                                           S, F, _native.ptr(out_face), st), "flooder_face_closure_f32")
+            return out_face, None
         out_face = torch.empty(n_slots if face_slots is not None else (S, F), dtype=torch.float32, device=dev)
         with _span(timer, "face_max"):
             _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), n_slots, _native.ptr(out_face), st),

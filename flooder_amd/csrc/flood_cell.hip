@@ -410,6 +410,19 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
     const float* vs = ARG(verts) + (int64_t)s * k1 * DIM;
     const int n_live = R;  // live slots of this simplex
     if (q * CHUNK >= n_live) continue;
+    // face ownership (flood_common.hpp): `own` = the faces whose own samples this simplex evaluates.  A row whose minimal
+    // face is not among them is an ABSENT sample: never open, outside the region's box, delivered to no face, written as
+    // settled where a tile is flagged (the finish drops it on arrival); an item none of whose rows is owned is dropped.
+    const bool owned_rows = fused && ARG(acc.owner) != nullptr;
+    uint32_t own = 0xffffffffu;
+    if (owned_rows) {
+      const FaceAcc acc = ARG(acc);
+      own = acc.own_mask(s, lane);
+      const uint32_t* const run_faces = TILES ? acc.tile_faces : acc.chunk_faces;
+      uint32_t there = 0u;
+      for (int sub = 0; sub < n_sub; ++sub) there |= run_faces[q + sub];
+      if ((there & own) == 0u) continue;
+    }
     auto defer = [&](int qq, int seeded_flag, float c_next) {
       if (lane == 0) {
         const int pos = atomicAdd(ARG(dl.count), 1);
@@ -426,6 +439,7 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
     int row[SPL];    // row of the weight table / column of the output
     float blo[DIM], bhi[DIM];
     auto make_samples = [&]() {
+      const uint8_t* const min_face = owned_rows ? ARG(acc.min_face) : nullptr;
 #pragma unroll
       for (int i = 0; i < SPL; ++i) {
         int slot = q * CHUNK + i * 64 + lane;
@@ -433,6 +447,7 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
         if (slot >= n_live) slot = n_live - 1;  // duplicate of the last live sample, never stored
         const int r = slot;
         row[i] = r;
+        if (min_face) open[i] = open[i] && ((own >> min_face[r]) & 1u) != 0u;  // (else: absent)
 #pragma unroll
         for (int k = 0; k < DIM; ++k) p[i][k] = 0.f;
         if (k1 == 4) {  // tetrahedra: the weight row is one 16 B load (same fma order as the general loop)
@@ -490,18 +505,20 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
         make_samples();
 #pragma unroll
         for (int i = 0; i < SPL; ++i) {
+          // (open here: a live slot that is not absent - a slot behind the last row repeats that row, which counts
+          // through its own lane; an absent sample stays out of the region)
 #pragma unroll
           for (int k = 0; k < DIM; ++k) {
-            mn[k] = __builtin_fminf(mn[k], p[i][k]);
-            mx[k] = __builtin_fmaxf(mx[k], p[i][k]);
+            mn[k] = __builtin_fminf(mn[k], open[i] ? p[i][k] : __builtin_inff());
+            mx[k] = __builtin_fmaxf(mx[k], open[i] ? p[i][k] : -__builtin_inff());
           }
 #pragma unroll
           for (int f = 0; f <= DIM; ++f) {
             float dd = -po[f];
 #pragma unroll
             for (int k = 0; k < DIM; ++k) dd = __builtin_fmaf(pn[f][k], p[i][k] - org[k], dd);
-            dmn[f] = __builtin_fminf(dmn[f], dd);
-            dmx[f] = __builtin_fmaxf(dmx[f], dd);
+            dmn[f] = __builtin_fminf(dmn[f], open[i] ? dd : __builtin_inff());
+            dmx[f] = __builtin_fmaxf(dmx[f], open[i] ? dd : -__builtin_inff());
           }
         }
       }
@@ -713,7 +730,8 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
                                  : 0xffffffffu;
 #pragma unroll
       for (int i = 0; i < SPL; ++i) {
-        const bool settled = (q * CHUNK + i * 64 + lane < n_live) && !open[i];
+        bool settled = (q * CHUNK + i * 64 + lane < n_live) && !open[i];
+        if (acc.owner) settled = settled && ((own >> acc.min_face[row[i]]) & 1u) != 0u;  // (an absent sample delivers nothing)
         mb[i] = settled ? acc.memb[row[i]] : 0u;
         um |= mb[i];
       }
@@ -1702,12 +1720,42 @@ int launch_simplex_planes(int dim, const float* verts, int k1, int64_t n_simplic
 
 namespace {
 
+// Face ownership (flood_common.hpp: FaceAcc::owner): every (simplex, proper face) sends its simplex's key to the face's
+// owner word; the largest key stays.  The launch that splits the simplices by weight does it in blocks of its own behind
+// block 0: it follows the zero fill of the words and the witness sweep (whose simplices carry a negative weight by now)
+// on the stream and precedes every launch of the cell sweep, and it is one block of a few microseconds - the owner blocks
+// run beside it.  (Inside the launch that computes the weights the zero fill of the words would race with the atomics.)
+struct OwnerJob {
+  unsigned long long* owner = nullptr;
+  const int32_t* slot = nullptr;
+  int n_faces = 0;
+};
+__device__ __forceinline__ void choose_owners(const OwnerJob& oj, const float* __restrict__ weight, int n, int block,
+                                              int n_blocks, int tid, int nt) {
+  const int64_t total = (int64_t)n * oj.n_faces;
+  for (int64_t t = (int64_t)block * nt + tid; t < total; t += (int64_t)n_blocks * nt) {
+    const int s = (int)(t / oj.n_faces);
+    if (t - (int64_t)s * oj.n_faces == 0) continue;   // (face 0: the simplex itself)
+    atomicMax(&oj.owner[oj.slot[t]], owner_key(s, weight[s]));
+  }
+}
+inline int owner_blocks(const OwnerJob& oj, int n, int nt) {
+  if (!oj.owner) return 0;
+  const int64_t b = ((int64_t)n * oj.n_faces + 4 * nt - 1) / (4 * nt);
+  return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+
 // Order-preserving split of 0 .. n-1 by weight[i] <= limit: one block, ballot scans (n is a few thousand).
 // Runs of four chunks pay in sparse volumetric clouds (most runs fit the stage); where fewer than half of the simplices
 // are sparse (weight <= sparse_limit) the whole sweep stays chunk by chunk: every simplex on the heavy list.
 __global__ __launch_bounds__(1024) void split_simplices_kernel(const float* __restrict__ weight, int n, float limit,
                                                                float sparse_limit, int32_t* __restrict__ light,
-                                                               int32_t* __restrict__ heavy, int32_t* __restrict__ counts) {
+                                                               int32_t* __restrict__ heavy, int32_t* __restrict__ counts,
+                                                               OwnerJob oj) {
+  if (blockIdx.x > 0) {   // (whole blocks: none of them meets a barrier below)
+    choose_owners(oj, weight, n, (int)blockIdx.x - 1, (int)gridDim.x - 1, (int)threadIdx.x, 1024);
+    return;
+  }
   // (a negative weight marks a simplex the witness sweep has already handled: on neither list)
   __shared__ int s_cl[16], s_ch[16];
   __shared__ int s_sparse, s_act;
@@ -1771,7 +1819,11 @@ template <int NT>
 __global__ __launch_bounds__(NT) void class_order_kernel(const float* __restrict__ weight, int n, float limit,
                                                                float sparse_limit, int runs_allowed, int reorder,
                                                                int32_t* __restrict__ light, int32_t* __restrict__ heavy,
-                                                               int32_t* __restrict__ counts) {
+                                                               int32_t* __restrict__ counts, OwnerJob oj) {
+  if (blockIdx.x > 0) {   // (whole blocks: none of them meets a barrier below)
+    choose_owners(oj, weight, n, (int)blockIdx.x - 1, (int)gridDim.x - 1, (int)threadIdx.x, NT);
+    return;
+  }
   __shared__ int s_cnt[NT / 64][SPLIT_CLASSES + 1];
   constexpr int ID_LDS = 7680;
   __shared__ int s_id[ID_LDS];
@@ -1979,28 +2031,34 @@ int flooder::fused_cell(const flooder_fused_sweep_t& a, void* stream) {
   int32_t* const split = weight ? a.defer_ctl + FLOODER_DEFER_CTL_LIGHT : nullptr;   // light, heavy, done
   const int n = (int)a.n_simplices;
   const hipStream_t st = (hipStream_t)stream;
+  // face ownership: the owner words are filled by the split launch below, so it needs the weights (and one slot per
+  // distinct face, the row tables of the plan); a block without face_owner sweeps every row of every simplex
+  if (a.face_owner && (!weight || !a.face_slot || !a.min_face || !a.chunk_faces || !a.tile_faces))
+    return fail(FLOODER_E_ARG, "flooder_fused_cell: face_owner needs simplex_weight, face_slot, min_face, chunk_faces and tile_faces");
+  OwnerJob oj;
+  if (a.face_owner) { oj.owner = reinterpret_cast<unsigned long long*>(a.face_owner); oj.slot = a.face_slot; oj.n_faces = a.n_faces; }
   if (weight) {  // split the simplices (order kept) into the light and the heavy list
     const bool long_queue = a.n_simplices * (int64_t)((a.R + 255) / 256) >= (int64_t)g_cell_super_min_chunks;
     // (more simplices than the one-launch form stages in LDS - its runs would be read from memory, a chain of cache
     // misses: 50 us for cfg 5's 25 217 - take the pair; option 2: the pair always, for A/B runs and the tests)
     if (long_queue && (g_cell_split_launches == 2 || a.n_simplices > 7680)) {
-      hipLaunchKernelGGL(split_simplices_kernel, dim3(1), dim3(1024), 0, st, weight, n, (float)g_cell_super_weight,
-                         (float)g_cell_super_sparse, light, heavy, split);
+      hipLaunchKernelGGL(split_simplices_kernel, dim3(1 + owner_blocks(oj, n, 1024)), dim3(1024), 0, st, weight, n,
+                         (float)g_cell_super_weight, (float)g_cell_super_sparse, light, heavy, split, oj);
       // ... and the heavy list heaviest first: its densest simplices hold the chunks that one wave evaluates
       // exhaustively for 150 us and more, and the last of them to start was the tail of the chunk launch
       if (g_cell_weight_classes)
         hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, st, weight, n,
-                           (float)g_cell_super_weight, (float)g_cell_super_sparse, 2, 1, light, heavy, split);
+                           (float)g_cell_super_weight, (float)g_cell_super_sparse, 2, 1, light, heavy, split, OwnerJob{});
     } else if (long_queue) {
       // light list in the given order + heavy list heaviest first (its densest simplices hold the chunks that one wave
       // evaluates exhaustively for 150 us and more: started last they were the tail of the chunk launch) in ONE launch
-      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS_LONG>, dim3(1), dim3(SPLIT_THREADS_LONG), 0, st, weight, n,
-                         (float)g_cell_super_weight, (float)g_cell_super_sparse, (g_cell_weight_classes ? 2 : 0) | 1 | 4, 0,
-                         light, heavy, split);
+      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS_LONG>, dim3(1 + owner_blocks(oj, n, SPLIT_THREADS_LONG)),
+                         dim3(SPLIT_THREADS_LONG), 0, st, weight, n, (float)g_cell_super_weight, (float)g_cell_super_sparse,
+                         (g_cell_weight_classes ? 2 : 0) | 1 | 4, 0, light, heavy, split, oj);
     } else {
-      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1), dim3(SPLIT_THREADS), 0, st, weight, n,
-                         (float)g_cell_super_weight, (float)g_cell_super_sparse, g_cell_weight_classes ? 2 : 0, 0, light,
-                         heavy, split);
+      hipLaunchKernelGGL(class_order_kernel<SPLIT_THREADS>, dim3(1 + owner_blocks(oj, n, SPLIT_THREADS)), dim3(SPLIT_THREADS), 0,
+                         st, weight, n, (float)g_cell_super_weight, (float)g_cell_super_sparse, g_cell_weight_classes ? 2 : 0,
+                         0, light, heavy, split, oj);
     }
   }
   DeferList dl{a.defer_list, a.defer_c, a.defer_list ? a.defer_ctl + FLOODER_DEFER_CTL_COUNT : nullptr, light, heavy,
@@ -2011,10 +2069,12 @@ int flooder::fused_cell(const flooder_fused_sweep_t& a, void* stream) {
     dl.tile_c = a.defer_c + n_chunk_slots;
     dl.tile_count = a.defer_ctl + FLOODER_DEFER_CTL_TILE_COUNT;
   }
-  return sweep_cell_entry(a,
-                          FaceAcc{a.memb, a.face_bits, a.n_faces, reinterpret_cast<unsigned long long*>(a.top), a.top_list,
-                                  a.top_count, a.face_slot, a.flag_key, a.flag_hist},
-                          dl, "flooder_sweep_cell_faces_f32: bad argument", stream);
+  FaceAcc acc{a.memb, a.face_bits, a.n_faces, reinterpret_cast<unsigned long long*>(a.top), a.top_list,
+              a.top_count, a.face_slot, a.flag_key, a.flag_hist};
+  if (a.face_owner) {
+    acc.owner = oj.owner; acc.min_face = a.min_face; acc.chunk_faces = a.chunk_faces; acc.tile_faces = a.tile_faces;
+  }
+  return sweep_cell_entry(a, acc, dl, "flooder_sweep_cell_faces_f32: bad argument", stream);
 }
 
 extern "C" {

@@ -242,10 +242,39 @@ struct FaceAcc {
   // bounds' top 12 bits: the finish starts the tiles with the largest bounds - the longest searches - first
   uint32_t* flag_key = nullptr;
   int32_t* flag_hist = nullptr;
+  // face ownership (null: off; needs `slot`): owner[slot] = key of the ONE incident simplex that evaluates the samples
+  // whose minimal face is that slot's face (owner_key below; 0 = nobody has asked), min_face[r] = minimal face of sample
+  // row r (0: the full simplex - interior rows are always evaluated), chunk_faces / tile_faces = OR of 1 << min_face
+  // over every aligned run of 256 / 64 rows.  A shared face's samples have bit-identical coordinates in every incident
+  // simplex, so the others skip them; what they would have delivered to their own words comes back through the
+  // closure of the face values (flood_finish.hip: face_closure_kernel).
+  const unsigned long long* owner = nullptr;
+  const uint8_t* min_face = nullptr;
+  const uint32_t* chunk_faces = nullptr;
+  const uint32_t* tile_faces = nullptr;
+  // mask of the faces of simplex s whose own samples s evaluates (all 64 lanes active; wave-uniform result)
+  __device__ __forceinline__ uint32_t own_mask(int64_t s, int lane) const {
+    bool mine = false;
+    if (lane > 0 && lane < n_faces) {
+      const unsigned long long k =
+          __hip_atomic_load(owner + slot[s * (int64_t)n_faces + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      mine = (uint32_t)k == ~(uint32_t)s;
+    }
+    return (uint32_t)__ballot(mine) | 1u;
+  }
   __device__ __forceinline__ int64_t slot_of(int64_t s, int f) const {
     return slot ? (int64_t)slot[s * (int64_t)n_faces + f] : s * (int64_t)n_faces + f;
   }
 };
+
+// Key of simplex s (its row in this call) for FaceAcc::owner: the largest key wins (atomicMax on zeroed words) - a
+// simplex the witness sweep has handled (weight < 0: it has evaluated all its rows already) before a lighter one (the
+// dense neighbour is the one that skips) before a lower row.
+__device__ __forceinline__ unsigned long long owner_key(int s, float w) {
+  const uint32_t wb = __float_as_uint(w) < 0x7f800000u ? __float_as_uint(w) : 0x7f800000u;
+  const uint32_t hi = w < 0.f ? 0xffffffffu : 0x7fffffffu - wb;
+  return ((unsigned long long)hi << 32) | (unsigned long long)(~(uint32_t)s);
+}
 
 template <template <int> class F, typename... Args>
 int dispatch_dim(int dim, Args&&... args) {

@@ -880,6 +880,28 @@ __global__ void face_values_kernel(const uint32_t* __restrict__ bits, int64_t n,
     out[i] = __builtin_sqrtf(__uint_as_float(bits[i]));
 }
 
+// Face values under face ownership (include/flooder_hip.h: flooder_face_closure_f32): a group of W lanes per simplex,
+// lane = face; every lane loads its face's raw word once and takes the maximum over the lanes of the faces inside its own
+// through the lane network - raw words only, no atomics, and every writer of a slot writes the same bits.
+template <int W>
+__global__ __launch_bounds__(256) void face_closure_kernel(const uint32_t* __restrict__ bits, const int32_t* __restrict__ slot,
+                                                           const uint32_t* __restrict__ sub_faces, int64_t n_simplices,
+                                                           int n_faces, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int f = lane & (W - 1), base = lane & ~(W - 1);
+  const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / W;   // (whole groups: blockDim is a multiple of W)
+  const bool on = s < n_simplices && f < n_faces;
+  const int64_t my_slot = on ? (int64_t)slot[s * n_faces + f] : 0;
+  const uint32_t raw = on ? bits[my_slot] : 0u;
+  const uint32_t sub = on ? sub_faces[f] : 0u;
+  uint32_t v = raw;
+  for (int g = 0; g < n_faces; ++g) {  // (uniform trip count: every lane takes part in every exchange)
+    const uint32_t t = (uint32_t)__shfl((int)raw, base + g);
+    v = ((sub >> g) & 1u) && t > v ? t : v;
+  }
+  if (on) out[my_slot] = __builtin_sqrtf(__uint_as_float(v));
+}
+
 template <int DIM>
 struct FinishOp {
   static int run(const flooder_fused_sweep_t& a, const Levels& lv, FaceAcc acc, hipStream_t st) {
@@ -1007,6 +1029,23 @@ int flooder_face_values_f32(const uint32_t* face_bits, int64_t n, float* out_fac
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(face_values_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, face_bits, n, out_face);
   return check_launch("face_values");
+}
+
+int flooder_face_closure_f32(const uint32_t* face_bits, const int32_t* face_slot, const uint32_t* sub_faces,
+                             int64_t n_simplices, int n_faces, float* out_face, void* stream) {
+  if (n_simplices == 0) return FLOODER_OK;
+  if (!face_bits || !face_slot || !sub_faces || !out_face || n_simplices < 0 || n_faces < 1 || n_faces > 32)
+    return fail(FLOODER_E_ARG, "flooder_face_closure_f32: bad argument");
+  const int w = n_faces <= 16 ? 16 : 32;
+  const int64_t blocks = (n_simplices * w + 255) / 256;
+  if (blocks > 0x7fffffffLL) return fail(FLOODER_E_ARG, "flooder_face_closure_f32: too many simplices");
+  if (w == 16)
+    hipLaunchKernelGGL(face_closure_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, face_bits, face_slot,
+                       sub_faces, n_simplices, n_faces, out_face);
+  else
+    hipLaunchKernelGGL(face_closure_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, face_bits, face_slot,
+                       sub_faces, n_simplices, n_faces, out_face);
+  return check_launch("face_closure");
 }
 
 }  // extern "C"

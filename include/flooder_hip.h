@@ -504,6 +504,16 @@ int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, co
 /* out_face[i] = sqrt(float(face_bits[i])), i < n: the filtration values (core.py:257, 272: distances, not squares). */
 int flooder_face_values_f32(const uint32_t* face_bits, int64_t n, float* out_face, void* stream);
 
+/* The same for face words filled under face ownership (flooder_fused_sweep_t, face_owner), where a simplex's words hold
+ * only what that simplex delivered: one thread per (simplex s, face f) writes
+ *   out_face[slot[s, f]] = sqrt(max over the faces g of s inside f, f included, of face_bits[slot[s, g]]),
+ * the maximum over the face's closure.  sub_faces: n_faces words, bit g of word f set when face g lies inside face f.
+ * Only the raw words are read, so no order between the threads is needed; the writers of one slot write identical bits
+ * (every sample of a face is delivered to that face's own word by the owner of the sample's minimal face).  Slots of no
+ * (s, f) are not written: the caller zeroes out_face.  face_slot (n_simplices x n_faces, as in the sweep) is required. */
+int flooder_face_closure_f32(const uint32_t* face_bits, const int32_t* face_slot, const uint32_t* sub_faces,
+                             int64_t n_simplices, int n_faces, float* out_face, void* stream);
+
 /* weight[s] = rough number of cloud points inside the bounding box of simplex s (walk of the box tree down to its
  * 1024-point nodes, overlapped volume fractions).  The host queues the simplices by descending weight: work per
  * simplex is heavy-tailed and the long ones should start first.  Replaces the sort by ball centre of core.py:174-179
@@ -687,6 +697,20 @@ typedef struct flooder_fused_sweep_s {
    * struct ends before this field): they launch it.  The library keeps no memory of what it wrote between calls. */
   int32_t planes_ready;
   int32_t reserved;
+  /* face ownership (fields added behind planes_ready: a caller that does not have them, or passes face_owner NULL, gets
+   * none).  Needs face_slot with ONE slot per distinct face of the complex, built from cells with ascending vertex ids
+   * (a shared face's samples then have bit-identical coordinates in every incident simplex), and simplex_weight (the
+   * launch that splits the simplices by weight chooses the owners).  face_owner: one ZEROED 64-bit word per slot, 8-byte
+   * aligned; flooder_fused_cell writes, per proper face, the key of the incident simplex that evaluates the face's own
+   * samples - a simplex the witness sweep has handled before a lighter one before a lower row - and the cell sweep builds
+   * every row whose MINIMAL face (min_face: R bytes, the face of the fewest vertices the row lies on; face 0 = the full
+   * simplex, always evaluated) this simplex does not own as an absent sample.  chunk_faces / tile_faces: per aligned run
+   * of 256 / 64 rows the OR of (1 << min_face) over its rows.  The face words then hold, per simplex, only what that
+   * simplex delivered: read them through flooder_face_closure_f32. */
+  uint64_t* face_owner;
+  const uint8_t* min_face;
+  const uint32_t* chunk_faces;
+  const uint32_t* tile_faces;
 } flooder_fused_sweep_t;
 
 /* flooder_sweep_witness_f32, flooder_sweep_cell_faces_f32, flooder_finish_faces_f32 on the fields of *p (host memory;
