@@ -10,6 +10,10 @@ constexpr int PLANE_ROW = 24;
 
 template <int DIM>
 __device__ __forceinline__ void simplex_planes_row(const float* __restrict__ verts, int k1, int64_t s, float* __restrict__ tab) {
+  // The source decides the arithmetic: no contraction by the compiler in here, every fused step is written as an fma.
+  // Both writers of the table and the float32 replica of the tests (tests/wit_reference.py: plane_row, pinned word for
+  // word by tests/test_gpu_plane_rows.py) then compute the same 24 words.
+#pragma clang fp contract(off)
   const float* vs = verts + s * (int64_t)k1 * DIM;
   float pn[DIM + 1][DIM], po[DIM + 1], pslack[DIM + 1], org[DIM];
   float sext2 = 0.f;  // squared extent of the simplex around org
@@ -49,16 +53,16 @@ __device__ __forceinline__ void simplex_planes_row(const float* __restrict__ ver
           l1 = __builtin_fmaf(e1[k], e1[k], l1);
           l2 = __builtin_fmaf(e2[k], e2[k], l2);
         }
-        nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
-        nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
-        nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        nrm[0] = __builtin_fmaf(e1[1], e2[2], -(e1[2] * e2[1]));
+        nrm[1] = __builtin_fmaf(e1[2], e2[0], -(e1[0] * e2[2]));
+        nrm[2] = __builtin_fmaf(e1[0], e2[1], -(e1[1] * e2[0]));
         l12 = l1 * l2;
       } else {
         const float ex = vs[id[1] * 2 + 0] - vs[id[0] * 2 + 0];
         const float ey = vs[id[1] * 2 + 1] - vs[id[0] * 2 + 1];
         nrm[0] = ey;
         nrm[1] = -ex;
-        l12 = ex * ex + ey * ey;
+        l12 = __builtin_fmaf(ex, ex, ey * ey);
       }
       float len2 = 0.f, side = 0.f;
 #pragma unroll

@@ -97,6 +97,51 @@ template <int DIM>
 struct Region {
   float pn[DIM + 1][DIM], po[DIM + 1], ps[DIM + 1], org[DIM], sext, blo[DIM], bhi[DIM], slo[DIM + 1], shi[DIM + 1], epsb;
   static constexpr int WORDS = (DIM + 1) * DIM + 4 * (DIM + 1) + 3 * DIM + 2;
+  // phase 1 of the witness sweep ("1. region"): the simplex's table row `pt` (simplex_planes_row) and its k1 vertices
+  // -> the polytope.  The source decides the arithmetic here, not the compiler's contraction pass
+  // (tests/wit_reference.py replays it; flooder_wit_probe_f32 shows the words).
+  __device__ __forceinline__ void fill(const float* __restrict__ pt, const float* __restrict__ vs, int k1) {
+#pragma clang fp contract(off)
+    typename RowVec<4>::type t[PLANE_ROW / 4];
+#pragma unroll
+    for (int i = 0; i < PLANE_ROW / 4; ++i) t[i] = load_uniform_row<4>(pt + 4 * i);
+    auto at = [&](int i) { return t[i >> 2][i & 3]; };
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) org[k] = at(k);
+    sext = at(3);
+#pragma unroll
+    for (int f = 0; f <= DIM; ++f) {
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) pn[f][k] = at(4 + 5 * f + k);
+      po[f] = at(4 + 5 * f + 3);
+      ps[f] = at(4 + 5 * f + 4) + 1e-6f;
+    }
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) { blo[k] = __builtin_inff(); bhi[k] = -__builtin_inff(); }
+#pragma unroll
+    for (int f = 0; f <= DIM; ++f) { slo[f] = __builtin_inff(); shi[f] = -__builtin_inff(); }
+    float amax = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      float v[DIM];
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) {
+        v[k] = vs[j * DIM + k];
+        blo[k] = __builtin_fminf(blo[k], v[k]);
+        bhi[k] = __builtin_fmaxf(bhi[k], v[k]);
+        amax = __builtin_fmaxf(amax, __builtin_fabsf(v[k]));
+      }
+#pragma unroll
+      for (int f = 0; f <= DIM; ++f) {
+        float dd = -po[f];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) dd = __builtin_fmaf(pn[f][k], v[k] - org[k], dd);
+        slo[f] = __builtin_fminf(slo[f], dd);
+        shi[f] = __builtin_fmaxf(shi[f], dd);
+      }
+    }
+    // (a sample is a rounded combination of the vertices: it may leave their box by a few ulps)
+    epsb = 8.f * 1.1920929e-7f * amax;
+  }
   __device__ __forceinline__ void store(float* c) const {
     int i = 0;
 #pragma unroll
@@ -155,17 +200,24 @@ struct Region {
 // (eps = 2^-23) - where its slack counts as 0, and the slack along a face normal is itself computed with up to
 // 2 eps sext <= 7 eps amax of rounding.  Those 10.5 eps amax are taken off the excess here, as 2 epsb = 16 eps amax on
 // every side: with them  dist(p, x) >= excess(x) + max(slack(p), 0)  holds for the numbers as computed, whatever the
-// size of the coordinates against the simplex (tests/test_wit_sorted_stage_cpu.py: clouds offset by 1e3).
+// size of the coordinates against the simplex (tests/test_wit_sorted_stage_cpu.py: clouds offset by 1e3; with the
+// device's own numbers tests/test_gpu_wit_probe.py, which fails on those clouds with a pad of 0).
 constexpr float EXCESS_PAD = 2.f;   // in units of epsb (the gather box grows by as much: every point of excess < c_max is gathered)
 template <int DIM>
 struct Excess {
   float pn[DIM + 1][DIM], po[DIM + 1], org[DIM], blo_e[DIM], bhi_e[DIM], slo_t[DIM + 1], shi_t[DIM + 1], inv_den[DIM + 1];
   __device__ __forceinline__ Excess(const Region<DIM>& g, float c_max) {
+    // (no contraction by the compiler: the fused steps are the fma written here - tests/wit_reference.py replays them)
+#pragma clang fp contract(off)
 #pragma unroll
-    for (int k = 0; k < DIM; ++k) { blo_e[k] = g.blo[k] - (1.f + EXCESS_PAD) * g.epsb; bhi_e[k] = g.bhi[k] + (1.f + EXCESS_PAD) * g.epsb; org[k] = g.org[k]; }
+    for (int k = 0; k < DIM; ++k) {
+      blo_e[k] = __builtin_fmaf(-(1.f + EXCESS_PAD), g.epsb, g.blo[k]);
+      bhi_e[k] = __builtin_fmaf(1.f + EXCESS_PAD, g.epsb, g.bhi[k]);
+      org[k] = g.org[k];
+    }
 #pragma unroll
     for (int f = 0; f <= DIM; ++f) {
-      const float tol = g.ps[f] * (g.sext + c_max) + EXCESS_PAD * g.epsb;
+      const float tol = __builtin_fmaf(g.ps[f], g.sext + c_max, EXCESS_PAD * g.epsb);
       slo_t[f] = g.slo[f] - tol;
       shi_t[f] = g.shi[f] + tol;
       inv_den[f] = 1.f / (1.001f + g.ps[f]);
@@ -309,47 +361,10 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     // extents along the face normals -> LDS
     float c_max;
     {
+      // (no contraction by the compiler in this block either: what feeds Region and Excess is what is written)
+#pragma clang fp contract(off)
       Region<DIM> rg;
-      const float* pt = plane_tab + s * PLANE_ROW;
-      typename RowVec<4>::type t[PLANE_ROW / 4];
-#pragma unroll
-      for (int i = 0; i < PLANE_ROW / 4; ++i) t[i] = load_uniform_row<4>(pt + 4 * i);
-      auto at = [&](int i) { return t[i >> 2][i & 3]; };
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) rg.org[k] = at(k);
-      rg.sext = at(3);
-#pragma unroll
-      for (int f = 0; f <= DIM; ++f) {
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) rg.pn[f][k] = at(4 + 5 * f + k);
-        rg.po[f] = at(4 + 5 * f + 3);
-        rg.ps[f] = at(4 + 5 * f + 4) + 1e-6f;
-      }
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) { rg.blo[k] = __builtin_inff(); rg.bhi[k] = -__builtin_inff(); }
-#pragma unroll
-      for (int f = 0; f <= DIM; ++f) { rg.slo[f] = __builtin_inff(); rg.shi[f] = -__builtin_inff(); }
-      float amax = 0.f;
-      for (int j = 0; j < k1; ++j) {
-        float v[DIM];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-          v[k] = vs[j * DIM + k];
-          rg.blo[k] = __builtin_fminf(rg.blo[k], v[k]);
-          rg.bhi[k] = __builtin_fmaxf(rg.bhi[k], v[k]);
-          amax = __builtin_fmaxf(amax, __builtin_fabsf(v[k]));
-        }
-#pragma unroll
-        for (int f = 0; f <= DIM; ++f) {
-          float dd = -rg.po[f];
-#pragma unroll
-          for (int k = 0; k < DIM; ++k) dd = __builtin_fmaf(rg.pn[f][k], v[k] - rg.org[k], dd);
-          rg.slo[f] = __builtin_fminf(rg.slo[f], dd);
-          rg.shi[f] = __builtin_fmaxf(rg.shi[f], dd);
-        }
-      }
-      // (a sample is a rounded combination of the vertices: it may leave their box by a few ulps)
-      rg.epsb = 8.f * 1.1920929e-7f * amax;
+      rg.fill(plane_tab + s * PLANE_ROW, vs, k1);
       float ext = 0.f, vol = 1.f;
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
@@ -467,10 +482,12 @@ __global__ __launch_bounds__(WTHREADS, WBLOCKS) void wit_sweep_kernel(
     };
     bool gathered = false;
     for (int att = 0; att < 1; ++att) {  // (one try: a region with more leaves than the cap is no case for this sweep)
+      // (Excess's blo_e / bhi_e, by the same fma, grown by c_max)
+#pragma clang fp contract(off)
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
-        qlo[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 1] - (1.f + EXCESS_PAD) * s_rg[Region<DIM>::WORDS - 1] - c_max;
-        qhi[k] = s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 2] + (1.f + EXCESS_PAD) * s_rg[Region<DIM>::WORDS - 1] + c_max;
+        qlo[k] = __builtin_fmaf(-(1.f + EXCESS_PAD), s_rg[Region<DIM>::WORDS - 1], s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 1]) - c_max;
+        qhi[k] = __builtin_fmaf(1.f + EXCESS_PAD, s_rg[Region<DIM>::WORDS - 1], s_rg[Region<DIM>::WORDS - 2 - 3 * DIM + 3 * k + 2]) + c_max;
       }
       int* fa = s_front;
       int* fb = s_front + WFRONT;
@@ -1351,6 +1368,79 @@ __global__ __launch_bounds__(1024) void wit_list_kernel(const float* __restrict_
   }
 }
 
+// Test-facing probe of the margin arithmetic (flooder_wit_probe_f32; precedent: flooder_selftest): one workgroup of 64
+// per simplex runs phase 1 as the sweep does - Region::fill on the simplex's table row, c_max as a fraction of the box
+// extent (the sweep's `cmax_ext * ext` branch), bin_scale, the gather box, Excess - and writes out every number the
+// sweep's pruning rests on, through Region::store, the Excess members and the kernel's own expressions: per point of
+// the simplex's list excess and bin, per weight row the sample (built as make_sample builds it), its slack and
+// limit(slack, k / bin_scale) for k = 0 .. NBIN.  tests/test_gpu_wit_probe.py compares every word with the replica.
+template <int DIM>
+__global__ __launch_bounds__(64) void wit_probe_kernel(const float* __restrict__ verts, const float* __restrict__ planes,
+                                                       float cmax_frac, const float* __restrict__ pts,
+                                                       const int64_t* __restrict__ pt_off, const float* __restrict__ weights,
+                                                       int R, float* __restrict__ region, float* __restrict__ excess_w,
+                                                       float* __restrict__ scalars, float* __restrict__ pt_excess,
+                                                       int32_t* __restrict__ pt_bin, float* __restrict__ samples,
+                                                       float* __restrict__ limits) {
+#pragma clang fp contract(off)
+  constexpr int k1 = DIM + 1;
+  constexpr int EW = 2 * DIM + 3 * (DIM + 1), CW = 2 + 2 * DIM;
+  const int64_t s = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* vs = verts + s * (int64_t)k1 * DIM;
+  Region<DIM> rg;
+  rg.fill(planes + s * PLANE_ROW, vs, k1);
+  float ext = 0.f;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) ext = __builtin_fmaxf(ext, rg.bhi[k] - rg.blo[k]);
+  const float c_max = cmax_frac * ext;
+  const float bin_scale = (float)NBIN / c_max;
+  const Excess<DIM> excess(rg, c_max);
+  if (tid == 0) {
+    rg.store(region + s * Region<DIM>::WORDS);
+    float* e = excess_w + s * EW;
+    int i = 0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) { e[i++] = excess.blo_e[k]; e[i++] = excess.bhi_e[k]; }
+#pragma unroll
+    for (int f = 0; f <= DIM; ++f) { e[i++] = excess.slo_t[f]; e[i++] = excess.shi_t[f]; e[i++] = excess.inv_den[f]; }
+    float* c = scalars + s * CW;
+    c[0] = c_max;
+    c[1] = bin_scale;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {   // (the gather box of the sweep)
+      c[2 + 2 * k] = __builtin_fmaf(-(1.f + EXCESS_PAD), rg.epsb, rg.blo[k]) - c_max;
+      c[3 + 2 * k] = __builtin_fmaf(1.f + EXCESS_PAD, rg.epsb, rg.bhi[k]) + c_max;
+    }
+  }
+  for (int64_t i = pt_off[s] + tid; i < pt_off[s + 1]; i += 64) {
+    float x[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) x[k] = pts[i * DIM + k];
+    const float e = excess(x);
+    const float eb = e * bin_scale;
+    pt_excess[i] = e;
+    pt_bin[i] = eb < (float)NBIN ? (int)eb : NBIN;   // (the sweep forms (int)eb only below NBIN)
+  }
+  for (int r = tid; r < R; r += 64) {
+    float p[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) p[k] = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) p[k] = __builtin_fmaf(w, vs[j * DIM + k], p[k]);
+    }
+    const float dl = rg.slack(p);
+    float* o = samples + (s * R + r) * (int64_t)(DIM + 1);
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) o[k] = p[k];
+    o[DIM] = dl;
+    float* l = limits + (s * R + r) * (int64_t)(NBIN + 1);
+    for (int k = 0; k <= NBIN; ++k) l[k] = Region<DIM>::limit(dl, (float)k / bin_scale);
+  }
+}
+
 template <int DIM>
 struct WitOp {
   static int run(const flooder_fused_sweep_t& a, const Levels& lv, WitPlan plan, WitOut out, FaceAcc acc,
@@ -1438,6 +1528,38 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
   a.flag_key = flag_key; a.flag_hist = flag_hist; a.top = top; a.top_list = top_list; a.top_count = top_count;
   a.simplex_weight = simplex_weight; a.wit_item_list = item_list; a.plane_scratch = plane_scratch; a.wit_stats = stats;
   return fused_witness(a, stream);
+}
+
+// Layout of `out` (float32 words; S simplices of dim + 1 vertices, P points in all, R weight rows, W = words of
+// Region::store, E = 2 dim + 3 (dim + 1), C = 2 + 2 dim): plane rows 24 S | Region W S | Excess (blo_e, bhi_e per axis;
+// slo_t, shi_t, inv_den per face) E S | c_max, bin_scale, (qlo, qhi) per axis C S | excess per point P | per (simplex,
+// row) sample and slack (dim + 1) R S | per (simplex, row) limit(slack, k / bin_scale), k = 0 .. 64: 65 R S.
+// `bins`: (int)(excess * bin_scale) per point, 64 where the product is not below 64.  pt_off: S + 1 offsets into pts.
+int flooder_wit_probe_f32(const float* verts, int dim, int64_t n_simplices, float cmax_frac, const float* pts,
+                          const int64_t* pt_off, int64_t n_points, const float* weights, int R, float* out, int32_t* bins,
+                          void* stream) {
+  if (!verts || !pts || !pt_off || !weights || !out || !bins || n_simplices < 1 || n_simplices > 0x7fffffffLL ||
+      n_points < 0 || R < 1 || !(cmax_frac > 0.f) || (dim != 2 && dim != 3))
+    return fail(FLOODER_E_ARG, "flooder_wit_probe_f32: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t S = n_simplices;
+  const int W = dim == 2 ? Region<2>::WORDS : Region<3>::WORDS, E = 2 * dim + 3 * (dim + 1), C = 2 + 2 * dim;
+  float* planes = out;
+  float* region = planes + PLANE_ROW * S;
+  float* excess_w = region + W * S;
+  float* scalars = excess_w + E * S;
+  float* pt_excess = scalars + C * S;
+  float* samples = pt_excess + n_points;
+  float* limits = samples + (int64_t)(dim + 1) * R * S;
+  const int rc = launch_simplex_planes(dim, verts, dim + 1, S, planes, st);
+  if (rc != FLOODER_OK) return rc;
+  if (dim == 2)
+    hipLaunchKernelGGL((wit_probe_kernel<2>), dim3((unsigned)S), dim3(64), 0, st, verts, planes, cmax_frac, pts, pt_off, weights,
+                       R, region, excess_w, scalars, pt_excess, bins, samples, limits);
+  else
+    hipLaunchKernelGGL((wit_probe_kernel<3>), dim3((unsigned)S), dim3(64), 0, st, verts, planes, cmax_frac, pts, pt_off, weights,
+                       R, region, excess_w, scalars, pt_excess, bins, samples, limits);
+  return check_launch("wit_probe");
 }
 
 }  // extern "C"

@@ -533,6 +533,17 @@ int flooder_simplex_prepare_f32(const float* nodes, int64_t n_pts, int dim, cons
  * caller's to say: flooder_fused_sweep_t, planes_ready). */
 void flooder_simplex_planes_forget(void);
 
+/* Test-facing probe of the witness sweep's margin arithmetic (dim 2 / 3): phase 1 of the sweep - plane rows, Region,
+ * Excess, c_max = cmax_frac x the longest side of the vertices' box, bin_scale, gather box - for S simplices of dim + 1
+ * vertices, then excess and bin of the points pts[pt_off[s] .. pt_off[s + 1]) of every simplex s, and for every weight
+ * row (R, dim + 1) the sample, its slack and limit(slack, k / bin_scale), k = 0 .. 64.  `out` (float32 words, in this
+ * order; W = (dim + 1) dim + 4 (dim + 1) + 3 dim + 2): 24 S plane rows | W S Region words | (2 dim + 3 (dim + 1)) S
+ * Excess words | (2 + 2 dim) S scalars | n_points excesses | (dim + 1) R S samples and slacks | 65 R S limits.
+ * `bins`: n_points int32, 64 where excess x bin_scale is not below 64.  What the words are: csrc/flood_wit.hip. */
+int flooder_wit_probe_f32(const float* verts, int dim, int64_t n_simplices, float cmax_frac, const float* pts,
+                          const int64_t* pt_off, int64_t n_points, const float* weights, int R, float* out, int32_t* bins,
+                          void* stream);
+
 /* Device self-test of the 64-lane DPP reductions: out128[0:64] = min(in64), out128[64:128] = max. */
 int flooder_selftest(const float* in64, float* out128, void* stream);
 

@@ -23,15 +23,18 @@ def dev():
     return torch.device("cuda:0")
 
 
-def fused_chain(index, verts, plan, n_faces, planes_ready, between=None):
+def fused_chain(index, verts, plan, n_faces, planes_ready, between=None, planes=None):
     """prepare on `verts` -> between(verts, planes) -> witness, cell, finish (all three with `planes_ready`; all valid
-    inputs) -> face values.  Returns (face value bits (S, F) int32, the witness sweep's 24 counters)."""
+    inputs) -> face values.  `planes`: the caller's buffer for the 24 S plane words (tests/test_gpu_plane_rows.py puts
+    guard words behind it).  Returns (face value bits (S, F) int32, the witness sweep's 24 counters, planes)."""
     lib, dev = _native.load(), verts.device
     st = _native.current_stream_ptr(dev)
     S, k1, _ = verts.shape
     R, F, QW = plan.w_perm.shape[0], n_faces, core.QUEUE_WORDS
     tiles, chunks = (R + 63) // 64, (R + 255) // 256
-    planes = torch.empty(24 * S, dtype=torch.float32, device=dev)
+    if planes is None:
+        planes = torch.empty(24 * S, dtype=torch.float32, device=dev)
+    assert planes.numel() == 24 * S and planes.is_contiguous()
     n_zeroed = 7 * QW + 24 + 2 * S + 48 + 8192 + S * F
     zeroed_all = torch.full((n_zeroed,), 7, dtype=torch.int32, device=dev)   # (the prepare launch clears it)
     qwit, z = zeroed_all[:QW], zeroed_all[QW:]
@@ -72,7 +75,7 @@ def fused_chain(index, verts, plan, n_faces, planes_ready, between=None):
     _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), S * F, _native.ptr(out), st),
                   "flooder_face_values_f32")
     torch.cuda.synchronize()
-    return out.view(torch.int32).cpu(), stats[16:40].cpu()
+    return out.view(torch.int32).cpu(), stats[16:40].cpu(), planes
 
 
 @pytest.mark.parametrize("dim", [2, 3])
@@ -104,11 +107,11 @@ def test_plane_rows_are_handed_over_by_the_caller(dim, dev, monkeypatch):
     try:
         assert lib.flooder_set_option(b"wit_surface_pct", 0) == 0
         nan_rows = lambda verts, planes: planes.fill_(float("nan"))   # noqa: E731
-        ready, wit_1 = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 1)
-        launched, wit_0 = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 0, between=nan_rows)
-        rewritten, wit_2 = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 0,
+        ready, wit_1, _ = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 1)
+        launched, wit_0, _ = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 0, between=nan_rows)
+        rewritten, wit_2, _ = fused_chain(index, verts_a.clone(), plan, faces.n_faces, 0,
                                        between=lambda verts, planes: verts.copy_(verts_b))
-        fresh, _ = fused_chain(index, verts_b.clone(), plan, faces.n_faces, 1)
+        fresh, _, _ = fused_chain(index, verts_b.clone(), plan, faces.n_faces, 1)
     finally:
         set_options(lib, keep)
     for what, counters in (("planes_ready 1", wit_1), ("planes_ready 0", wit_0), ("rewritten verts", wit_2)):
