@@ -52,6 +52,10 @@ constexpr int EXH_MAX = 4 * CAPW;         // kept points evaluated exhaustively 
 constexpr int UNR = 4;            // candidate rows in flight per lane in the staging loops
 constexpr int KEEP0 = CAPW - CAPW / 3;      // first stage slot under the kept-candidate list (its CAPW ints = a third of the stage)
 constexpr int BRUTE_CAP = KEEP0 - 4;  // compacted points the classification pass may leave in the stage
+#ifndef FLOODER_CELL_CULL_MIN
+#define FLOODER_CELL_CULL_MIN (64 * UNR / LEAF)
+#endif
+constexpr int CULL_MIN = FLOODER_CELL_CULL_MIN;  // leaf lists up to this length are not culled by the region's planes (see there)
 
 // Density grid of the cloud (flooder_density_grid_f32: G^DIM point counts over the cloud's box).  Where its cells are
 // well filled a chunk reads the local density from the cells under its box - nine loads - instead of walking the
@@ -975,6 +979,49 @@ __global__ __launch_bounds__(256, FLOODER_CELL_WAVES) void cell_sweep_kernel(Cel
       };
 
       n_leaves = gather();
+#if FLOODER_GATHER_PLANES
+      // A leaf whose box lies outside one slab holds only points that keep_point drops: take it off the list before
+      // the classification loads its 16 rows (node_meets_slabs, flood_planes.hpp).  One lane per gathered leaf, its box
+      // read again (the gather has just had it: a cache hit), the list compacted in place - entry `n_out + rank` lies
+      // at or below the entry the lane has read, and the reads of a pass are out before its writes.  (Inside the
+      // gather - per tested node, 64 children at a time, inner levels too - the same test cost more than the
+      // classification saved: most children fail the box test already.  DESIGN section 3.2.)  The classification
+      // takes 64 * UNR candidates a step: a list that is one step long stays one step long whatever is dropped.
+      if (n_leaves > CULL_MIN) {
+        constexpr int PU = 2;  // passes of 64 leaves with their loads in flight together
+        const uint32_t leaf0 = (uint32_t)ARG(lv.off[0]);
+        int n_out = 0;
+        for (int base = 0; base < n_leaves; base += 64 * PU) {
+          int leaf[PU];
+          bool on[PU];
+          float lo[PU][DP], hi[PU][DP];
+#pragma unroll
+          for (int u = 0; u < PU; ++u) {
+            const int idx = base + u * 64 + lane;
+            on[u] = idx < n_leaves;
+            leaf[u] = s_leaf[on[u] ? idx : 0];
+            const uint32_t nb_ = (leaf0 + (uint32_t)leaf[u]) * (uint32_t)(2 * DP * sizeof(float));
+            load_row_at<DP>(nodes, nb_, lo[u]);
+            load_row_at<DP>(nodes, nb_ + (uint32_t)(DP * sizeof(float)), hi[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < PU; ++u) {
+            if (base + u * 64 < n_leaves) {
+              const bool stay = on[u] && node_meets_slabs<DIM>(lo[u], hi[u], pn, po, org, slab_lo, slab_hi);
+              const unsigned long long m = __ballot(stay);
+              if (stay) s_leaf[n_out + lane_rank(m)] = leaf[u];
+              n_out += __popcll(m);
+            }
+          }
+        }
+#ifdef FLOODER_PHASE_TIMERS
+        // (slot 11 of the phase sums holds no phase: leaves gathered << 32 | leaves the planes dropped)
+        t_phase[11] += ((unsigned long long)n_leaves << 32) + (unsigned long long)(n_leaves - n_out);
+#endif
+        n_leaves = n_out;
+        wave_lds_sync();
+      }
+#endif
       PHASE(4);
       if (n_leaves < 0) { give_up = true; ++g_gather; break; }
       for (int i = lane; i < (ncells + 3) / 2; i += 64) s_cell32[i] = 0u;

@@ -97,4 +97,68 @@ __device__ __forceinline__ void simplex_planes_row(const float* __restrict__ ver
   }
 }
 
+// Node box against the slabs of a region (flood_cell.hip: keep_point).  A point x is kept there when, for every
+// plane f, dd_f(x) = fl(sum_k pn[f][k] * fl(x_k - org_k) - po[f]) - a chain of DIM fmas that starts at -po[f] - lies
+// in [slab_lo[f], slab_hi[f]].  `false` here says that no x with lo <= x <= hi can pass that test: the node, inner
+// node or leaf, holds nothing for the region.  (The cell sweep asks for the leaves a gather has collected.)
+//
+// Per plane the support interval [smin, smax] of the box along pn[f]: with a_k = fl(lo_k - org_k), b_k = fl(hi_k -
+// org_k) - rounding is monotone, so fl(x_k - org_k) lies in [a_k, b_k] for every x in the box - the sum over the axes
+// of min / max(pn_k * a_k, pn_k * b_k), minus po[f].  The node goes when smin - pad > slab_hi[f] or smax + pad <
+// slab_lo[f].
+//
+// The pad.  u = 2^-24 (half an ulp), m_k = max(|a_k|, |b_k|), M = |po| + sum_k |pn_k| m_k: no partial sum of either
+// computation exceeds M (1 + u)^3 in magnitude.
+//   keep_point's chain: DIM fmas, each rounds a partial sum once, u M each              <= 3 u M
+//   the support sum:    DIM products rounded, u |pn_k| m_k each, together <= u M;
+//                       DIM - 1 additions and the subtraction of po, u M each          <= 4 u M
+//   M itself:           |po| + sum_k max(|pn_k a_k|, |pn_k b_k|) - the rounded products, which are fl(|pn_k| m_k) -
+//                       a sum of non-negative terms, DIM + DIM roundings: relative error 6 u, taken from below
+//   smin - pad, smax + pad: one rounding of a number below M + pad                     <= u (M + pad)
+// all of it with second-order terms below 8.1 u M for DIM <= 3: pad = 16 u M = 2^-20 M leaves a factor of two.  The
+// absolute term stands for products that leave the normal range (4 roundings of at most 2^-126 each way, or as many
+// operands flushed to zero).
+// Every comparison is written so that NaN gives "keep": a NaN slab limit, interval end or pad drops nothing.  An
+// empty box (lo = +inf, hi = -inf: pad rows of the tree) gives products of infinite size and pad = inf, or NaN
+// (0 * inf under a zero normal); a plane switched off (pn = 0, po = 3e38) gives smin = smax = -po = dd of every point, so it drops a node
+// only where it drops every point.  fmin / fmax skip a NaN operand, so a NaN box coordinate is NOT covered: callers
+// ask here only about nodes that passed the box test, which such a node (and an empty one) fails.
+// (tests/test_gather_planes_cpu.py holds the float32 replica and shows that pad = 0 is not enough.)
+constexpr float GATHER_PAD_REL = 9.5367431640625e-07f;  // 2^-20
+constexpr float GATHER_PAD_ABS = 1.0e-36f;
+#ifndef FLOODER_GATHER_PLANES
+#define FLOODER_GATHER_PLANES 1  // 0: the cell sweep classifies every leaf whose box meets the region's box (A/B builds)
+#endif
+
+template <int DIM, int DP>
+__device__ __forceinline__ bool node_meets_slabs(const float (&lo)[DP], const float (&hi)[DP], const float (&pn)[DIM + 1][DIM],
+                                                 const float (&po)[DIM + 1], const float (&org)[DIM],
+                                                 const float (&slab_lo)[DIM + 1], const float (&slab_hi)[DIM + 1]) {
+#pragma clang fp contract(off)
+  float a[DIM], b[DIM];
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    a[k] = lo[k] - org[k];
+    b[k] = hi[k] - org[k];
+  }
+  bool out = false;
+#pragma unroll
+  for (int f = 0; f <= DIM; ++f) {
+    float smin = 0.f, smax = 0.f, mag = __builtin_fabsf(po[f]);
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      const float pa = pn[f][k] * a[k], pb = pn[f][k] * b[k];
+      const float mn = __builtin_fminf(pa, pb), mx = __builtin_fmaxf(pa, pb);
+      smin = k == 0 ? mn : smin + mn;
+      smax = k == 0 ? mx : smax + mx;
+      mag = mag + __builtin_fmaxf(__builtin_fabsf(pa), __builtin_fabsf(pb));  // = fl(|pn_k| m_k)
+    }
+    smin = smin - po[f];
+    smax = smax - po[f];
+    const float pad = __builtin_fmaf(GATHER_PAD_REL, mag, GATHER_PAD_ABS);
+    out = out || (smin - pad > slab_hi[f]) || (smax + pad < slab_lo[f]);
+  }
+  return !out;
+}
+
 }  // namespace flooder

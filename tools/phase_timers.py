@@ -31,9 +31,14 @@ for _ in range(2):
     core._sweep_dimension_cell(index, verts, weights, faces, None, stats=stats)
 torch.cuda.synchronize()
 t = stats[16:28].cpu().numpy().astype(float)
+t[11] = 0.0   # (leaf counts of the gathers, printed below)
 n_chunks = verts.shape[0] * ((weights.shape[0] + 255) // 256)
 names = ["pop", "samples+box+planes", "gather0", "density", "gather1", "count", "prefix", "scatter", "query", "brute", "output", "-"]
 tot = t.sum()
 for n, v in zip(names, t):
     print(f"{n:22s} {v/tot*100:6.2f} %   {v/n_chunks/2400:8.2f} us/chunk at 2.4 GHz  (raw cycles {v:.3e})")
 print("stats", stats[:12].tolist())
+# (slot 11 is no phase: leaves that met a gather's box << 32 | leaves the region's planes dropped - gathers with a known
+# cell size only, library built with FLOODER_GATHER_PLANES on)
+n_box, n_cut = int(stats[27]) >> 32, int(stats[27]) & 0xffffffff
+print(f"leaves over the box {n_box}, dropped by the planes {n_cut} ({100.0 * n_cut / max(n_box, 1):.1f} %)")
