@@ -134,6 +134,7 @@ QUEUE_WORDS = 512
 FINISH_CTL_PASS_HEADS, FINISH_CTL_TOP_COUNT = 0, 3
 FINISH_CTL_TOP_HARD_HEAD, FINISH_CTL_TOP_HARD_LEN, FINISH_CTL_REST_HARD_HEAD, FINISH_CTL_REST_HARD_LEN = 4, 5, 6, 7
 FINISH_CTL_SINGLE_LEFT, FINISH_CTL_QUEUES, FINISH_CTL_WORDS = 8, 24, 24 + 3 * QUEUE_WORDS
+FLAG_HIST_WORDS = 8192
 DEFER_CTL_COUNT, DEFER_CTL_QUEUE, DEFER_CTL_LIGHT, DEFER_CTL_HEAVY, DEFER_CTL_SPLIT_DONE = 0, 1, 2, 3, 4
 DEFER_CTL_TILE_COUNT, DEFER_CTL_WORDS = 6, 8
 CELL_QUEUE_RUNS, CELL_QUEUE_CHUNKS, CELL_QUEUE_TILES, CELL_QUEUE_WORDS = 0, QUEUE_WORDS, 2 * QUEUE_WORDS, 3 * QUEUE_WORDS

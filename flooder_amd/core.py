@@ -434,6 +434,39 @@ def _span(timer: Optional[_KernelTimer], name: str):
     return timer.span(name) if timer is not None else _NullSpan()
 
 
+def _no_simplices(faces: _FaceTable, R: int, dev, want_dist: bool):
+    """What a sweep driver returns for an empty simplex shard: (0, F) face maxima, (0, R) distances if wanted."""
+    return (torch.empty((0, faces.n_faces), dtype=torch.float32, device=dev),
+            torch.empty((0, R), dtype=torch.float32, device=dev) if want_dist else None)
+
+
+def _face_epilogue(lib, st, d2: torch.Tensor, faces: _FaceTable, rows: torch.Tensor,
+                   reduce_hook: Optional[Callable[[torch.Tensor], None]] = None, want_dist: bool = False,
+                   inv: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None,
+                   out_face: Optional[torch.Tensor] = None):
+    """The tail every (S, R) sweep shares: [reduce_hook: cross-shard MIN on the squared-distance bits ``d2``] -> face
+    maxima + sqrt (``flooder_face_max_f32``; int64 bits of doubles: ``_f64``) -> (out_face (S, F), out_dist (S, R) or None).
+    ``rows``: the face table's rows in the order of ``d2``'s columns; ``inv``: that order's inverse, which puts
+    ``out_dist`` back into the caller's sample order; ``out_face``: the caller's rows to write instead of a new tensor."""
+    S, R = d2.shape
+    if reduce_hook is not None:
+        with _span(timer, "reduce"):
+            reduce_hook(d2)
+    f64 = d2.dtype == torch.int64
+    dtype = torch.float64 if f64 else torch.float32
+    if out_face is None:
+        out_face = torch.empty((S, faces.n_faces), dtype=dtype, device=d2.device)
+    out_dist = torch.empty((S, R), dtype=dtype, device=d2.device) if want_dist else None
+    face_max = lib.flooder_face_max_f64 if f64 else lib.flooder_face_max_f32
+    with _span(timer, "face_max"):
+        _native.check(face_max(_native.ptr(d2), S, R, _native.ptr(faces.ptr), _native.ptr(rows), faces.n_faces,
+                               _native.ptr(out_face), _native.ptr(out_dist), st),
+                      "flooder_face_max_f64" if f64 else "flooder_face_max_f32")
+    if out_dist is not None and inv is not None:
+        out_dist = out_dist[:, inv]  # back to the caller's sample order
+    return out_face, out_dist
+
+
 def _sweep_dimension_hip(pts_pad: torch.Tensor, search: torch.Tensor, axis: int, dim: int,
                          verts: torch.Tensor, centers: torch.Tensor, radii: torch.Tensor,
                          weights: torch.Tensor, faces: _FaceTable,
@@ -453,8 +486,7 @@ def _sweep_dimension_hip(pts_pad: torch.Tensor, search: torch.Tensor, axis: int,
     dp = pts_pad.shape[1]
     n = pts_pad.shape[0]
     if S == 0:  # (a simplex shard may be empty)
-        return (torch.empty((0, faces.n_faces), dtype=torch.float32, device=dev),
-                torch.empty((0, R), dtype=torch.float32, device=dev) if want_dist else None)
+        return _no_simplices(faces, R, dev, want_dist)
 
     verts = verts.to(torch.float32).contiguous()
     centers = centers.to(torch.float32).contiguous()
@@ -521,18 +553,7 @@ def _sweep_dimension_hip(pts_pad: torch.Tensor, search: torch.Tensor, axis: int,
         LAST_STATS.groups += 1
         del cand
 
-    if reduce_hook is not None:
-        with _span(timer, "reduce"):
-            reduce_hook(d2)
-
-    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
-    out_dist = torch.empty((S, R), dtype=torch.float32, device=dev) if want_dist else None
-    with _span(timer, "face_max"):
-        _native.check(lib.flooder_face_max_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr),
-                                               _native.ptr(faces.rows), faces.n_faces,
-                                               _native.ptr(out_face), _native.ptr(out_dist), st),
-                      "flooder_face_max_f32")
-    return out_face, out_dist
+    return _face_epilogue(lib, st, d2, faces, faces.rows, reduce_hook, want_dist, timer=timer)
 
 
 def cloud_box(points: torch.Tensor) -> torch.Tensor:
@@ -1273,18 +1294,7 @@ def _sweep_dimension_f64(index: PointIndex, pts64_sorted: torch.Tensor, verts: t
         _native.check(lib.flooder_sweep_bvh_f64(_native.ptr(pts64_sorted), index.n, index.dim, _native.ptr(index.nodes),
                                                 _native.ptr(verts), _native.ptr(w_perm), k1, R, S, _native.ptr(queue),
                                                 _native.ptr(d2), st), "flooder_sweep_bvh_f64")
-    if reduce_hook is not None:
-        with _span(timer, "reduce"):
-            reduce_hook(d2)
-    out_face = torch.empty((S, faces.n_faces), dtype=torch.float64, device=dev)
-    out_dist = torch.empty((S, R), dtype=torch.float64, device=dev) if want_dist else None
-    with _span(timer, "face_max"):
-        _native.check(lib.flooder_face_max_f64(_native.ptr(d2), S, R, _native.ptr(faces.ptr), _native.ptr(rows_perm),
-                                               faces.n_faces, _native.ptr(out_face), _native.ptr(out_dist), st),
-                      "flooder_face_max_f64")
-    if out_dist is not None:
-        out_dist = out_dist[:, inv]
-    return out_face, out_dist
+    return _face_epilogue(lib, st, d2, faces, rows_perm, reduce_hook, want_dist, inv, timer)
 
 
 def bvh_sorts_samples(dim: int, S: int, R: int) -> bool:
@@ -1304,6 +1314,39 @@ SHARD_SORTED_TILES = True
 
 def shards_sorted_tiles(dim: int, S: int, R: int, method: str) -> bool:
     return SHARD_SORTED_TILES and method == "bvh" and bvh_sorts_samples(dim, S, R)
+
+
+def _sorted_sample_order(lib, st, index: PointIndex, verts: torch.Tensor, w_perm: torch.Tensor,
+                         sort_state: Optional[torch.Tensor], late_rows: Optional[torch.Tensor], bits: int) -> torch.Tensor:
+    """The sort stage of the sorted-sample sweep: a Z-order key per sample of every simplex -> one radix sort on the low
+    ``bits`` bits -> ``order`` (S * R int32, which the sweep reads: it must outlive it).  ``late_rows`` (None, or
+    ``SamplePlan.late_rows``): the keys of ``flooder_sample_keys_late_f32``, which sort every row but a face's pilot
+    behind the pilots.  ``sort_state``: the sort's state words zeroed by the caller (``SORT_STATE_BY_CALLER``), or None."""
+    dev = verts.device
+    S, k1, _ = verts.shape
+    R = w_perm.shape[0]
+    n_s = S * R
+    keys, keys_sorted, order = (torch.empty(n_s, dtype=torch.int32, device=dev) for _ in range(3))
+    tmp_bytes = int(lib.flooder_index_sort_bytes(n_s))
+    tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+    if late_rows is not None:
+        _native.check(lib.flooder_sample_keys_late_f32(_native.ptr(verts), _native.ptr(w_perm), k1, R, S, index.dim,
+                                                       _native.ptr(index.box), _native.ptr(late_rows),
+                                                       _native.ptr(keys), st), "flooder_sample_keys_late_f32")
+    else:
+        _native.check(lib.flooder_sample_keys_f32(_native.ptr(verts), _native.ptr(w_perm), k1, R, S, index.dim,
+                                                  _native.ptr(index.box), _native.ptr(keys), st),
+                      "flooder_sample_keys_f32")
+    if sort_state is not None:
+        _native.check(lib.flooder_index_sort_zeroed(_native.ptr(keys), n_s, bits, _native.ptr(keys_sorted), _native.ptr(order),
+                                                    _native.ptr(tmp), tmp_bytes, _native.ptr(sort_state), st),
+                      "flooder_index_sort_zeroed (samples)")
+    else:
+        _native.check(lib.flooder_index_sort(_native.ptr(keys), n_s, bits, _native.ptr(keys_sorted), _native.ptr(order),
+                                             _native.ptr(tmp), tmp_bytes, st), "flooder_index_sort (samples)")
+    # (keys, keys_sorted and tmp are dropped here, before the sweep is launched: everything runs on the one current
+    # stream and torch's caching allocator is stream-ordered - whoever gets these blocks next writes them behind the sort)
+    return order
 
 
 def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
@@ -1337,37 +1380,18 @@ def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.
     queue = torch.zeros(QUEUE_WORDS + n_sort_state, dtype=torch.int32, device=dev)
     sort_state = queue[QUEUE_WORDS:] if n_sort_state else None
     queue = queue[:QUEUE_WORDS]
-
-    def sort_sample_keys(keys, n_s, bits, keys_sorted, order, tmp, tmp_bytes):
-        if sort_state is not None:
-            _native.check(lib.flooder_index_sort_zeroed(_native.ptr(keys), n_s, bits, _native.ptr(keys_sorted), _native.ptr(order),
-                                                        _native.ptr(tmp), tmp_bytes, _native.ptr(sort_state), st),
-                          "flooder_index_sort_zeroed (samples)")
-        else:
-            _native.check(lib.flooder_index_sort(_native.ptr(keys), n_s, bits, _native.ptr(keys_sorted), _native.ptr(order),
-                                                 _native.ptr(tmp), tmp_bytes, st), "flooder_index_sort (samples)")
     if (sorted_samples and SORTED_FUSED_FACES and not want_dist and reduce_hook is None and plan.memb_all is not None
             and plan.late_rows is not None and tile_shard is None):
         # ---- only the face maxima are wanted: the sorted sweep delivers them itself (no (S, R) buffer, no face-max
         # pass) and drops every sample that cannot raise one - csrc/flood_sorted.hip, FUSED
-        n_s = S * R
         F = faces.n_faces
-        keys = torch.empty(n_s, dtype=torch.int32, device=dev)
-        keys_sorted = torch.empty(n_s, dtype=torch.int32, device=dev)
-        order = torch.empty(n_s, dtype=torch.int32, device=dev)
-        tmp_bytes = int(lib.flooder_index_sort_bytes(n_s))
-        tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
         face_bits = torch.zeros(S * F, dtype=torch.int32, device=dev)
         with _span(timer, "sweep"):
-            _native.check(lib.flooder_sample_keys_late_f32(_native.ptr(verts), _native.ptr(w_perm), k1, R, S, index.dim,
-                                                           _native.ptr(index.box), _native.ptr(plan.late_rows),
-                                                           _native.ptr(keys), st), "flooder_sample_keys_late_f32")
-            sort_sample_keys(keys, n_s, 32, keys_sorted, order, tmp, tmp_bytes)
+            order = _sorted_sample_order(lib, st, index, verts, w_perm, sort_state, plan.late_rows, 32)
             blk = _native.SortedSweep(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
                                       weights=w_perm, R=R, n_faces=F, n_simplices=S, sample_order=order, queue=queue,
                                       memb=plan.memb_all, face_bits=face_bits, stats=stats)
             _native.check(lib.flooder_sorted_faces(ctypes.byref(blk), st), "flooder_sorted_faces")
-        del keys, keys_sorted, tmp
         out_face = torch.empty((S, F), dtype=torch.float32, device=dev)
         with _span(timer, "face_max"):
             _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), S * F, _native.ptr(out_face), st),
@@ -1381,16 +1405,8 @@ def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.
         if sorted_samples:
             # tiles of 64 spatially consecutive samples of ALL simplices (Z-order keys, one radix sort) instead of
             # the samples of one simplex each: see csrc/flood_sorted.hip
-            n_s = S * R
-            keys = torch.empty(n_s, dtype=torch.int32, device=dev)
-            keys_sorted = torch.empty(n_s, dtype=torch.int32, device=dev)
-            order = torch.empty(n_s, dtype=torch.int32, device=dev)
-            tmp_bytes = int(lib.flooder_index_sort_bytes(n_s))
-            tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
-            _native.check(lib.flooder_sample_keys_f32(_native.ptr(verts), _native.ptr(w_perm), k1, R, S, index.dim,
-                                                      _native.ptr(index.box), _native.ptr(keys), st),
-                          "flooder_sample_keys_f32")
-            sort_sample_keys(keys, n_s, int(lib.flooder_sample_key_bits(index.dim)), keys_sorted, order, tmp, tmp_bytes)
+            order = _sorted_sample_order(lib, st, index, verts, w_perm, sort_state, None,
+                                         int(lib.flooder_sample_key_bits(index.dim)))
             # (a tile shard: every rank sorts ALL samples - the same order everywhere - and takes a contiguous world-th of
             # the tiles)
             blk = _native.SortedSweep(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
@@ -1398,25 +1414,12 @@ def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.
                                       stats=stats, shard_rank=0 if tile_shard is None else int(tile_shard[0]),
                                       shard_world=0 if tile_shard is None else int(tile_shard[1]))
             _native.check(lib.flooder_sorted_minima(ctypes.byref(blk), st), "flooder_sorted_minima")
-            del keys, keys_sorted, tmp
         else:
             _native.check(lib.flooder_sweep_bvh_f32(
                 _native.ptr(index.pts), index.n, index.dim, _native.ptr(index.nodes), _native.ptr(verts),
                 _native.ptr(w_perm), k1, R, S, _native.ptr(queue), _native.ptr(d2), _native.ptr(stats), st),
                 "flooder_sweep_bvh_f32")
-    if reduce_hook is not None:
-        with _span(timer, "reduce"):
-            reduce_hook(d2)
-    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
-    out_dist = torch.empty((S, R), dtype=torch.float32, device=dev) if want_dist else None
-    with _span(timer, "face_max"):
-        _native.check(lib.flooder_face_max_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr),
-                                               _native.ptr(rows_perm), faces.n_faces,
-                                               _native.ptr(out_face), _native.ptr(out_dist), st),
-                      "flooder_face_max_f32")
-    if out_dist is not None:
-        out_dist = out_dist[:, plan.inv]  # back to the caller's sample order
-    return out_face, out_dist
+    return _face_epilogue(lib, st, d2, faces, rows_perm, reduce_hook, want_dist, plan.inv, timer)
 
 
 # Most neighbours per sample of the robust filtration (``flood_complex(neighbors=k)``; FLOODER_KNN_MAX).  A register-budget
@@ -1501,12 +1504,7 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
                            queue=queue, out_bits=d2, stats=stats)
     with _span(timer, "sweep"):
         _native.check(lib.flooder_sweep_knn_f32(ctypes.byref(blk), st), "flooder_sweep_knn_f32")
-    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
-    with _span(timer, "face_max"):
-        _native.check(lib.flooder_face_max_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr),
-                                               _native.ptr(plan.rows_perm), faces.n_faces,
-                                               _native.ptr(out_face), None, st),
-                      "flooder_face_max_f32")
+    out_face, _ = _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer)
     if keep is not None:
         keep(d2)
     return out_face, None
@@ -1546,10 +1544,8 @@ def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights
         with _span(timer, "sweep"):
             _native.check(lib.flooder_sweep_knn_profile_f32(ctypes.byref(blk), st), "flooder_sweep_knn_profile_f32")
         with _span(timer, "face_max"):
-            for c in range(n_cols):
-                _native.check(lib.flooder_face_max_f32(_native.ptr(planes[c]), b - a, R, _native.ptr(faces.ptr),
-                                                       _native.ptr(plan.rows_perm), F, _native.ptr(out_faces[c][a:b]),
-                                                       None, st), "flooder_face_max_f32")
+            for c in range(n_cols):   # (one span for the planes of a group: the epilogue gets no timer)
+                _face_epilogue(lib, st, planes[c], faces, plan.rows_perm, out_face=out_faces[c][a:b])
     return out_faces
 
 
@@ -1606,10 +1602,7 @@ def _sweep_dimension_knn_sharded(index: PointIndex, verts: torch.Tensor, weights
                                stat=NEIGHBOR_STATS.index(stat), out_bits=d2)
         with _span(timer, "merge"):
             _native.check(lib.flooder_knn_merge_f32(ctypes.byref(mrg), st), "flooder_knn_merge_f32")
-        with _span(timer, "face_max"):
-            _native.check(lib.flooder_face_max_f32(_native.ptr(d2), b - a, R, _native.ptr(faces.ptr),
-                                                   _native.ptr(plan.rows_perm), F, _native.ptr(out_face[a:b]), None, st),
-                          "flooder_face_max_f32")
+        _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer, out_face=out_face[a:b])
     return out_face, None
 
 
@@ -1656,6 +1649,86 @@ FACE_OWNER = True
 # kept as an option.
 FACE_OWNER_GROUPED = False
 
+# Word offsets into `ctl`, the fused sweep's own control block: the flag count, the cell sweep's defer_ctl (its words by
+# name: _native.DEFER_CTL_*), then the histogram of the flagged tiles' bounds and the cursors of the finish's counting
+# sort (_native.FLAG_HIST_WORDS).  The finish has a block of its own, finish_ctl (_native.FINISH_CTL_*).
+CTL_FLAG_COUNT, CTL_DEFER, CTL_HIST = 1, 12, 48
+
+
+def fused_layout(S: int, n_slots: int, wit: bool, owner: bool) -> Tuple[Dict[str, Tuple[int, int]], int]:
+    """Where everything of the fused sweep that starts at zero lies in its one arena -> ({region: (first int32 word,
+    words)}, words in all).  The sharded work-queue heads of the launches in front (the witness sweep's only when it
+    runs), then the finish's control block, `top` (a uint64 per simplex), `ctl`, and a face word per slot.  Under face
+    ownership (``owner``) a 64-bit owner word per slot follows, 8-byte aligned by one pad word where needed, and the
+    result vector: a slot that none of a call's simplices touches (a rank's share) keeps the zero fill's 0.0."""
+    sizes = [("wit_queue", QUEUE_WORDS)] if wit else []
+    sizes += [("cell_queue", _native.CELL_QUEUE_WORDS), ("finish_ctl", _native.FINISH_CTL_WORDS), ("top", 2 * S),
+              ("ctl", CTL_HIST + _native.FLAG_HIST_WORDS), ("face_bits", n_slots)]
+    if owner:
+        sizes += [("face_owner", 2 * n_slots), ("result", n_slots)]
+    regions, n_words = {}, 0
+    for name, words in sizes:
+        if name == "face_owner":
+            n_words += n_words & 1
+        regions[name] = (n_words, words)
+        n_words += words
+    return regions, n_words
+
+
+class FusedWorkspace:
+    """Every buffer the launches of the fused 2-D / 3-D sweep share, for S simplices x R samples: ``arena`` (``n_words``
+    int32 laid out by ``fused_layout``; ``flooder_simplex_prepare_f32`` clears it, and where that launch is switched off
+    it is allocated zeroed), its regions as named views, and the scratch that needs no initial value.  ``n_slots``: face
+    words (None: one per (simplex, face), S * n_faces); ``wit`` / ``owner``: the witness sweep / face ownership take
+    part (their regions are None otherwise); ``planes``: the caller's buffer for the 24 S plane words.  Reads
+    ``CELL_SUPER``, ``SWEEP_PREPARE_FUSED``, ``CELL_PROBE`` and ``FINISH_HARD_CAP``; needs no library and no GPU."""
+
+    def __init__(self, S: int, R: int, n_faces: int, n_slots: Optional[int], device, wit: bool, owner: bool,
+                 planes: Optional[torch.Tensor] = None):
+        def empty(shape, dtype=torch.int32):
+            return torch.empty(shape, dtype=dtype, device=device)
+
+        regions, self.n_words = fused_layout(S, S * n_faces if n_slots is None else n_slots, wit, owner)
+        # face planes per simplex (filled by the prepare launch or the sweep's entry)
+        self.planes = planes if planes is not None else empty(24 * S, torch.float32)
+        self.arena = (torch.empty if CELL_SUPER and SWEEP_PREPARE_FUSED else torch.zeros)(self.n_words, dtype=torch.int32,
+                                                                                            device=device)
+        self.wit_queue = self.face_owner = self.result = None
+        for name, (first, words) in regions.items():
+            setattr(self, name, self.arena[first:first + words])
+        self.top = self.top.view(torch.int64)
+        if owner:
+            self.result = self.result.view(torch.float32)
+        self.flag_count, self.defer_ctl, self.flag_hist = self.ctl[CTL_FLAG_COUNT:], self.ctl[CTL_DEFER:], self.ctl[CTL_HIST:]
+        self.top_count = self.finish_ctl[_native.FINISH_CTL_TOP_COUNT:]
+        self.hard = empty(4 * FINISH_HARD_CAP, torch.int64)
+        self.top_list = empty(S)
+        self.d2 = empty((S, R))
+        self.flags = empty((3, S * ((R + 63) // 64)))   # flagged tiles, their bounds, ordered
+        # (chunk entries, then up to four tile entries per chunk: dense chunks hand their tiles to a third launch)
+        n_defer = 5 * S * ((R + 255) // 256)
+        self.defer_list = empty(n_defer) if CELL_SUPER else None
+        self.defer_c = empty(n_defer, torch.float32) if CELL_SUPER else None
+        self.split = empty((2, S)) if CELL_SUPER else None     # light / heavy simplices
+        self.wgt = empty(S, torch.float32) if CELL_SUPER else None
+
+    def block_fields(self) -> Dict[str, object]:
+        """The buffer fields of ``_native.FusedSweep`` this workspace stands behind, by name (those of a stage that is
+        switched off are left out: NULL).  The caller adds the cloud, the lattice, the stats views and planes_ready."""
+        f = dict(face_bits=self.face_bits, d2_scratch=self.d2, flag_list=self.flags[0], flag_count=self.flag_count,
+                 simplex_weight=self.wgt, plane_scratch=self.planes, cell_queue=self.cell_queue, defer_list=self.defer_list,
+                 defer_c=self.defer_c, finish_ctl=self.finish_ctl, hard_scratch=self.hard, hard_cap=FINISH_HARD_CAP)
+        if CELL_PROBE:
+            f.update(flag_key=self.flags[1], flag_hist=self.flag_hist, flag_sorted=self.flags[2], top=self.top,
+                     top_list=self.top_list, top_count=self.top_count)
+        if CELL_SUPER:
+            f.update(defer_ctl=self.defer_ctl, light_list=self.split[0], heavy_list=self.split[1])
+        if self.face_owner is not None:
+            f["face_owner"] = self.face_owner
+        if self.wit_queue is not None:   # (split[0]: its item list - scratch until the cell sweep's entry fills it)
+            f.update(wit_queue=self.wit_queue, wit_item_list=self.split[0])
+        return f
+
 
 def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                           reduce_hook: Optional[Callable[[torch.Tensor], None]],
@@ -1693,93 +1766,47 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         return None if stats is None else stats[a:b]
 
     if S == 0:
-        return (torch.empty((0, faces.n_faces), dtype=torch.float32, device=dev),
-                torch.empty((0, R), dtype=torch.float32, device=dev) if want_dist else None)
-    planes = torch.empty(24 * S, dtype=torch.float32, device=dev)   # face planes per simplex (filled by the sweep's entry)
+        return _no_simplices(faces, R, dev, want_dist)
     if FUSED_FACES and not want_dist and reduce_hook is None and plan.memb_all is not None:
         # ---- only the per-face maxima are wanted: fused path.  The cell sweep delivers every settled sample to
         # face_bits (integer atomic max), the finish drops what cannot raise a face maximum, the (S, R) buffer is
         # scratch that only the flagged tiles touch.
         F = faces.n_faces
-        tiles = (R + 63) // 64
-        slot_t, n_slots = face_slots if face_slots is not None else (None, S * F)
-        # `ctl`, this function's own control block: the flag count, the cell sweep's defer_ctl (its words by name:
-        # _native.DEFER_CTL_*), then the histogram of the flagged tiles' bounds and the cursors of the finish's counting
-        # sort; `fctl` is the finish's (_native.FINISH_CTL_*)
-        CTL_FLAG_COUNT, CTL_DEFER, CTL_HIST = 1, 12, 48
-        # (one zero fill for everything that starts at zero: top | ctl | face_bits)
-        # (the sharded work-queue heads of the sweep's launches sit in front: QUEUE_WORDS each)
+        slot_t, n_slots = face_slots if face_slots is not None else (None, None)
         # (a short queue - a rank's share of a multi-GPU run - leaves the witness sweep's workgroups one simplex each: the
         # launch then lasts as long as its longest item, 250 - 300 us, where the cell sweep balances chunk by chunk;
         # measured on an eighth of cfg 2: 0.65 ms per rank with it, 0.55 without)
         use_wit = (CELL_WITNESS and CELL_SUPER and CELL_PROBE and index.dim in (2, 3) and S >= WIT_MIN_SIMPLICES
                    and index.n <= WIT_MAX_POINTS_PER_SIMPLEX * S and plan.wit is not None)
-        # (with the simplex weights wanted, the launch that computes them clears these words and writes the plane rows on
-        # its way - flooder_simplex_prepare_f32 below -: one launch instead of three)
-        n_zeroed = ((1 if use_wit else 0) * QUEUE_WORDS + _native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS + 2 * S
-                    + CTL_HIST + 8192 + n_slots)
-        # face ownership: behind the face words one 64-bit owner word per slot (8-byte aligned) and the result vector -
-        # a slot none of this call's simplices touches (a rank's share) keeps the zero fill's 0.0
+        # face ownership: one incident simplex evaluates a shared face's samples (the comment at FACE_OWNER)
         use_owner = (FACE_OWNER and face_slots is not None and plan.owner_order and CELL_SUPER and SWEEP_PREPARE_FUSED
                      and plan.sub_faces.numel() == F)
-        n_plain = n_zeroed
-        if use_owner:
-            n_zeroed += (n_zeroed & 1) + 3 * n_slots
-        zeroed = (torch.empty if CELL_SUPER and SWEEP_PREPARE_FUSED else torch.zeros)(n_zeroed, dtype=torch.int32, device=dev)
-        zeroed_all = zeroed
-        if use_wit:
-            qwit = zeroed[:QUEUE_WORDS]
-            zeroed = zeroed[QUEUE_WORDS:]
-        qbuf = zeroed[:_native.CELL_QUEUE_WORDS]
-        fctl = zeroed[_native.CELL_QUEUE_WORDS:_native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS]
-        zeroed = zeroed[_native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS:]
-        top = zeroed[:2 * S].view(torch.int64)
-        ctl = zeroed[2 * S:2 * S + CTL_HIST + 8192]
-        face_bits = zeroed[2 * S + CTL_HIST + 8192:2 * S + CTL_HIST + 8192 + n_slots]
-        owner = zeroed_all[n_plain + (n_plain & 1):n_plain + (n_plain & 1) + 2 * n_slots] if use_owner else None
-        hard = torch.empty(4 * FINISH_HARD_CAP, dtype=torch.int64, device=dev)
-        top_list = torch.empty(S, dtype=torch.int32, device=dev)
-        d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-        flags = torch.empty((3, S * tiles), dtype=torch.int32, device=dev)  # flagged tiles, their bounds, ordered
-        chunks = (R + 255) // 256
-        # (chunk entries, then up to four tile entries per chunk: dense chunks hand their tiles to a third launch)
-        defer_list = torch.empty(5 * S * chunks, dtype=torch.int32, device=dev) if CELL_SUPER else None
-        defer_c = torch.empty(5 * S * chunks, dtype=torch.float32, device=dev) if CELL_SUPER else None
-        wgt = None
-        split = torch.empty((2, S), dtype=torch.int32, device=dev) if CELL_SUPER else None  # light / heavy simplices
+        ws = FusedWorkspace(S, R, F, n_slots, dev, use_wit, use_owner)
         if CELL_SUPER:  # rough point count per simplex box: dense simplices skip the run-of-four launch
-            wgt = torch.empty(S, dtype=torch.float32, device=dev)
+            # (with the simplex weights wanted, the launch that computes them clears the arena and writes the plane rows
+            # on its way: one launch instead of three)
             if SWEEP_PREPARE_FUSED:
                 _native.check(lib.flooder_simplex_prepare_f32(_native.ptr(index.nodes), index.n, index.dim, _native.ptr(verts),
-                                                              k1, S, _native.ptr(wgt), _native.ptr(planes),
-                                                              _native.ptr(zeroed_all), n_zeroed, st),
+                                                              k1, S, _native.ptr(ws.wgt), _native.ptr(ws.planes),
+                                                              _native.ptr(ws.arena), ws.n_words, st),
                               "flooder_simplex_prepare_f32")
             else:
                 _native.check(lib.flooder_simplex_weight_f32(_native.ptr(index.nodes), index.n, index.dim, _native.ptr(verts),
-                                                             k1, S, _native.ptr(wgt), st), "flooder_simplex_weight_f32")
+                                                             k1, S, _native.ptr(ws.wgt), st), "flooder_simplex_weight_f32")
         # ONE parameter block for the three launches (include/flooder_hip.h: flooder_fused_sweep_t): they share the cloud,
         # the lattice, the result words and most of the scratch
         wst = stats[16:40] if use_wit and stats is not None and stats.numel() >= 40 else None
         blk = _native.FusedSweep(
             pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, density_grid=index.dens,
             cloud_box=index.box, verts=verts, weights=w_perm, R=R, n_faces=F, n_simplices=S, memb=plan.memb_all,
-            alpha=float(CELL_ALPHA), face_bits=face_bits, face_slot=slot_t, d2_scratch=d2, flag_list=flags[0],
-            flag_count=ctl[CTL_FLAG_COUNT:].data_ptr(), simplex_weight=wgt, plane_scratch=planes,
-            cell_queue=qbuf.data_ptr(), defer_list=defer_list, defer_c=defer_c, cell_stats=sub(0, 9),
-            finish_ctl=fctl.data_ptr(), hard_scratch=hard, hard_cap=FINISH_HARD_CAP, probed=1 if CELL_PROBE else 0,
-            finish_stats=sub(9, 16))
-        if CELL_PROBE:
-            blk.flag_key, blk.flag_hist, blk.flag_sorted = flags[1].data_ptr(), ctl[CTL_HIST:].data_ptr(), flags[2].data_ptr()
-            blk.top, blk.top_list = top.data_ptr(), top_list.data_ptr()
-            blk.top_count = fctl[_native.FINISH_CTL_TOP_COUNT:].data_ptr()
-        if CELL_SUPER:
-            blk.defer_ctl, blk.light_list, blk.heavy_list = ctl[CTL_DEFER:].data_ptr(), split[0].data_ptr(), split[1].data_ptr()
+            alpha=float(CELL_ALPHA), face_slot=slot_t, cell_stats=sub(0, 9), probed=1 if CELL_PROBE else 0,
+            finish_stats=sub(9, 16), **ws.block_fields())
         if use_owner:   # (the cell sweep's entry chooses the owners; the witness sweep evaluates all rows of its simplices)
-            blk.face_owner, blk.min_face = owner.data_ptr(), plan.min_face.data_ptr()
+            blk.min_face = plan.min_face.data_ptr()
             blk.chunk_faces, blk.tile_faces = plan.chunk_faces.data_ptr(), plan.tile_faces.data_ptr()
-        if use_wit:   # (split[0]: the witness sweep's item list - scratch until the cell sweep's entry fills it)
+        if use_wit:
             blk.n_coarse, blk.coarse_rows, blk.parents = plan.wit[2], plan.wit[0].data_ptr(), plan.wit[1].data_ptr()
-            blk.wit_queue, blk.wit_item_list, blk.wit_stats = qwit.data_ptr(), split[0].data_ptr(), _native.ptr(wst) or None
+            blk.wit_stats = _native.ptr(wst) or None
             if WIT_RUNS and plan.wit_runs is not None:   # (run test of its pass over all samples)
                 blk.wit_runs, blk.wit_run_len, blk.wit_n_runs = plan.wit_runs[0].data_ptr(), plan.wit_runs[1], plan.wit_runs[2]
         # (flooder_simplex_prepare_f32 above has written the plane rows of these verts on this stream; else the first of
@@ -1793,25 +1820,26 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
         with _span(timer, "fallback"):
             _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
         if stats is not None:  # (diagnostic runs only: a host synchronisation)
-            c_d = ctl[CTL_DEFER:CTL_DEFER + _native.DEFER_CTL_WORDS].tolist()
+            c_d = ws.defer_ctl[:_native.DEFER_CTL_WORDS].tolist()
             LAST_STATS.deferred_chunks = int(c_d[_native.DEFER_CTL_COUNT])
             LAST_STATS.light_heavy = (int(c_d[_native.DEFER_CTL_LIGHT]), int(c_d[_native.DEFER_CTL_HEAVY]))
             LAST_STATS.dense_tiles = int(c_d[_native.DEFER_CTL_TILE_COUNT])
-            c_h = fctl[:_native.FINISH_CTL_QUEUES].tolist()
+            c_h = ws.finish_ctl[:_native.FINISH_CTL_QUEUES].tolist()
             LAST_STATS.hard_entries = (int(c_h[_native.FINISH_CTL_TOP_HARD_LEN]), int(c_h[_native.FINISH_CTL_REST_HARD_LEN]))
             LAST_STATS.finish_single_left = int(c_h[_native.FINISH_CTL_SINGLE_LEFT])
         if use_owner:   # an owner delivers to the faces of its own simplex: every face takes the maximum over its closure
-            out_face = zeroed_all[n_zeroed - n_slots:].view(torch.float32)
             with _span(timer, "face_max"):
-                _native.check(lib.flooder_face_closure_f32(_native.ptr(face_bits), _native.ptr(slot_t), _native.ptr(plan.sub_faces),
-                                                           S, F, _native.ptr(out_face), st), "flooder_face_closure_f32")
-            return out_face, None
+                _native.check(lib.flooder_face_closure_f32(_native.ptr(ws.face_bits), _native.ptr(slot_t),
+                                                           _native.ptr(plan.sub_faces), S, F, _native.ptr(ws.result), st),
+                              "flooder_face_closure_f32")
+            return ws.result, None
         out_face = torch.empty(n_slots if face_slots is not None else (S, F), dtype=torch.float32, device=dev)
         with _span(timer, "face_max"):
-            _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), n_slots, _native.ptr(out_face), st),
+            _native.check(lib.flooder_face_values_f32(_native.ptr(ws.face_bits), ws.face_bits.numel(), _native.ptr(out_face), st),
                           "flooder_face_values_f32")
         return out_face, None
 
+    planes = torch.empty(24 * S, dtype=torch.float32, device=dev)   # face planes per simplex (filled by the sweep's entry)
     ctl = torch.zeros(8 + 4 * QUEUE_WORDS, dtype=torch.int32, device=dev)  # flag counter, list length | queue heads
     qbuf = ctl[8:8 + 3 * QUEUE_WORDS]
     q_items = ctl[8 + 3 * QUEUE_WORDS:]
@@ -1828,20 +1856,7 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
             _native.ptr(index.pts), index.n, index.dim, _native.ptr(index.nodes), _native.ptr(verts),
             _native.ptr(w_perm), k1, R, S, _native.ptr(flags), ctl[1:].data_ptr(), q_items.data_ptr(),
             _native.ptr(d2), 0, None, None, _native.ptr(sub(9, 13)), st), "flooder_sweep_bvh_items_f32")
-
-    if reduce_hook is not None:
-        with _span(timer, "reduce"):
-            reduce_hook(d2)
-    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
-    out_dist = torch.empty((S, R), dtype=torch.float32, device=dev) if want_dist else None
-    with _span(timer, "face_max"):
-        _native.check(lib.flooder_face_max_f32(_native.ptr(d2), S, R, _native.ptr(faces.ptr),
-                                               _native.ptr(rows_perm), faces.n_faces,
-                                               _native.ptr(out_face), _native.ptr(out_dist), st),
-                      "flooder_face_max_f32")
-    if out_dist is not None:
-        out_dist = out_dist[:, plan.inv]
-    return out_face, out_dist
+    return _face_epilogue(lib, st, d2, faces, rows_perm, reduce_hook, want_dist, plan.inv, timer)
 
 
 def _face_max_cpu(dist: torch.Tensor, faces: _FaceTable) -> torch.Tensor:

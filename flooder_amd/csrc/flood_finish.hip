@@ -819,6 +819,7 @@ __global__ __launch_bounds__(64 * SINGLE_WAVES) void finish_single_kernel(
 // started first the last pass ends when the work does, not when the last long tile that happened to be queued
 // late does (cfg 3: -27 % of the pass, cfg 5: -29 %, simulated from measured tile times).
 constexpr int KEY_BUCKETS = 4096;
+static_assert(2 * KEY_BUCKETS == FLOODER_FLAG_HIST_WORDS, "flag_hist: the histogram, then the sort's cursors");
 __global__ __launch_bounds__(256) void order_flags_kernel(const int32_t* __restrict__ flag_list,
                                                           const uint32_t* __restrict__ flag_key,
                                                           const int32_t* __restrict__ flag_count,

@@ -380,7 +380,7 @@ int flooder_sweep_cell_f32(const float* pts_sorted, int64_t n_pts, int dim, cons
  * stops recording and evaluates them as they come, so that its candidates are streamed and classified once instead of
  * twice - unless the kept set, extrapolated from the share of the candidates seen so far, exceeds this percentage of
  * the cap ("cell_exh_dense" / "cell_exh_sparse") beyond which the chunk is left to the finish anyway.
- * flag_key / flag_hist (both NULL, or as many uint32 as flag_list holds / 8192 zeroed int32; need top): the probe's
+ * flag_key / flag_hist (both NULL, or as many uint32 as flag_list holds / FLOODER_FLAG_HIST_WORDS zeroed int32; need top): the probe's
  * bound of every flagged tile, parallel to flag_list, and a histogram of the bounds' top 12 bits - with them the
  * finish works the tiles off longest search first.
  * plane_scratch: as flooder_sweep_cell_f32.
@@ -443,7 +443,7 @@ int flooder_sweep_witness_f32(const float* pts_sorted, int64_t n_pts, int dim, c
  *   sweep's probe may already have filled: then probed = 1 and the probe pass is skipped); top: n_simplices uint64
  *   (zeroed unless probed); top_list: n_simplices int32;
  *   flag_key / flag_hist / flag_sorted: all NULL, or what flooder_sweep_cell_faces_f32 filled plus scratch of the
- *   size of flag_list - a counting sort by descending bound puts the long searches first in the last pass's queue
+ *   size of flag_list (flag_hist: FLOODER_FLAG_HIST_WORDS zeroed int32, its second half the sort's) - a counting sort by descending bound puts the long searches first in the last pass's queue
  *   (option "finish_order" 0 turns it off);
  *   hard_scratch / hard_cap: NULL / 0, or 4 * hard_cap uint64 of scratch - a tile that has evaluated more leaves
  *   than option "finish_budget" (14; a wave raises its issue priority after 32 leaves, so a long search runs ahead of
@@ -485,6 +485,9 @@ int flooder_finish_faces_f32(const float* pts_sorted, int64_t n_pts, int dim, co
 #define FLOODER_FINISH_CTL_SINGLE_LEFT 8    /* samples the short-list launch left over                           */
 #define FLOODER_FINISH_CTL_QUEUES 24        /* sharded heads of pass p: + p * FLOODER_QUEUE_WORDS (p = 0, 1, 2)  */
 #define FLOODER_FINISH_CTL_WORDS (FLOODER_FINISH_CTL_QUEUES + 3 * FLOODER_QUEUE_WORDS)
+/* flag_hist of the three launches, zeroed words: the histogram of the flagged tiles' bounds (the top 12 bits: 4096
+ * buckets), then as many cursors of the finish's counting sort */
+#define FLOODER_FLAG_HIST_WORDS 8192
 /* defer_ctl of flooder_sweep_cell_faces_f32, FLOODER_DEFER_CTL_WORDS zeroed words: */
 #define FLOODER_DEFER_CTL_COUNT 0           /* chunks on defer_list ...                                          */
 #define FLOODER_DEFER_CTL_QUEUE 1           /* ... and a word kept for their queue head (popped from `queue`)    */
@@ -667,7 +670,7 @@ typedef struct flooder_fused_sweep_s {
   int32_t* flag_list;
   int32_t* flag_count;
   uint32_t* flag_key;
-  int32_t* flag_hist;
+  int32_t* flag_hist;         /* FLOODER_FLAG_HIST_WORDS zeroed int32 */
   int32_t* flag_sorted;
   uint64_t* top;
   int32_t* top_list;

@@ -16,7 +16,6 @@ pytestmark = pytest.mark.gpu
 
 N_POINTS = 20_000             # three levels of the box tree (16 * 64 < 20 000 <= 16 * 64 * 64)
 INF_BITS = 0x7F800000
-CTL_FLAG_COUNT, CTL_DEFER, CTL_HIST = 1, 12, 48   # the control block of core._sweep_dimension_cell
 ptr = _native.ptr
 
 
@@ -39,74 +38,54 @@ def lattice(ppe, dim, dev):
 
 
 def fused_chain(index, verts, plan, F, positional):
-    """prepare -> witness -> cell -> finish -> face values, buffers laid out as core._sweep_dimension_cell lays them out.
+    """prepare -> witness -> cell -> finish -> face values, on the buffers of a core.FusedWorkspace.
     Returns (face value bits (S, F), simplices the witness sweep handled, flagged tiles the finish was given)."""
     lib, dev = _native.load(), verts.device
     st = _native.current_stream_ptr(dev)
     S, k1, _ = verts.shape
-    R, QW = plan.w_perm.shape[0], core.QUEUE_WORDS
-    tiles, chunks = (R + 63) // 64, (R + 255) // 256
-    planes = torch.empty(24 * S, dtype=torch.float32, device=dev)
-    n_zeroed = QW + _native.CELL_QUEUE_WORDS + _native.FINISH_CTL_WORDS + 2 * S + CTL_HIST + 8192 + S * F
-    zeroed_all = torch.full((n_zeroed,), 7, dtype=torch.int32, device=dev)   # (the prepare launch clears it)
-    qwit, z = zeroed_all[:QW], zeroed_all[QW:]
-    qbuf, z = z[:_native.CELL_QUEUE_WORDS], z[_native.CELL_QUEUE_WORDS:]
-    fctl, z = z[:_native.FINISH_CTL_WORDS], z[_native.FINISH_CTL_WORDS:]
-    top, ctl, face_bits = z[:2 * S].view(torch.int64), z[2 * S:2 * S + CTL_HIST + 8192], z[2 * S + CTL_HIST + 8192:]
-    flag_count, flag_hist, defer_ctl = ctl[CTL_FLAG_COUNT:], ctl[CTL_HIST:], ctl[CTL_DEFER:]
-    top_count = fctl[_native.FINISH_CTL_TOP_COUNT:]
-    hard = torch.empty(4 * core.FINISH_HARD_CAP, dtype=torch.int64, device=dev)
-    top_list = torch.empty(S, dtype=torch.int32, device=dev)
-    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    flags = torch.empty((3, S * tiles), dtype=torch.int32, device=dev)
-    defer_list = torch.empty(5 * S * chunks, dtype=torch.int32, device=dev)
-    defer_c = torch.empty(5 * S * chunks, dtype=torch.float32, device=dev)
-    split = torch.empty((2, S), dtype=torch.int32, device=dev)
-    wgt = torch.empty(S, dtype=torch.float32, device=dev)
+    R = plan.w_perm.shape[0]
+    ws = core.FusedWorkspace(S, R, F, None, dev, wit=True, owner=False)
+    ws.arena.fill_(7)   # (the prepare launch clears it)
+    flags, split, d2 = ws.flags, ws.split, ws.d2
     stats = torch.zeros(40, dtype=torch.int64, device=dev)
     coarse_rows, parents, n_coarse = plan.wit
-    _native.check(lib.flooder_simplex_prepare_f32(ptr(index.nodes), index.n, index.dim, ptr(verts), k1, S, ptr(wgt),
-                                                  ptr(planes), ptr(zeroed_all), n_zeroed, st), "flooder_simplex_prepare_f32")
+    _native.check(lib.flooder_simplex_prepare_f32(ptr(index.nodes), index.n, index.dim, ptr(verts), k1, S, ptr(ws.wgt),
+                                                  ptr(ws.planes), ptr(ws.arena), ws.n_words, st), "flooder_simplex_prepare_f32")
     if positional:
         p, n, dim = ptr(index.pts), index.n, index.dim
         _native.check(lib.flooder_sweep_witness_f32(
             p, n, dim, ptr(index.nodes), ptr(verts), ptr(plan.w_perm), k1, R, S, ptr(coarse_rows), n_coarse, ptr(parents),
-            qwit.data_ptr(), ptr(d2), ptr(plan.memb_all), F, face_bits.data_ptr(), None, flags[0].data_ptr(),
-            flag_count.data_ptr(), flags[1].data_ptr(), flag_hist.data_ptr(), top.data_ptr(), ptr(top_list),
-            top_count.data_ptr(), ptr(wgt), split[0].data_ptr(), ptr(planes), stats[16:].data_ptr(), st),
+            ptr(ws.wit_queue), ptr(d2), ptr(plan.memb_all), F, ptr(ws.face_bits), None, ptr(flags[0]),
+            ptr(ws.flag_count), ptr(flags[1]), ptr(ws.flag_hist), ptr(ws.top), ptr(ws.top_list),
+            ptr(ws.top_count), ptr(ws.wgt), ptr(split[0]), ptr(ws.planes), stats[16:].data_ptr(), st),
             "flooder_sweep_witness_f32")
         _native.check(lib.flooder_sweep_cell_faces_f32(
-            p, n, dim, ptr(index.nodes), ptr(verts), ptr(plan.w_perm), k1, R, S, float(core.CELL_ALPHA), qbuf.data_ptr(),
-            ptr(d2), ptr(plan.memb_all), F, face_bits.data_ptr(), None, flags[0].data_ptr(), flag_count.data_ptr(),
-            flags[1].data_ptr(), flag_hist.data_ptr(), top.data_ptr(), ptr(top_list), top_count.data_ptr(), ptr(defer_list),
-            ptr(defer_c), defer_ctl.data_ptr(), ptr(wgt), split[0].data_ptr(), split[1].data_ptr(), ptr(planes),
+            p, n, dim, ptr(index.nodes), ptr(verts), ptr(plan.w_perm), k1, R, S, float(core.CELL_ALPHA), ptr(ws.cell_queue),
+            ptr(d2), ptr(plan.memb_all), F, ptr(ws.face_bits), None, ptr(flags[0]), ptr(ws.flag_count),
+            ptr(flags[1]), ptr(ws.flag_hist), ptr(ws.top), ptr(ws.top_list), ptr(ws.top_count), ptr(ws.defer_list),
+            ptr(ws.defer_c), ptr(ws.defer_ctl), ptr(ws.wgt), ptr(split[0]), ptr(split[1]), ptr(ws.planes),
             ptr(index.dens), ptr(index.box), stats[0:].data_ptr(), st), "flooder_sweep_cell_faces_f32")
         _native.check(lib.flooder_finish_faces_f32(
-            p, n, dim, ptr(index.nodes), ptr(verts), ptr(plan.w_perm), k1, R, S, flags[0].data_ptr(), flag_count.data_ptr(),
-            flags[1].data_ptr(), flag_hist.data_ptr(), flags[2].data_ptr(), fctl.data_ptr(), top.data_ptr(), ptr(top_list), 1,
-            ptr(d2), ptr(plan.memb_all), F, face_bits.data_ptr(), None, ptr(hard), core.FINISH_HARD_CAP,
+            p, n, dim, ptr(index.nodes), ptr(verts), ptr(plan.w_perm), k1, R, S, ptr(flags[0]), ptr(ws.flag_count),
+            ptr(flags[1]), ptr(ws.flag_hist), ptr(flags[2]), ptr(ws.finish_ctl), ptr(ws.top), ptr(ws.top_list), 1,
+            ptr(d2), ptr(plan.memb_all), F, ptr(ws.face_bits), None, ptr(ws.hard), core.FINISH_HARD_CAP,
             stats[9:].data_ptr(), st), "flooder_finish_faces_f32")
     else:
         blk = _native.FusedSweep(
             pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, density_grid=index.dens,
             cloud_box=index.box, verts=verts, weights=plan.w_perm, R=R, n_faces=F, n_simplices=S, memb=plan.memb_all,
-            alpha=float(core.CELL_ALPHA), face_bits=face_bits.data_ptr(), d2_scratch=d2, flag_list=flags[0].data_ptr(),
-            flag_count=flag_count.data_ptr(), flag_key=flags[1].data_ptr(), flag_hist=flag_hist.data_ptr(),
-            flag_sorted=flags[2].data_ptr(), top=top.data_ptr(), top_list=top_list, top_count=top_count.data_ptr(),
-            simplex_weight=wgt, plane_scratch=planes, cell_queue=qbuf.data_ptr(), defer_list=defer_list, defer_c=defer_c,
-            defer_ctl=defer_ctl.data_ptr(), light_list=split[0].data_ptr(), heavy_list=split[1].data_ptr(),
-            cell_stats=stats[0:].data_ptr(), finish_ctl=fctl.data_ptr(), hard_scratch=hard, hard_cap=core.FINISH_HARD_CAP,
-            probed=1, finish_stats=stats[9:].data_ptr(), n_coarse=n_coarse, coarse_rows=coarse_rows, parents=parents,
-            wit_queue=qwit.data_ptr(), wit_item_list=split[0].data_ptr(), wit_stats=stats[16:].data_ptr(), planes_ready=1)
+            alpha=float(core.CELL_ALPHA), cell_stats=stats[0:].data_ptr(), probed=1, finish_stats=stats[9:].data_ptr(),
+            n_coarse=n_coarse, coarse_rows=coarse_rows, parents=parents, wit_stats=stats[16:].data_ptr(), planes_ready=1,
+            **ws.block_fields())
         if plan.wit_runs is not None:
             blk.wit_runs, blk.wit_run_len, blk.wit_n_runs = plan.wit_runs[0].data_ptr(), plan.wit_runs[1], plan.wit_runs[2]
         _native.check(lib.flooder_fused_witness(ctypes.byref(blk), st), "flooder_fused_witness")
         _native.check(lib.flooder_fused_cell(ctypes.byref(blk), st), "flooder_fused_cell")
         _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
     out = torch.empty((S, F), dtype=torch.float32, device=dev)
-    _native.check(lib.flooder_face_values_f32(face_bits.data_ptr(), S * F, ptr(out), st), "flooder_face_values_f32")
+    _native.check(lib.flooder_face_values_f32(ptr(ws.face_bits), S * F, ptr(out), st), "flooder_face_values_f32")
     torch.cuda.synchronize()
-    return out.view(torch.int32).cpu(), int(stats[16].item()), int(flag_count[0].item())
+    return out.view(torch.int32).cpu(), int(stats[16].item()), int(ws.flag_count[0].item())
 
 
 @pytest.mark.parametrize("dim,ppe", [(2, 32), (3, 14)])   # 528 / 560 rows: the first lattices of core.WIT_MIN_ROWS rows

@@ -45,7 +45,8 @@ class Case:
         self.slot, self.n_slots, _ = core.shared_face_slots(self.stree, d, rows, [v.cpu().numpy() for v in self.vertex_idxs], DEV)
         self.index = core.PointIndex(self.pts)
 
-    def sweep(self, owner, slots=True, mine=None, stats=None, grouped=False):
+    def sweep(self, owner, slots=True, mine=None, stats=None, grouped=False, spare=0):
+        """`spare`: slots behind the complex's own that no simplex touches"""
         keep = core.FACE_OWNER, core.FACE_OWNER_GROUPED
         core.FACE_OWNER, core.FACE_OWNER_GROUPED = owner, grouped
         try:
@@ -56,7 +57,7 @@ class Case:
                 simp, slot = simp[mine], slot[torch.as_tensor(mine, device=DEV)].contiguous()
             verts = self.lms[torch.as_tensor(simp, device=DEV)].contiguous()
             out, _ = core._sweep_dimension_cell(self.index, verts, self.weights, self.faces, None, stats=stats, plan=plan,
-                                                face_slots=(slot, self.n_slots) if slots else None)
+                                                face_slots=(slot, self.n_slots + spare) if slots else None)
             if mine is not None and slots:   # (what a rank contributes to the MIN over the ranks: bench.py)
                 out = torch.maximum(out, core.shard_slot_fill(slot, self.n_slots))
             torch.cuda.synchronize()
@@ -166,6 +167,26 @@ def test_ownership_removes_work_on_the_gaussian(gauss):
           counts[True, True].tolist(), "without", counts[False, False].tolist())
     for key in ((True, False), (True, True)):
         assert counts[key][0] < counts[False, False][0] and counts[key][1] < counts[False, False][1]
+
+
+def test_both_parities_of_the_pad_word_before_the_owner_words():
+    """the owner words are 64-bit and follow the face words in the sweep's arena (core.fused_layout): with one spare slot
+    more the pad word in front of them comes or goes, and no value may move"""
+    case = Case(cloud("gauss", 20_000), 10, n_lms=40)
+    S, n = case.simp.shape[0], case.n_slots
+    before = [sum(core.fused_layout(S, n + spare, False, True)[0]["face_bits"]) for spare in (0, 1)]
+    assert before[0] & 1 != before[1] & 1   # (the witness queue in front, where it runs, is an even number of words)
+    for spare in (0, 1):
+        owner_at, owner_words = core.fused_layout(S, n + spare, False, True)[0]["face_owner"]
+        assert owner_at == before[spare] + (before[spare] & 1) and owner_at % 2 == 0 and owner_words == 2 * (n + spare)
+    exact, padded = case.sweep(True), case.sweep(True, spare=1)
+    assert exact.shape == (n,) and padded.shape == (n + 1,)
+    assert np.array_equal(exact, padded[:n]) and padded[n] == 0   # (the bits of 0.0)
+    assert np.array_equal(exact, case.sweep(False))
+    verts = case.lms[torch.as_tensor(case.simp, device=DEV)].contiguous()
+    tree, _ = core._sweep_dimension_bvh(case.index, verts, case.weights, case.faces, None)
+    torch.cuda.synchronize()
+    assert np.array_equal(tree.cpu().numpy().view(np.int32), exact[case.slot.cpu().numpy()])
 
 
 def test_closure_entry_on_hand_made_words():

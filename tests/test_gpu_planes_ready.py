@@ -1,7 +1,7 @@
 """`planes_ready` of flooder_fused_sweep_t (include/flooder_hip.h): the caller, not a note inside the library, says whether
 plane_scratch holds the face-plane rows of these simplices.  The chain the product runs - flooder_simplex_prepare_f32,
 flooder_fused_witness, flooder_fused_cell, flooder_fused_finish, flooder_face_values_f32 - is called here entry by
-entry, with the buffers laid out as core._sweep_dimension_cell lays them out.  Runs on a real MI355X only (-m gpu)."""
+entry, on the buffers of a core.FusedWorkspace.  Runs on a real MI355X only (-m gpu)."""
 import ctypes
 
 import pytest
@@ -30,49 +30,30 @@ def fused_chain(index, verts, plan, n_faces, planes_ready, between=None, planes=
     lib, dev = _native.load(), verts.device
     st = _native.current_stream_ptr(dev)
     S, k1, _ = verts.shape
-    R, F, QW = plan.w_perm.shape[0], n_faces, core.QUEUE_WORDS
-    tiles, chunks = (R + 63) // 64, (R + 255) // 256
-    if planes is None:
-        planes = torch.empty(24 * S, dtype=torch.float32, device=dev)
-    assert planes.numel() == 24 * S and planes.is_contiguous()
-    n_zeroed = 7 * QW + 24 + 2 * S + 48 + 8192 + S * F
-    zeroed_all = torch.full((n_zeroed,), 7, dtype=torch.int32, device=dev)   # (the prepare launch clears it)
-    qwit, z = zeroed_all[:QW], zeroed_all[QW:]
-    qbuf, fctl, z = z[:3 * QW], z[3 * QW:6 * QW + 24], z[6 * QW + 24:]
-    top, ctl, face_bits = z[:2 * S].view(torch.int64), z[2 * S:2 * S + 48 + 8192], z[2 * S + 48 + 8192:]
-    hard = torch.empty(4 * core.FINISH_HARD_CAP, dtype=torch.int64, device=dev)
-    top_list = torch.empty(S, dtype=torch.int32, device=dev)
-    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    flags = torch.empty((3, S * tiles), dtype=torch.int32, device=dev)
-    defer_list = torch.empty(5 * S * chunks, dtype=torch.int32, device=dev)
-    defer_c = torch.empty(5 * S * chunks, dtype=torch.float32, device=dev)
-    split = torch.empty((2, S), dtype=torch.int32, device=dev)
-    wgt = torch.empty(S, dtype=torch.float32, device=dev)
+    R, F = plan.w_perm.shape[0], n_faces
+    assert planes is None or (planes.numel() == 24 * S and planes.is_contiguous())
+    ws = core.FusedWorkspace(S, R, F, None, dev, wit=True, owner=False, planes=planes)
+    ws.arena.fill_(7)   # (the prepare launch clears it)
+    planes = ws.planes
     stats = torch.zeros(40, dtype=torch.int64, device=dev)
     _native.check(lib.flooder_simplex_prepare_f32(_native.ptr(index.nodes), index.n, index.dim, _native.ptr(verts), k1, S,
-                                                  _native.ptr(wgt), _native.ptr(planes), _native.ptr(zeroed_all), n_zeroed,
+                                                  _native.ptr(ws.wgt), _native.ptr(planes), _native.ptr(ws.arena), ws.n_words,
                                                   st), "flooder_simplex_prepare_f32")
     if between is not None:
         between(verts, planes)
     blk = _native.FusedSweep(
         pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, density_grid=index.dens,
         cloud_box=index.box, verts=verts, weights=plan.w_perm, R=R, n_faces=F, n_simplices=S, memb=plan.memb_all,
-        alpha=float(core.CELL_ALPHA), face_bits=face_bits, d2_scratch=d2, flag_list=flags[0],
-        flag_count=ctl[1:].data_ptr(), flag_key=flags[1].data_ptr(), flag_hist=ctl[48:].data_ptr(),
-        flag_sorted=flags[2].data_ptr(), top=top.data_ptr(), top_list=top_list, top_count=fctl[3:].data_ptr(),
-        simplex_weight=wgt, plane_scratch=planes, cell_queue=qbuf.data_ptr(), defer_list=defer_list, defer_c=defer_c,
-        defer_ctl=ctl[12:].data_ptr(), light_list=split[0].data_ptr(), heavy_list=split[1].data_ptr(),
-        cell_stats=stats[0:9], finish_ctl=fctl.data_ptr(), hard_scratch=hard, hard_cap=core.FINISH_HARD_CAP, probed=1,
-        finish_stats=stats[9:16], n_coarse=plan.wit[2], coarse_rows=plan.wit[0], parents=plan.wit[1],
-        wit_queue=qwit.data_ptr(), wit_item_list=split[0].data_ptr(), wit_stats=stats[16:40],
-        planes_ready=planes_ready)
+        alpha=float(core.CELL_ALPHA), cell_stats=stats[0:9], probed=1, finish_stats=stats[9:16], n_coarse=plan.wit[2],
+        coarse_rows=plan.wit[0], parents=plan.wit[1], wit_stats=stats[16:40], planes_ready=planes_ready,
+        **ws.block_fields())
     if plan.wit_runs is not None:
         blk.wit_runs, blk.wit_run_len, blk.wit_n_runs = plan.wit_runs[0].data_ptr(), plan.wit_runs[1], plan.wit_runs[2]
     _native.check(lib.flooder_fused_witness(ctypes.byref(blk), st), "flooder_fused_witness")
     _native.check(lib.flooder_fused_cell(ctypes.byref(blk), st), "flooder_fused_cell")
     _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
     out = torch.empty((S, F), dtype=torch.float32, device=dev)
-    _native.check(lib.flooder_face_values_f32(_native.ptr(face_bits), S * F, _native.ptr(out), st),
+    _native.check(lib.flooder_face_values_f32(_native.ptr(ws.face_bits), S * F, _native.ptr(out), st),
                   "flooder_face_values_f32")
     torch.cuda.synchronize()
     return out.view(torch.int32).cpu(), stats[16:40].cpu(), planes

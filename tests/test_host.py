@@ -191,8 +191,9 @@ def test_control_words_have_the_values_of_the_header(tmp_path):
     if cc is None:
         pytest.skip("no C compiler")
     header = open(os.path.join(ROOT, "include", "flooder_hip.h")).read()
-    names = re.findall(r"#define FLOODER_((?:FINISH_CTL|DEFER_CTL|CELL_QUEUE|WIT_QUEUE)_[A-Z_]+|QUEUE_WORDS)\b", header)
-    assert len(names) == len(set(names)) == 22, names
+    names = re.findall(r"#define FLOODER_((?:FINISH_CTL|DEFER_CTL|CELL_QUEUE|WIT_QUEUE)_[A-Z_]+|QUEUE_WORDS|FLAG_HIST_WORDS)\b",
+                       header)
+    assert len(names) == len(set(names)) == 23, names
     src = tmp_path / "words.c"
     src.write_text("\n".join(['#include <stdio.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
                               'int main(void) {'] + [f'printf("{n} %d\\n", (int)(FLOODER_{n}));' for n in names] +
