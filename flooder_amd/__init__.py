@@ -12,6 +12,7 @@ from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
 from .grad import FloodFiltration, flood_filtration
 from .profile import FloodProfile, flood_profile
+from .neighbors import neighbor_distance
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -27,6 +28,7 @@ __all__ = [
     "FloodFiltration",
     "flood_profile",
     "FloodProfile",
+    "neighbor_distance",
     "generate_landmarks",
     "generate_grid",
     "generate_uniform_weights",

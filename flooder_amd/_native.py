@@ -90,7 +90,15 @@ class KnnSweep(_Block):
         i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats""")
 
 
-KNN_COLS_MAX = 64   # FLOODER_KNN_COLS_MAX: every (k, stat) pair with k <= 32 and two statistics
+class KnnSorted(_Block):
+    """``flooder_knn_sorted_t``: the k-nearest sweep over tiles of 64 consecutive entries of a sample order (the robust
+    dimension pass above 3-D; ``neighbor_distance`` in its query form k1 = R = 1)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
+        i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats; p sample_order""")
+
+
+KNN_COLS_MAX = 64  # FLOODER_KNN_COLS_MAX: every (k, stat) pair with k <= 32 and two statistics
 
 
 class KnnProfile(_Block):
@@ -236,6 +244,8 @@ SIGNATURES = {
     "flooder_segment_sum_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     # the k nearest points of every sample (flood_complex(neighbors=k))
     "flooder_sweep_knn_f32": (c_int, [ctypes.POINTER(KnnSweep), c_void_p]),
+    # ... the same sweep over tiles of the sorted sample order (above 3-D; neighbor_distance)
+    "flooder_sweep_knn_sorted_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p]),
     # ... every (k, stat) column of a list from one sweep at the largest k (flood_profile)
     "flooder_sweep_knn_profile_f32": (c_int, [ctypes.POINTER(KnnProfile), c_void_p]),
     # ... and which k points realise the statistic of a witness sample (flood_filtration(neighbors=k))

@@ -1316,6 +1316,14 @@ def shards_sorted_tiles(dim: int, S: int, R: int, method: str) -> bool:
     return SHARD_SORTED_TILES and method == "bvh" and bvh_sorts_samples(dim, S, R)
 
 
+def _zeroed_queue(lib, dev, n_sorted: int = 0):
+    """(sharded work-queue heads, state words of the radix sort of ``n_sorted`` sample keys or None) from ONE zero fill:
+    ``flooder_index_sort_zeroed`` then makes no memset launch of its own (nine for four passes)."""
+    n_sort_state = int(lib.flooder_index_sort_state_words(n_sorted, 32)) if n_sorted and SORT_STATE_BY_CALLER else 0
+    zeroed = torch.zeros(QUEUE_WORDS + n_sort_state, dtype=torch.int32, device=dev)
+    return zeroed[:QUEUE_WORDS], (zeroed[QUEUE_WORDS:] if n_sort_state else None)
+
+
 def _sorted_sample_order(lib, st, index: PointIndex, verts: torch.Tensor, w_perm: torch.Tensor,
                          sort_state: Optional[torch.Tensor], late_rows: Optional[torch.Tensor], bits: int) -> torch.Tensor:
     """The sort stage of the sorted-sample sweep: a Z-order key per sample of every simplex -> one radix sort on the low
@@ -1374,12 +1382,8 @@ def _sweep_dimension_bvh(index: PointIndex, verts: torch.Tensor, weights: torch.
     w_perm, rows_perm = plan.w_perm, plan.rows_perm
 
     sorted_samples = bvh_sorts_samples(index.dim, S, R)
-    # sharded work-queue heads + (sorted samples) the state of the radix sort of the sample keys, one zero fill for both:
-    # flooder_index_sort_zeroed then makes no memset launch of its own (nine for four passes)
-    n_sort_state = (int(lib.flooder_index_sort_state_words(S * R, 32)) if sorted_samples and SORT_STATE_BY_CALLER else 0)
-    queue = torch.zeros(QUEUE_WORDS + n_sort_state, dtype=torch.int32, device=dev)
-    sort_state = queue[QUEUE_WORDS:] if n_sort_state else None
-    queue = queue[:QUEUE_WORDS]
+    # sharded work-queue heads + (sorted samples) the state of the radix sort of the sample keys, one zero fill for both
+    queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)
     if (sorted_samples and SORTED_FUSED_FACES and not want_dist and reduce_hook is None and plan.memb_all is not None
             and plan.late_rows is not None and tile_shard is None):
         # ---- only the face maxima are wanted: the sorted sweep delivers them itself (no (S, R) buffer, no face-max
@@ -1481,6 +1485,20 @@ def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, red
     return neighbors, method
 
 
+# The k-nearest sweep over tiles of the sorted sample order (``flooder_sweep_knn_sorted_f32``) instead of one simplex per
+# tile: None = where ``bvh_sorts_samples`` says so (above 3 dimensions), True / False = always / never (within the sorted
+# sweeps' limits).  A Python constant for A/B runs and tests, the twin of ``BVH_SORTED_SAMPLES``; the values do not
+# depend on it.  The default follows the measurement of DESIGN.md section 9.3 (tools/time_knn.py).
+KNN_SORTED_SAMPLES: Optional[bool] = None
+
+
+def knn_sorts_samples(dim: int, S: int, R: int) -> bool:
+    """Does the robust dimension pass of S simplices x R samples in ``dim`` dimensions sweep sorted tiles?"""
+    if KNN_SORTED_SAMPLES is None:
+        return bvh_sorts_samples(dim, S, R)
+    return bool(KNN_SORTED_SAMPLES) and BVH_SORTED_MIN_SAMPLES <= S * R < (1 << 32) - 2 and S * R * 20 <= SORTED_WORKSPACE_BYTES
+
+
 def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                          k: int, stat: str, plan: Optional["SamplePlan"] = None,
                          stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None, keep=None):
@@ -1488,7 +1506,9 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     maxima of the k-distance (``stat="kth"``) or of the distance to the empirical measure (``"dtm"``).
 
     sweep_knn (plain stores of the SQUARED statistic's bits into the (S, R) buffer, samples in the order of
-    ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  No host synchronisation.  ``keep``: a callable
+    ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  Where ``knn_sorts_samples`` says so the sweep
+    runs over tiles of the sorted sample order (sample keys -> radix sort -> ``flooder_sweep_knn_sorted_f32``, all inside
+    the ``sweep`` span) into the same buffer: the same words.  No host synchronisation.  ``keep``: a callable
     that is handed the (S, R) int32 buffer (columns in swept order) - ``flood_filtration`` finds its witnesses there."""
     lib = _native.load()
     dev = index.pts.device
@@ -1497,13 +1517,21 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     R = weights.shape[0]
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
-    queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
+    sorted_samples = knn_sorts_samples(index.dim, S, R)
+    queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)   # sharded work-queue heads
     d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    blk = _native.KnnSweep(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
-                           weights=plan.w_perm, R=R, k=int(k), n_simplices=S, stat=NEIGHBOR_STATS.index(stat),
-                           queue=queue, out_bits=d2, stats=stats)
+    args = dict(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
+                weights=plan.w_perm, R=R, k=int(k), n_simplices=S, stat=NEIGHBOR_STATS.index(stat), queue=queue,
+                out_bits=d2, stats=stats)
     with _span(timer, "sweep"):
-        _native.check(lib.flooder_sweep_knn_f32(ctypes.byref(blk), st), "flooder_sweep_knn_f32")
+        if sorted_samples:
+            order = _sorted_sample_order(lib, st, index, verts, plan.w_perm, sort_state, None,
+                                         int(lib.flooder_sample_key_bits(index.dim)))
+            blk = _native.KnnSorted(sample_order=order, **args)
+            _native.check(lib.flooder_sweep_knn_sorted_f32(ctypes.byref(blk), st), "flooder_sweep_knn_sorted_f32")
+        else:
+            blk = _native.KnnSweep(**args)
+            _native.check(lib.flooder_sweep_knn_f32(ctypes.byref(blk), st), "flooder_sweep_knn_f32")
     out_face, _ = _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer)
     if keep is not None:
         keep(d2)

@@ -31,6 +31,15 @@
 // over them is the sum the single sweep forms at k = t, so one walk of the K slots stores the word of every listed
 // column into that column's (S, R) plane - the words flooder_sweep_knn_f32 writes for that (k, stat), bit for bit.
 // One kernel body serves both; the epilogue is selected at compile time.
+//
+// flooder_sweep_knn_sorted_f32 is the same sweep over SORTED TILES (SORTED): a wave takes 64 consecutive entries of
+// `sample_order` - the samples of ALL simplices along the curve order of flood_sorted.hip, neighbours in space whatever
+// simplex they belong to - instead of the samples of one simplex, and stores each word to its own cell (scattered
+// 4-byte stores, every cell written once).  Only where a wave gets its 64 samples and where it stores them differs: the
+// walk, the lists and the epilogue are the lines below for every form.  The exactness argument above does not mention
+// which samples share a wave, so the words are those of flooder_sweep_knn_f32; the order is a performance input only.
+// With k1 = 1, R = 1 and weights = [[1.0]] a "simplex" is a query point (fma(1.0f, v, 0.0f) is v): the form that
+// flooder_amd.neighbor_distance runs.
 
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
@@ -47,19 +56,22 @@ struct KnnProfileCols {   // column of (statistic, rank - 1), -1: not asked for 
 
 // PROFILE = false: flooder_sweep_knn_f32, one word per sample (`stat` of its k values; `cols` is not read).
 // PROFILE = true: flooder_sweep_knn_profile_f32, k = the largest k of the columns, out_bits holds a plane per column.
-template <int DIM, int K, bool PROFILE>
+// SORTED = false: an item is (simplex, tile of 64 of its samples; `order` is not read).
+// SORTED = true: flooder_sweep_knn_sorted_f32, an item is 64 consecutive entries of `order` (n_simplices * R of them).
+template <int DIM, int K, bool PROFILE, bool SORTED>
 __global__ __launch_bounds__(256) void sweep_knn_kernel(
     const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
     const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int k, int stat,
     int32_t* __restrict__ queue, uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats,
-    KnnProfileCols cols) {
+    KnnProfileCols cols, const uint32_t* __restrict__ order) {
   constexpr int DP = padded_dim(DIM);
   __shared__ float s_lb[4][MAXL][FAN];
   __shared__ int64_t s_grp[4][MAXL];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const int tiles = (R + 63) / 64;
-  const int64_t n_items = n_simplices * tiles;
+  const int64_t n_samples = n_simplices * (int64_t)R;
+  const int64_t n_items = SORTED ? (n_samples + 63) / 64 : n_simplices * tiles;
   const int top = lv.n_levels - 1;
   const int first = K - k;   // the k live slots are list[first .. K-1]  (wave-uniform)
   unsigned long long n_leaf_eval = 0, n_leaf_test = 0, n_node_test = 0, max_item_tests = 0;
@@ -69,13 +81,24 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
     const int64_t g = queue_pop(queue, q_shard, q_tried, n_items, lane);  // sharded heads (flood_common.hpp)
     if (g < 0) break;
     const unsigned long long tests_before = n_leaf_test + n_node_test;
-    const int64_t s = g / tiles;
-    const int tile = (int)(g - s * tiles);
-
-    // ---- this lane's sample: p = sum_j w[r,j] * v[s,j,:], as sweep_bvh builds it
-    int r = tile * 64 + lane;
-    const bool live = r < R;
-    if (!live) r = R - 1;  // duplicate of the last sample, never stored
+    // ---- this lane's sample (s, r): of the item's simplex, or entry `lane` of the item's run of the sorted order
+    int64_t s;
+    int r;
+    bool live;
+    if constexpr (SORTED) {
+      const int64_t pos = g * 64 + lane;
+      live = pos < n_samples;
+      const uint32_t id = order[live ? pos : n_samples - 1];  // duplicate of the last entry, never stored
+      const uint32_t si = id / (uint32_t)R;
+      s = (int64_t)si;
+      r = (int)(id - si * (uint32_t)R);
+    } else {
+      s = g / tiles;
+      r = (int)(g - s * tiles) * 64 + lane;
+      live = r < R;
+      if (!live) r = R - 1;  // duplicate of the last sample, never stored
+    }
+    // p = sum_j w[r,j] * v[s,j,:], as sweep_bvh builds it
     float p[DIM];
     const float* vs = verts + s * (int64_t)k1 * DIM;
 #pragma unroll
@@ -232,7 +255,13 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
   }
 }
 
-// The launch of sweep_knn_kernel<DIM, K, PROFILE> at K = the smallest of 2, 4, 8, 16, 32 that holds k.
+// the sorted order of a block that has one
+inline const int32_t* order_of(const flooder_knn_sorted_t& a) { return a.sample_order; }
+template <typename Args>
+inline const int32_t* order_of(const Args&) { return nullptr; }
+
+// The launch of sweep_knn_kernel<DIM, K, PROFILE, SORTED> at K = the smallest of 2, 4, 8, 16, 32 that holds k; SORTED
+// for the block that carries a sample order.
 // (the tree sweeps exist for one ambient dimension as well; the k-nearest sweep is defined for 2 .. 8: `who_dim`)
 template <int DIM, bool PROFILE, typename Args>
 int launch_sweep_knn(const Args& a, int k, int stat, const KnnProfileCols& cols, const Levels& lv, hipStream_t st,
@@ -240,13 +269,15 @@ int launch_sweep_knn(const Args& a, int k, int stat, const KnnProfileCols& cols,
   if constexpr (DIM < 2) {
     return fail(FLOODER_E_ARG, who_dim);
   } else {
-    const int64_t n_items = a.n_simplices * ((a.R + 63) / 64);
+    constexpr bool SORTED = std::is_same<Args, flooder_knn_sorted_t>::value;
+    const int64_t n_items = SORTED ? (a.n_simplices * (int64_t)a.R + 63) / 64 : a.n_simplices * ((a.R + 63) / 64);
     int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
     if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
     auto launch = [&](auto kc) {
-      hipLaunchKernelGGL((sweep_knn_kernel<DIM, decltype(kc)::value, PROFILE>), dim3((unsigned)grid), dim3(256), 0, st,
+      hipLaunchKernelGGL((sweep_knn_kernel<DIM, decltype(kc)::value, PROFILE, SORTED>), dim3((unsigned)grid), dim3(256), 0, st,
                          a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, k, stat, a.queue,
-                         a.out_bits, reinterpret_cast<unsigned long long*>(a.stats), cols);
+                         a.out_bits, reinterpret_cast<unsigned long long*>(a.stats), cols,
+                         reinterpret_cast<const uint32_t*>(order_of(a)));
     };
     if (k <= 2) launch(std::integral_constant<int, 2>{});
     else if (k <= 4) launch(std::integral_constant<int, 4>{});
@@ -262,6 +293,14 @@ struct SweepKnnOp {
   static int run(const flooder_knn_sweep_t& a, const Levels& lv, hipStream_t st) {
     return launch_sweep_knn<DIM, false>(a, a.k, a.stat, KnnProfileCols{}, lv, st, "sweep_knn",
                                         "flooder_sweep_knn_f32: dim must be in 2..8");
+  }
+};
+
+template <int DIM>
+struct SweepKnnSortedOp {
+  static int run(const flooder_knn_sorted_t& a, const Levels& lv, hipStream_t st) {
+    return launch_sweep_knn<DIM, false>(a, a.k, a.stat, KnnProfileCols{}, lv, st, "sweep_knn_sorted",
+                                        "flooder_sweep_knn_sorted_f32: dim must be in 2..8");
   }
 };
 
@@ -293,6 +332,25 @@ extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream)
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad argument (null pointer, fewer points than k, k1, R)");
   const Levels lv = make_levels(a.n_pts);
   return dispatch_dim<SweepKnnOp>(a.dim, a, lv, (hipStream_t)stream);
+}
+
+extern "C" int flooder_sweep_knn_sorted_f32(const flooder_knn_sorted_t* p, void* stream) {
+  flooder_knn_sorted_t a;
+  if (int rc = take(p, a, "flooder_sweep_knn_sorted_f32: bad parameter block (abi / size)")) return rc;
+  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: k must be in 1..32");
+  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: dim must be in 2..8");
+  if (a.stat != 0 && a.stat != 1)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: stat must be 0 (kth) or 1 (dtm)");
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.n_pts < a.k || a.k1 < 1 ||
+      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: bad argument (null pointer, fewer points than k, k1, R)");
+  if (!a.sample_order) return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: sample_order is NULL");
+  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
+    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: n_simplices * R must be below 2^32 - 2");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<SweepKnnSortedOp>(a.dim, a, lv, (hipStream_t)stream);
 }
 
 extern "C" int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream) {

@@ -868,6 +868,41 @@ typedef struct flooder_knn_sweep_s {        /* flooder_sweep_knn_f32 */
 int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream);
 
 /*
+ * flooder_sweep_knn_sorted_f32: flooder_sweep_knn_f32 over SORTED TILES.  A wave takes 64 consecutive entries of
+ * sample_order - N = n_simplices * R ids g = s * R + r, each once, as flooder_sample_keys_f32 + flooder_index_sort
+ * produce them for flooder_sorted_minima - instead of the samples of one simplex: ceil(N / 64) tiles of samples that
+ * are neighbours in space whatever simplex they belong to, all 64 lanes busy.  Everything else is the kernel of
+ * flooder_sweep_knn_f32 (same samples, same distances, same lists, same epilogue, same counters per tile), and
+ * out_bits[s, r] receives, by a scattered 4-byte store, every cell once, the word flooder_sweep_knn_f32 writes there:
+ * the k smallest of a multiset depend neither on the order of offering nor on which samples share a wave.  The order
+ * is a performance input only - any permutation of 0 .. N - 1 gives the same words; an entry >= N is out of bounds.
+ * Query form: k1 = 1, R = 1, weights = {1.0f} and verts = (Q, dim) query points give out_bits[q] = the squared
+ * statistic of query q (flooder_amd.neighbor_distance); queries must be finite.
+ * Refused (FLOODER_E_ARG) as flooder_sweep_knn_f32 refuses, and: sample_order NULL, n_simplices * R >= 2^32 - 2.
+ * n_simplices == 0 or R == 0: FLOODER_OK, no pointer is looked at.
+ */
+typedef struct flooder_knn_sorted_s {       /* flooder_sweep_knn_sorted_f32 */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) */
+  int32_t R;
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_MAX */
+  int64_t n_simplices;
+  int32_t stat;               /* 0 = kth, 1 = dtm */
+  int32_t reserved;
+  int32_t* queue;
+  uint32_t* out_bits;         /* (n_simplices, R) */
+  uint64_t* stats;            /* may be NULL */
+  const int32_t* sample_order;  /* N = n_simplices * R entries, as flooder_sorted_sweep_t's */
+} flooder_knn_sorted_t;
+int flooder_sweep_knn_sorted_f32(const flooder_knn_sorted_t* p, void* stream);
+
+/*
  * flooder_sweep_knn_profile_f32: ONE sweep at k_max = max(col_k) that writes a plane of flooder_sweep_knn_f32's words
  * for every listed (k, stat) column (flooder_amd.flood_profile).  A lane ends a tile with its k_max smallest d2
  * ascending in registers; the first t of them are its t smallest, and the running ascending float32 sum over them is
