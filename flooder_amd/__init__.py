@@ -12,7 +12,7 @@ from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
 from .grad import FloodFiltration, flood_filtration
 from .profile import FloodProfile, flood_profile
-from .neighbors import neighbor_distance
+from .neighbors import neighbor_distance, nearest_neighbors
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -29,6 +29,7 @@ __all__ = [
     "flood_profile",
     "FloodProfile",
     "neighbor_distance",
+    "nearest_neighbors",
     "generate_landmarks",
     "generate_grid",
     "generate_uniform_weights",

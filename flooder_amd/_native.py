@@ -98,6 +98,15 @@ class KnnSorted(_Block):
         i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats; p sample_order""")
 
 
+class KnnIds(_Block):
+    """``flooder_knn_ids_t``: the sweep over sorted tiles keeping (d2 word, original id) keys - which points the k
+    nearest of every sample are (``nearest_neighbors``, the backward of ``neighbor_distance``)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
+        i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats; p sample_order; p order; p out_ids;
+        p out_d2""")
+
+
 KNN_COLS_MAX = 64  # FLOODER_KNN_COLS_MAX: every (k, stat) pair with k <= 32 and two statistics
 
 
@@ -246,6 +255,8 @@ SIGNATURES = {
     "flooder_sweep_knn_f32": (c_int, [ctypes.POINTER(KnnSweep), c_void_p]),
     # ... the same sweep over tiles of the sorted sample order (above 3-D; neighbor_distance)
     "flooder_sweep_knn_sorted_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p]),
+    # ... keeping (d2 word, original id) keys: the neighbours themselves (nearest_neighbors, neighbor_distance's backward)
+    "flooder_knn_ids_sorted_f32": (c_int, [ctypes.POINTER(KnnIds), c_void_p]),
     # ... every (k, stat) column of a list from one sweep at the largest k (flood_profile)
     "flooder_sweep_knn_profile_f32": (c_int, [ctypes.POINTER(KnnProfile), c_void_p]),
     # ... and which k points realise the statistic of a witness sample (flood_filtration(neighbors=k))

@@ -40,6 +40,10 @@
 // which samples share a wave, so the words are those of flooder_sweep_knn_f32; the order is a performance input only.
 // With k1 = 1, R = 1 and weights = [[1.0]] a "simplex" is a query point (fma(1.0f, v, 0.0f) is v): the form that
 // flooder_amd.neighbor_distance runs.
+//
+// flooder_knn_ids_sorted_f32 is the sweep over sorted tiles keeping (d2 word, original id) KEYS per lane: which points
+// the k nearest are (flooder_amd.nearest_neighbors, the backward of neighbor_distance).  Ties decide there, so its culls
+// are strict and its kernel is a sibling (sweep_knn_ids_kernel below, with its own exactness and termination argument).
 
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
@@ -255,6 +259,294 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------- neighbour ids
+// flooder_knn_ids_sorted_f32: the sweep over sorted tiles keeping KEYS (d2 word, original id) instead of d2 words - WHICH
+// points the k nearest are, under the tie rule of flooder_witness_knn (flood_grad.hip).  A sibling of sweep_knn_kernel,
+// not a flag of it: the value sweeps keep their code.  The walk is the one above (keep in step); what differs:
+//
+//   the list   K (hi, lo) register pairs per lane, hi the d2 word compared as a signed int as above, lo the id compared
+//              unsigned.  The K - k front slots hold (-inf, 0), the
+//              smallest key there is; the k live slots start at (+inf, 0xffffffff), above every real key - ids are
+//              below 2^31, and a real d2 that overflowed to +inf still sorts in front of an empty slot.  No hi word
+//              is ever a NaN (d2 of finite inputs is not, and the two fillers are infinities): the culls read
+//              list[K-1].hi as a float.
+//   the culls  STRICT: a node, a leaf or a point is skipped only when lb * SAFE > bound (a point: key > k-th key).
+//   the marks  a visited child and a child past the end of its level hold CLOSED (-1; a bound is never negative), and a
+//              level is left when no child is open or the nearest open one is strictly farther than M.  A bound of
+//              +inf is a bound like any other: while M is +inf (some lane holds fewer than k points) nothing open is
+//              skipped.
+//   the ids    order[row] of the NB rows of a step, wave-uniform, fetched beside the rows through the scalar cache.  Rows
+//              of the padded last leaf (row >= n_pts) are no candidates and order is not read there (the index is
+//              clamped; the row is skipped by a wave-uniform test, whatever its +inf coordinates give).
+//
+// Exactness.  Keys are distinct (ids are), so "the k smallest keys of all points" is ONE set, and inserting any superset
+// of it in any order leaves exactly that set, ascending.  A subtree or a leaf is skipped only when lb * SAFE > the k-th
+// d2 of every lane concerned: each of its points then has a strictly larger d2, hence a larger key whatever its id.  A
+// box at lb == k-th d2 is opened and a point at d2 == k-th d2 is compared by its id: a smaller id displaces the k-th
+// entry.  Nothing is skipped while a lane holds fewer than k points.  The d2 words are those of the value sweep
+// (same samples, same arithmetic), so out_bits - the value sweep's epilogue over the k hi words - is its word, bit for bit.
+//
+// Termination.  Every step of the walk either closes one open child (a mark that no comparison of bounds can undo:
+// `inf <= inf` never reopens anything), descends into a child just closed, or leaves a level for good; levels and
+// children are finite.  At k == n_pts the lists fill only with the last leaf and M stays +inf until then: the walk visits
+// every child once and ends when none is open.
+constexpr float CLOSED = -1.f;
+
+__device__ __forceinline__ uint32_t load_uniform_u32(const uint32_t* p) {   // (load_uniform_row, for one word)
+  typedef const __attribute__((address_space(4))) uint32_t* cptr_t;
+  return *((cptr_t)(uintptr_t)p);
+}
+
+// key (ah, al) < key (bh, bl): hi signed, lo unsigned  (three 32-bit comparisons: as one signed 64-bit comparison of
+// (hi << 32 | lo) the list wants aligned register pairs, 8 to 30 VGPRs more and a wave per SIMD fewer at K = 8 and 16;
+// timed, the two forms are within 5 % of each other, either way, at every k)
+__device__ __forceinline__ bool key_less(int ah, uint32_t al, int bh, uint32_t bl) {
+  return ah < bh || (ah == bh && al < bl);
+}
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+template <int DIM, int K>
+__global__ __launch_bounds__(256) void sweep_knn_ids_kernel(
+    const float* __restrict__ pts, int64_t n_pts, const float* __restrict__ nodes, Levels lv,
+    const float* __restrict__ verts, const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int k,
+    int stat, int32_t* __restrict__ queue, const uint32_t* __restrict__ order, const uint32_t* __restrict__ pt_id,
+    uint32_t* __restrict__ out_ids, uint32_t* __restrict__ out_d2, uint32_t* __restrict__ out_bits,
+    unsigned long long* __restrict__ stats) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ float s_lb[4][MAXL][FAN];
+  __shared__ int64_t s_grp[4][MAXL];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int64_t n_samples = n_simplices * (int64_t)R;
+  const int64_t n_items = (n_samples + 63) / 64;
+  const int top = lv.n_levels - 1;
+  const int first = K - k;   // the k live slots are list[first .. K-1]  (wave-uniform)
+  unsigned long long n_leaf_eval = 0, n_leaf_test = 0, n_node_test = 0, max_item_tests = 0;
+
+  int q_shard = (int)(((int64_t)blockIdx.x * 4 + wv) % QSHARDS), q_tried = 0;
+  for (;;) {
+    const int64_t g = queue_pop(queue, q_shard, q_tried, n_items, lane);
+    if (g < 0) break;
+    const unsigned long long tests_before = n_leaf_test + n_node_test;
+    // ---- this lane's sample (s, r): entry `lane` of the item's run of the sorted order
+    const int64_t pos = g * 64 + lane;
+    const bool live = pos < n_samples;
+    const uint32_t sid = order[live ? pos : n_samples - 1];  // duplicate of the last entry, never stored
+    const uint32_t si = sid / (uint32_t)R;
+    const int64_t s = (int64_t)si;
+    const int r = (int)(sid - si * (uint32_t)R);
+    float p[DIM];
+    const float* vs = verts + s * (int64_t)k1 * DIM;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) p[c] = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) p[c] = __builtin_fmaf(w, vs[j * DIM + c], p[c]);
+    }
+    int lh[K];        // d2 words
+    uint32_t ll[K];   // original ids
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      lh[i] = i >= first ? (int)INF_BITS : (int)0xff800000u;
+      ll[i] = i >= first ? 0xffffffffu : 0u;
+    }
+
+    // ---- bounding box of the tile (wave-uniform)
+    float tlo[DIM], thi[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      tlo[c] = wave_min_f32(p[c]);
+      thi[c] = wave_max_f32(p[c]);
+    }
+    float M = __builtin_inff();  // largest k-th d2 of the tile (wave-uniform)
+
+    // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound to the tile box, CLOSED past
+    // the end of the level
+    float c_lo[DIM], c_hi[DIM];
+    auto child_bounds = [&](int lvl, int64_t grp) -> float {
+      const float lb = child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
+      return grp * FAN + lane < lv.count[lvl] ? lb : CLOSED;
+    };
+
+    int lvl = top;
+    float lb0 = child_bounds(top, 0);
+    int64_t grp0 = 0;
+    ++n_node_test;
+    if (top > 0) {
+      s_lb[wv][top][lane] = lb0;
+      if (lane == 0) s_grp[wv][top] = 0;
+    }
+    for (;;) {
+      if (lvl > 0) {
+        const float lbv = s_lb[wv][lvl][lane];
+        const bool open = lbv >= 0.f;
+        const float mn = wave_min_f32(open ? lbv : __builtin_inff());
+        if (__ballot(open) == 0ull || mn * SAFE > M) {  // nothing open, or nothing open that holds a key below a k-th
+          if (++lvl > top) break;
+          continue;
+        }
+        const int j = __builtin_ctzll(__ballot(open && lbv == mn));
+        if (lane == j) s_lb[wv][lvl][lane] = CLOSED;  // visited
+        const int64_t c = wave_uniform64(s_grp[wv][lvl]) * FAN + j;
+        --lvl;
+        const float lb = child_bounds(lvl, c);
+        ++n_node_test;
+        if (lvl > 0) {
+          s_lb[wv][lvl][lane] = lb;
+          if (lane == 0) s_grp[wv][lvl] = c;
+        } else {
+          lb0 = lb;
+          grp0 = c;
+        }
+        continue;
+      }
+      // ---- leaf level: nearest open leaf of the current group
+      const bool open = lb0 >= 0.f;
+      const float mn = wave_min_f32(open ? lb0 : __builtin_inff());
+      if (__ballot(open) == 0ull || mn * SAFE > M) {
+        if (++lvl > top) break;
+        continue;
+      }
+      const int j = __builtin_ctzll(__ballot(open && lb0 == mn));
+      if (lane == j) lb0 = CLOSED;  // visited
+      const int64_t c = grp0 * FAN + j;
+      ++n_leaf_test;
+      // can leaf c hold a key below the k-th of any lane?  (its box comes from lane j)
+      float lbp = 0.f;
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const float blo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[a]), j));
+        const float bhi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[a]), j));
+        const float gap = __builtin_fmaxf(__builtin_fmaxf(blo - p[a], p[a] - bhi), 0.f);
+        lbp = __builtin_fmaf(gap, gap, lbp);
+      }
+      if (__ballot(!(lbp * SAFE > __int_as_float(lh[K - 1]))) == 0ull) continue;
+      ++n_leaf_eval;
+      const int64_t row0 = c * (int64_t)LEAF;
+      const float* cp = pts + row0 * DP;
+      constexpr int NB = DP == 8 ? 4 : 8;   // rows (and their ids) in SGPRs at a time
+#pragma unroll 1
+      for (int h = 0; h < LEAF; h += NB) {
+        if (row0 + h >= n_pts) break;   // the rest of the padded last leaf
+        typename RowVec<DP>::type cc[NB];
+        uint32_t id[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          cc[u] = load_uniform_row<DP>(cp + (h + u) * DP);
+          const int64_t rw = row0 + h + u;
+          id[u] = load_uniform_u32(pt_id + (rw < n_pts ? rw : n_pts - 1));
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          if (row0 + h + u < n_pts) {   // (wave-uniform)
+            float d;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) {
+              const float t = p[a] - cc[u][a];
+              d = a == 0 ? t * t : __builtin_fmaf(t, t, d);
+            }
+            // the chain only when some lane's k-th key is above this one (wave vote); a lane where it is not passes
+            // the key through its list unchanged: every slot is below it
+            int ch = __float_as_int(d);
+            uint32_t cl = id[u];
+            if (__ballot(key_less(ch, cl, lh[K - 1], ll[K - 1])) != 0ull) {
+#pragma unroll
+              for (int i = 0; i < K; ++i) {
+                const bool lt = key_less(ch, cl, lh[i], ll[i]);
+                const int nh = lt ? lh[i] : ch;
+                const uint32_t nl = lt ? ll[i] : cl;
+                lh[i] = lt ? ch : lh[i];
+                ll[i] = lt ? cl : ll[i];
+                ch = nh;
+                cl = nl;
+              }
+            }
+          }
+        }
+      }
+      M = wave_max_f32(__int_as_float(lh[K - 1]));
+    }
+
+    if (live) {
+      const int64_t cell = s * (int64_t)R + r;
+      uint32_t* oi = out_ids + cell * k;
+      uint32_t* od = out_d2 ? out_d2 + cell * k : nullptr;
+      bool wide = false;   // rows of k words, k a multiple of 4, in 16-byte aligned buffers: 16-byte stores
+      if constexpr (K >= 4) wide = (k & 3) == 0 && (((uintptr_t)out_ids | (uintptr_t)out_d2) & 15) == 0;
+      if (wide) {
+        if constexpr (K >= 4) {
+#pragma unroll
+          for (int i = 0; i < K; i += 4) {
+            if (i >= first) {   // (first is a multiple of 4 here; the register indices are constants)
+              *reinterpret_cast<v4u*>(oi + (i - first)) = v4u{ll[i], ll[i + 1], ll[i + 2], ll[i + 3]};
+              if (od)
+                *reinterpret_cast<v4u*>(od + (i - first)) =
+                    v4u{(uint32_t)lh[i], (uint32_t)lh[i + 1], (uint32_t)lh[i + 2], (uint32_t)lh[i + 3]};
+            }
+          }
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          if (i >= first) {
+            oi[i - first] = ll[i];
+            if (od) od[i - first] = (uint32_t)lh[i];
+          }
+        }
+      }
+      if (out_bits) {   // the epilogue of sweep_knn_kernel over the hi words
+        float v = __int_as_float(lh[K - 1]);
+        if (stat != 0) {
+          float acc = 0.f;
+#pragma unroll
+          for (int i = 0; i < K; ++i) {
+            if (i == first) acc = __int_as_float(lh[i]);
+            else if (i > first) acc = acc + __int_as_float(lh[i]);
+          }
+          v = acc / (float)k;
+        }
+        out_bits[cell] = __float_as_uint(v);
+      }
+    }
+    const unsigned long long item_tests = n_leaf_test + n_node_test - tests_before;
+    max_item_tests = item_tests > max_item_tests ? item_tests : max_item_tests;
+  }
+  if (stats && lane == 0 && (n_node_test | n_leaf_test) != 0ull) {
+    atomicMax(&stats[3], max_item_tests);
+    atomicAdd(&stats[0], n_leaf_eval);
+    atomicAdd(&stats[1], n_leaf_test);
+    atomicAdd(&stats[2], n_node_test);
+  }
+}
+
+template <int DIM>
+struct KnnIdsOp {
+  static int run(const flooder_knn_ids_t& a, const Levels& lv, hipStream_t st) {
+    if constexpr (DIM < 2) {
+      return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: dim must be in 2..8");
+    } else {
+      const int64_t n_items = (a.n_simplices * (int64_t)a.R + 63) / 64;
+      int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
+      if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+      auto launch = [&](auto kc) {
+        hipLaunchKernelGGL((sweep_knn_ids_kernel<DIM, decltype(kc)::value>), dim3((unsigned)grid), dim3(256), 0, st,
+                           a.pts_sorted, a.n_pts, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat,
+                           a.queue, reinterpret_cast<const uint32_t*>(a.sample_order),
+                           reinterpret_cast<const uint32_t*>(a.order), reinterpret_cast<uint32_t*>(a.out_ids), a.out_d2,
+                           a.out_bits, reinterpret_cast<unsigned long long*>(a.stats));
+      };
+      if (a.k <= 2) launch(std::integral_constant<int, 2>{});
+      else if (a.k <= 4) launch(std::integral_constant<int, 4>{});
+      else if (a.k <= 8) launch(std::integral_constant<int, 8>{});
+      else if (a.k <= 16) launch(std::integral_constant<int, 16>{});
+      else launch(std::integral_constant<int, 32>{});
+      return check_launch("knn_ids_sorted");
+    }
+  }
+};
+
 // the sorted order of a block that has one
 inline const int32_t* order_of(const flooder_knn_sorted_t& a) { return a.sample_order; }
 template <typename Args>
@@ -351,6 +643,27 @@ extern "C" int flooder_sweep_knn_sorted_f32(const flooder_knn_sorted_t* p, void*
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: n_simplices * R must be below 2^32 - 2");
   const Levels lv = make_levels(a.n_pts);
   return dispatch_dim<SweepKnnSortedOp>(a.dim, a, lv, (hipStream_t)stream);
+}
+
+extern "C" int flooder_knn_ids_sorted_f32(const flooder_knn_ids_t* p, void* stream) {
+  flooder_knn_ids_t a;
+  if (int rc = take(p, a, "flooder_knn_ids_sorted_f32: bad parameter block (abi / size)")) return rc;
+  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: k must be in 1..32");
+  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: dim must be in 2..8");
+  if (a.stat != 0 && a.stat != 1)
+    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: stat must be 0 (kth) or 1 (dtm)");
+  if (a.n_pts > 0x7fffffffLL) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: more than 2^31 - 1 points");
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || a.n_pts < a.k || a.k1 < 1 ||
+      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: bad argument (null pointer, fewer points than k, k1, R)");
+  if (!a.sample_order) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: sample_order is NULL");
+  if (!a.order) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: order is NULL");
+  if (!a.out_ids) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: out_ids is NULL");
+  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
+    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: n_simplices * R must be below 2^32 - 2");
+  const Levels lv = make_levels(a.n_pts);
+  return dispatch_dim<KnnIdsOp>(a.dim, a, lv, (hipStream_t)stream);
 }
 
 extern "C" int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream) {

@@ -4,15 +4,19 @@
 evaluates them at the cloud's own points (an outlier score before landmark selection - farthest-point sampling picks
 stray points first) or at any other points (a function on a grid).  ROCm tensors run the k-nearest sweep over sorted
 tiles (``flooder_sweep_knn_sorted_f32`` in its query form: every query is a "simplex" of one vertex with one sample).
+
+``nearest_neighbors`` says WHICH points those k are (``flooder_knn_ids_sorted_f32``: the same sweep keeping (d2 word,
+original id) keys), and with them ``neighbor_distance`` is differentiable in the cloud and in the queries.
 """
 
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native, core
 
@@ -25,6 +29,31 @@ def _check_queries(queries: torch.Tensor, points: torch.Tensor) -> None:
         raise RuntimeError(f"queries.device ({queries.device}) != points.device ({points.device})")
     if queries.dtype != points.dtype:
         raise RuntimeError(f"queries.dtype ({queries.dtype}) != points.dtype ({points.dtype})")
+
+
+def _check_arguments(points, queries, neighbors, neighbor_stat, index) -> Tuple[torch.Tensor, int]:
+    """The argument checks of ``neighbor_distance`` and ``nearest_neighbors`` (one set of refusals, one wording) ->
+    (queries: ``points`` itself for None, neighbors as int)."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0:
+        got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
+        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
+    if points.dtype not in core.SUPPORTED_DTYPES:
+        raise TypeError(f"dtype ({points.dtype}) not supported")
+    if points.device.type not in ("cuda", "cpu"):
+        raise RuntimeError("Device not supported.")
+    on_gpu = points.is_cuda
+    if on_gpu and points.dtype is torch.float64:
+        raise ValueError("neighbor_distance on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
+    if on_gpu and not 2 <= points.shape[1] <= 8:
+        raise ValueError("neighbor_distance on ROCm tensors needs ambient dimension 2 to 8")
+    neighbors, _ = core._check_neighbors(points, neighbors, neighbor_stat, None)
+    if queries is None:
+        queries = points
+    else:
+        _check_queries(queries, points)
+    if index is not None:
+        core._check_index(index, points, on_gpu, "ROCm tensors")
+    return queries, neighbors
 
 
 def neighbor_distance(points: torch.Tensor, queries: Optional[torch.Tensor] = None, neighbors: int = 1,
@@ -46,42 +75,90 @@ def neighbor_distance(points: torch.Tensor, queries: Optional[torch.Tensor] = No
     dimensions (``ValueError`` otherwise: the k-nearest sweep has no float64 kernel); ``index``: a ``PointIndex`` of
     these very points (as for ``flood_complex``), else one is built - or recalled, in ``INDEX_CACHE`` mode.  Only the
     argument checks synchronise with the host.
+
+    Differentiable: when ``points`` or ``queries`` requires grad (and grad mode is on) the result carries a
+    ``grad_fn``.  With f the value and x_(1) .. x_(k) the neighbours of a query q, ``"kth"`` has df/dq =
+    (q - x_(k)) / f and sends the negative to x_(k); ``"dtm"`` has df/dq = sum_i (q - x_(i)) / (k f) and sends
+    -(q - x_(i)) / (k f) to each x_(i); ``squared=True`` has 2 in place of 1 / f; the gradient is 0 where f is 0; with
+    ``queries=None`` both roles accumulate into ``points.grad``.  The neighbours are those of ``nearest_neighbors``
+    (on ROCm tensors one sweep gives them and the values, which are bit for bit those of the call without grad) and
+    the backward on ROCm tensors is bit-identical run to run.  Without grad nothing changes: no ids are computed.
     """
-    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0:
-        got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
-        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
-    if points.dtype not in core.SUPPORTED_DTYPES:
-        raise TypeError(f"dtype ({points.dtype}) not supported")
-    if points.device.type not in ("cuda", "cpu"):
-        raise RuntimeError("Device not supported.")
-    on_gpu = points.is_cuda
-    if on_gpu and points.dtype is torch.float64:
-        raise ValueError("neighbor_distance on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
-    if on_gpu and not 2 <= points.shape[1] <= 8:
-        raise ValueError("neighbor_distance on ROCm tensors needs ambient dimension 2 to 8")
-    neighbors, _ = core._check_neighbors(points, neighbors, neighbor_stat, None)
-    if queries is None:
-        queries = points
-    else:
-        _check_queries(queries, points)
-    if index is not None:
-        core._check_index(index, points, on_gpu, "ROCm tensors")
+    own = queries is None
+    queries, neighbors = _check_arguments(points, queries, neighbors, neighbor_stat, index)
     if queries.shape[0] == 0:
         return torch.empty(0, dtype=points.dtype, device=points.device)
-    if on_gpu:
+    if torch.is_grad_enabled() and (points.requires_grad or queries.requires_grad):
+        return _NeighborDistance.apply(points, None if own else queries, neighbors, neighbor_stat, bool(squared), index)
+    if points.is_cuda:
         return _neighbor_distance_hip(points, queries, neighbors, neighbor_stat, squared, index)
+    dist, _ = _kdtree_query(points, queries, neighbors)
+    return _cpu_statistic(dist, neighbors, neighbor_stat, squared).to(points.dtype)
 
+
+def nearest_neighbors(points: torch.Tensor, queries: Optional[torch.Tensor] = None, neighbors: int = 1, *,
+                      squared: bool = False, index: Optional[core.PointIndex] = None):
+    """The k nearest points of ``points`` per query -> (``ids`` (Q, k) int64: rows of ``points`` in input order,
+    ``dist`` (Q, k) of ``points``' dtype: their distances, squared with ``squared=True``), both ascending by
+    (distance, id) and on the device of ``points``.
+
+    Arguments as ``neighbor_distance`` (same checks, same refusals): k = ``neighbors`` in 1..32, at most the number of
+    points; a point that occurs twice is two ids.  ``queries=None``: the cloud's own points - column 0 is then the
+    point itself, or a copy of it with a smaller id.  Q = 0 gives empty (0, k) tensors.
+
+    ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_knn_ids_sorted_f32``: exact in the sweeps' float32
+    arithmetic, and among points at the same float32 squared distance the smaller id comes first - the k-th place
+    included - the rule of ``flood_filtration``'s witnesses.  ``dist[:, k - 1]`` is ``neighbor_distance(..., "kth")``
+    bit for bit.  Only the argument checks synchronise with the host.
+
+    CPU tensors (float32, float64; any dimension) query scipy's kd-tree: which of several equidistant points sits at
+    the k-th place, and their order among themselves, is scipy's choice.
+    """
+    queries, neighbors = _check_arguments(points, queries, neighbors, "kth", index)
+    Q = queries.shape[0]
+    if Q == 0:
+        return (torch.empty((0, neighbors), dtype=torch.int64, device=points.device),
+                torch.empty((0, neighbors), dtype=points.dtype, device=points.device))
+    if points.is_cuda:
+        ids, d2, _ = _knn_ids_hip(points, queries, neighbors, "kth", index, want_d2=True, want_bits=False)
+        if squared:
+            return ids.long(), d2.view(torch.float32)
+        dist = torch.empty((Q, neighbors), dtype=torch.float32, device=points.device)
+        _native.check(_native.load().flooder_face_values_f32(_native.ptr(d2), Q * neighbors, _native.ptr(dist),
+                                                             _native.current_stream_ptr(points.device)),
+                      "flooder_face_values_f32")
+        return ids.long(), dist
+    dist, ids = _kdtree_query(points, queries, neighbors)
+    if squared:
+        dist = np.square(dist.astype(np.float64))
+    return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)), torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype)
+
+
+def _kdtree_query(points: torch.Tensor, queries: torch.Tensor, k: int):
+    """(dist, ids) of scipy's kd-tree query, both (Q, k), distances ascending (scipy drops the axis at k = 1)."""
     from scipy.spatial import KDTree
 
-    dist, _ = KDTree(np.asarray(points.detach())).query(np.asarray(queries.detach()), k=neighbors,
-                                                         workers=core.CPU_WORKERS)
-    dist = np.asarray(dist).reshape(queries.shape[0], neighbors)     # (Q, k) ascending (scipy drops the axis at k = 1)
+    dist, ids = KDTree(np.asarray(points.detach())).query(np.asarray(queries.detach()), k=k, workers=core.CPU_WORKERS)
+    Q = queries.shape[0]
+    return np.asarray(dist).reshape(Q, k), np.asarray(ids).reshape(Q, k)
+
+
+def _cpu_statistic(dist: np.ndarray, k: int, stat: str, squared: bool) -> torch.Tensor:
     if squared:
         d2 = np.square(dist.astype(np.float64))
-        val = d2[:, -1] if neighbor_stat == "kth" else d2.sum(axis=1) / neighbors
+        val = d2[:, -1] if stat == "kth" else d2.sum(axis=1) / k
     else:
-        val = core._robust_stat(dist, neighbors, neighbor_stat)
-    return torch.as_tensor(np.ascontiguousarray(val)).to(points.dtype)
+        val = core._robust_stat(dist, k, stat)
+    return torch.as_tensor(np.ascontiguousarray(val))
+
+
+def _index_of(points: torch.Tensor, index: Optional[core.PointIndex]) -> core.PointIndex:
+    if index is None:
+        index = core._recall_index(points)
+        if index is None:
+            index = core.PointIndex(points)
+            core._remember_index(points, index)
+    return index
 
 
 def _neighbor_distance_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, squared: bool,
@@ -94,11 +171,7 @@ def _neighbor_distance_hip(points: torch.Tensor, queries: torch.Tensor, k: int, 
     dev = points.device
     torch.cuda.set_device(dev)
     st = _native.current_stream_ptr(dev)
-    if index is None:
-        index = core._recall_index(points)
-        if index is None:
-            index = core.PointIndex(points)
-            core._remember_index(points, index)
+    index = _index_of(points, index)
     q = queries.detach().contiguous()
     Q, dim = q.shape
     one = torch.ones((1, 1), dtype=torch.float32, device=dev)
@@ -114,8 +187,97 @@ def _neighbor_distance_hip(points: torch.Tensor, queries: torch.Tensor, k: int, 
                                 weights=one, R=1, k=k, n_simplices=b - a, stat=core.NEIGHBOR_STATS.index(stat),
                                 queue=queue, out_bits=bits[a:b], sample_order=order)
         _native.check(lib.flooder_sweep_knn_sorted_f32(ctypes.byref(blk), st), "flooder_sweep_knn_sorted_f32")
+    return _root_of_bits(lib, bits, squared, st)
+
+
+def _root_of_bits(lib, bits: torch.Tensor, squared: bool, st) -> torch.Tensor:
     if squared:
         return bits.view(torch.float32)
-    out = torch.empty(Q, dtype=torch.float32, device=dev)
-    _native.check(lib.flooder_face_values_f32(_native.ptr(bits), Q, _native.ptr(out), st), "flooder_face_values_f32")
+    out = torch.empty(bits.shape[0], dtype=torch.float32, device=bits.device)
+    _native.check(lib.flooder_face_values_f32(_native.ptr(bits), bits.shape[0], _native.ptr(out), st),
+                  "flooder_face_values_f32")
     return out
+
+
+def _knn_ids_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
+                 want_d2: bool, want_bits: bool):
+    """``_neighbor_distance_hip``'s stages with ``flooder_knn_ids_sorted_f32`` as the sweep -> (ids (Q, k) int32, the
+    d2 words (Q, k) int32 or None, the words of the squared statistic (Q,) int32 or None).  A group's share of the
+    (Q, k) outputs counts towards ``core.SORTED_WORKSPACE_BYTES`` with the 24 B per query of the sort stage."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    q = queries.detach().contiguous()
+    Q, dim = q.shape
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    ids = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_d2 else None
+    bits = torch.empty(Q, dtype=torch.int32, device=dev) if want_bits else None
+    key_bits = int(lib.flooder_sample_key_bits(dim))
+    per_query = 24 + 4 * k * (2 if want_d2 else 1) + (4 if want_bits else 0)
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)
+        queue, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnIds(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=1, nodes=index.nodes, verts=verts,
+                             weights=one, R=1, k=k, n_simplices=b - a, stat=core.NEIGHBOR_STATS.index(stat),
+                             queue=queue, out_bits=None if bits is None else bits[a:b], sample_order=order,
+                             order=index.order32, out_ids=ids[a:b], out_d2=None if d2 is None else d2[a:b])
+        _native.check(lib.flooder_knn_ids_sorted_f32(ctypes.byref(blk), st), "flooder_knn_ids_sorted_f32")
+    return ids, d2, bits
+
+
+class _NeighborDistance(torch.autograd.Function):
+    """``neighbor_distance`` with its closed-form backward.  ``queries`` None: the cloud's own points (both roles of a
+    point accumulate into the gradient of ``points``)."""
+
+    @staticmethod
+    def forward(ctx, points, queries, k, stat, squared, index):
+        own = queries is None
+        qs = points if own else queries
+        if points.is_cuda:
+            ids, _, bits = _knn_ids_hip(points, qs, k, stat, index, want_d2=False, want_bits=True)
+            value = _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
+            ids = ids.long()
+        else:
+            dist, ids = _kdtree_query(points, qs, k)
+            value = _cpu_statistic(dist, k, stat, squared).to(points.dtype)
+            ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64))
+        ctx.save_for_backward(points, qs, ids, value)
+        ctx.own, ctx.k, ctx.stat, ctx.squared = own, k, stat, squared
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        from .grad import _scatter_rows
+
+        points, qs, ids, value = ctx.saved_tensors
+        own, k, stat, squared = ctx.own, ctx.k, ctx.stat, ctx.squared
+        need_p = ctx.needs_input_grad[0]
+        need_q = own or ctx.needs_input_grad[1]
+        Q, dim = qs.shape
+        dt, dev = points.dtype, points.device
+        if stat == "kth":
+            ids = ids[:, -1:]                                  # x_(k) alone
+        m = ids.shape[1]
+        # coefficient of (q - x_(i)): grad_out * (1 / f, 0 where f == 0; or 2) / (number of terms of the mean)
+        if squared:
+            coef = grad_out * (2.0 / m)
+        else:
+            coef = torch.where(value > 0, grad_out / (value * m), torch.zeros_like(value))
+        contrib = (qs.detach().unsqueeze(1) - points.detach()[ids]) * coef.view(Q, 1, 1)      # (Q, m, dim)
+        grad_q = contrib.sum(dim=1) if need_q else None
+        targets, vals = [], []
+        if need_p:
+            targets.append(ids.reshape(-1))
+            vals.append(-contrib.reshape(Q * m, dim))
+            if own:
+                targets.append(torch.arange(Q, dtype=torch.int64, device=dev))
+                vals.append(grad_q)
+        grad_p = _scatter_rows(targets, vals, points.shape[0], dim, dev, dt) if need_p else None
+        return grad_p, (None if own or not ctx.needs_input_grad[1] else grad_q), None, None, None, None

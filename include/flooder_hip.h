@@ -970,6 +970,52 @@ typedef struct flooder_witness_knn_s {      /* flooder_witness_knn */
 int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream);
 
 /*
+ * flooder_knn_ids_sorted_f32 (csrc/flood_knn.hip; flooder_amd.nearest_neighbors, the backward of neighbor_distance):
+ * flooder_sweep_knn_sorted_f32 keeping KEYS - WHICH points the k nearest of every sample are.  Per cell g = s * R + r
+ * (N = n_simplices * R of them, rows in cell order whatever sample_order says) the k smallest keys (d2 word, original
+ * id = order[row]) over ALL n_pts points, d2 = t0*t0, then fma(t, t, d2) as every sweep, are written ascending:
+ * out_ids[g, 0..k) and, unless NULL, out_d2[g, 0..k).  This is flooder_witness_knn's rule and its output word for word
+ * (ids as int32 here): a point that occurs twice is two ids, among equidistant points the smaller id comes first, rows
+ * of the padded last leaf are no candidates and order is never read there.  Unless NULL, out_bits[g] receives the word
+ * flooder_sweep_knn_sorted_f32 writes for `stat`, formed from the k d2 words by the same arithmetic (stat 0: the last
+ * word; stat 1: ascending sequential float32 sum / (float)k).  Every output word is written once, by plain stores (16
+ * bytes at a time when k is a multiple of 4 and out_ids / out_d2 are 16-byte aligned); no atomics.
+ * One query per lane over tiles of 64 consecutive entries of sample_order, the list in K (d2 word, id) register pairs, K
+ * as flooder_sweep_knn_f32.  Ties decide which ids are reported, so unlike the value sweeps every cull is STRICT: a node,
+ * a leaf or a point is skipped only when its lower bound (times the safety margin) is strictly above the k-th d2 it is
+ * compared with - every point skipped has a larger d2 and so a larger key whatever its id, and keys being distinct the k
+ * smallest are one set, independent of the tree and of the order of traversal.  Visited children carry a mark of their
+ * own, not a bound of +inf, so the walk ends (each step closes a child or leaves a level) even at k == n_pts, where no
+ * list is full before the tree is exhausted and nothing is ever culled.
+ * Query form as flooder_sweep_knn_sorted_f32 (k1 = 1, R = 1, weights = {1.0f}, verts = the queries).
+ * Refused (FLOODER_E_ARG) as flooder_sweep_knn_sorted_f32 refuses (out_bits may be NULL here), and: order NULL, out_ids
+ * NULL, n_pts > 2^31 - 1.  n_simplices == 0 or R == 0: FLOODER_OK, no pointer is looked at.
+ */
+typedef struct flooder_knn_ids_s {          /* flooder_knn_ids_sorted_f32 */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) */
+  int32_t R;
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_MAX */
+  int64_t n_simplices;
+  int32_t stat;               /* 0 = kth, 1 = dtm: the statistic of out_bits */
+  int32_t reserved;
+  int32_t* queue;
+  uint32_t* out_bits;         /* (n_simplices, R); may be NULL */
+  uint64_t* stats;            /* may be NULL */
+  const int32_t* sample_order;  /* N = n_simplices * R entries, as flooder_sorted_sweep_t's */
+  const int32_t* order;       /* PointIndex.order32: tree row -> original id */
+  int32_t* out_ids;           /* (N, k) */
+  uint32_t* out_d2;           /* (N, k); may be NULL */
+} flooder_knn_ids_t;
+int flooder_knn_ids_sorted_f32(const flooder_knn_ids_t* p, void* stream);
+
+/*
  * flooder_knn_merge_f32 (csrc/flood_knn_merge.hip; flood_complex(neighbor_reduce_hook=...), the robust filtration over
  * point shards): the exact k-best merge.  lists holds, for each of n_cells = S * R cells, n_lists ascending lists of k
  * float32 bit patterns - (n_lists, k, n_cells) int32, cell index contiguous: list w is the (k, S, R) plane buffer that
