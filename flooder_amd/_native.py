@@ -91,20 +91,18 @@ class KnnSweep(_Block):
 
 
 class KnnSorted(_Block):
-    """``flooder_knn_sorted_t``: the k-nearest sweep over tiles of 64 consecutive entries of a sample order (the robust
-    dimension pass above 3-D; ``neighbor_distance`` in its query form k1 = R = 1)."""
+    """``flooder_knn_sorted_t``, ``flooder_knn_sweep_t`` and a tail: the k-nearest sweep over tiles of 64 consecutive
+    entries of a sample order (the robust dimension pass above 3-D; ``neighbor_distance`` in its query form k1 = R = 1)."""
 
-    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
-        i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats; p sample_order""")
+    _fields_ = KnnSweep._fields_ + _fields("p sample_order")
 
 
 class KnnIds(_Block):
-    """``flooder_knn_ids_t``: the sweep over sorted tiles keeping (d2 word, original id) keys - which points the k
-    nearest of every sample are (``nearest_neighbors``, the backward of ``neighbor_distance``)."""
+    """``flooder_knn_ids_t``, ``flooder_knn_sorted_t`` and a tail (the library serves the three blocks as one, the longest):
+    the sweep over sorted tiles keeping (d2 word, original id) keys - which points the k nearest of every sample are
+    (``nearest_neighbors``, the backward of ``neighbor_distance``)."""
 
-    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
-        i32 k; i64 n_simplices; i32 stat; i32 reserved; p queue; p out_bits; p stats; p sample_order; p order; p out_ids;
-        p out_d2""")
+    _fields_ = KnnSorted._fields_ + _fields("p order; p out_ids; p out_d2")
 
 
 KNN_COLS_MAX = 64  # FLOODER_KNN_COLS_MAX: every (k, stat) pair with k <= 32 and two statistics

@@ -1499,6 +1499,26 @@ def knn_sorts_samples(dim: int, S: int, R: int) -> bool:
     return bool(KNN_SORTED_SAMPLES) and BVH_SORTED_MIN_SAMPLES <= S * R < (1 << 32) - 2 and S * R * 20 <= SORTED_WORKSPACE_BYTES
 
 
+def _knn_block_fields(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor) -> dict:
+    """The cloud and lattice fields of every k-nearest block; ``verts`` (S, k1, dim) float32, ``weights`` (R, k1)."""
+    return dict(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=verts.shape[1], nodes=index.nodes, verts=verts,
+                weights=weights, R=weights.shape[0], n_simplices=verts.shape[0])
+
+
+def _knn_profile_groups(index: PointIndex, verts: torch.Tensor, w_perm: torch.Tensor, columns, n_planes: int,
+                        bytes_per_simplex: int, workspace_bytes: int, stats: Optional[torch.Tensor] = None):
+    """Groups of consecutive simplices, ``bytes_per_simplex`` of workspace each, within ``workspace_bytes`` -> per group
+    (a, b, ``KnnProfile`` block of ``columns`` over rows a .. b - 1, its (n_planes, b - a, R) int32 plane buffer)."""
+    S, R, dev = verts.shape[0], w_perm.shape[0], index.pts.device
+    per_group = max(1, min(S, int(workspace_bytes) // max(1, bytes_per_simplex)))
+    for a in range(0, S, per_group):
+        b = min(S, a + per_group)
+        queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
+        planes = torch.empty((n_planes, b - a, R), dtype=torch.int32, device=dev)
+        yield a, b, _native.KnnProfile(columns, queue=queue, out_bits=planes, stats=stats,
+                                       **_knn_block_fields(index, verts[a:b], w_perm)), planes
+
+
 def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                          k: int, stat: str, plan: Optional["SamplePlan"] = None,
                          stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None, keep=None):
@@ -1513,15 +1533,13 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
-    S, k1, _ = verts.shape
-    R = weights.shape[0]
+    S, R = verts.shape[0], weights.shape[0]
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
     sorted_samples = knn_sorts_samples(index.dim, S, R)
     queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)   # sharded work-queue heads
     d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    args = dict(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes, verts=verts,
-                weights=plan.w_perm, R=R, k=int(k), n_simplices=S, stat=NEIGHBOR_STATS.index(stat), queue=queue,
+    args = dict(_knn_block_fields(index, verts, plan.w_perm), k=int(k), stat=NEIGHBOR_STATS.index(stat), queue=queue,
                 out_bits=d2, stats=stats)
     with _span(timer, "sweep"):
         if sorted_samples:
@@ -1552,23 +1570,14 @@ def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
-    S, k1, _ = verts.shape
-    R = weights.shape[0]
+    S, R = verts.shape[0], weights.shape[0]
     columns = [(int(k), NEIGHBOR_STATS.index(stat)) for k, stat in columns]
     n_cols = len(columns)
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
-    F = faces.n_faces
-    out_faces = [torch.empty((S, F), dtype=torch.float32, device=dev) for _ in range(n_cols)]
-    per_group = max(1, min(S, int(PROFILE_WORKSPACE_BYTES) // max(1, 4 * n_cols * R)))
-    for a in range(0, S, per_group):
-        b = min(S, a + per_group)
-        queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
-        planes = torch.empty((n_cols, b - a, R), dtype=torch.int32, device=dev)
-        v_g = verts[a:b]
-        blk = _native.KnnProfile(columns, pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=k1, nodes=index.nodes,
-                                 verts=v_g, weights=plan.w_perm, R=R, n_simplices=b - a, queue=queue, out_bits=planes,
-                                 stats=stats)
+    out_faces = [torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev) for _ in range(n_cols)]
+    for a, b, blk, planes in _knn_profile_groups(index, verts, plan.w_perm, columns, n_cols, 4 * n_cols * R,
+                                                 PROFILE_WORKSPACE_BYTES, stats):
         with _span(timer, "sweep"):
             _native.check(lib.flooder_sweep_knn_profile_f32(ctypes.byref(blk), st), "flooder_sweep_knn_profile_f32")
         with _span(timer, "face_max"):
@@ -1595,26 +1604,18 @@ def _sweep_dimension_knn_sharded(index: PointIndex, verts: torch.Tensor, weights
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
-    S, k1, _ = verts.shape
-    R = weights.shape[0]
+    S, R = verts.shape[0], weights.shape[0]
     k = int(k)
     k_local = min(k, int(index.n))
     world = max(1, int(getattr(hook, "world_size", 1)))
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
-    F = faces.n_faces
-    out_face = torch.empty((S, F), dtype=torch.float32, device=dev)
-    per_group = max(1, min(S, int(KNN_MERGE_WORKSPACE_BYTES) // max(1, 4 * k * R * (world + 1))))
-    for a in range(0, S, per_group):
-        b = min(S, a + per_group)
-        queue = torch.zeros(QUEUE_WORDS, dtype=torch.int32, device=dev)   # sharded work-queue heads
-        lists = torch.empty((k, b - a, R), dtype=torch.int32, device=dev)
+    out_face = torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev)
+    for a, b, blk, lists in _knn_profile_groups(index, verts, plan.w_perm, [(t, 0) for t in range(1, k_local + 1)], k,
+                                                4 * k * R * (world + 1), KNN_MERGE_WORKSPACE_BYTES):
         if k_local < k:   # a shard with fewer than k points: its lists end in +inf words
             _native.check(lib.flooder_fill_u32(_native.ptr(lists[k_local:]), (k - k_local) * (b - a) * R, INF_BITS,
                                                st), "flooder_fill_u32")
-        blk = _native.KnnProfile([(t, 0) for t in range(1, k_local + 1)], pts_sorted=index.pts, n_pts=index.n,
-                                 dim=index.dim, k1=k1, nodes=index.nodes, verts=verts[a:b], weights=plan.w_perm, R=R,
-                                 n_simplices=b - a, queue=queue, out_bits=lists, stats=None)
         with _span(timer, "sweep"):
             _native.check(lib.flooder_sweep_knn_profile_f32(ctypes.byref(blk), st), "flooder_sweep_knn_profile_f32")
         with _span(timer, "gather"):

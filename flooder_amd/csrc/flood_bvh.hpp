@@ -45,8 +45,12 @@ inline int64_t total_nodes(const Levels& lv) {
 // registers or spills, or that cost it time, was not kept (profiles/tree_helpers_isa.txt): such a site carries the
 // arithmetic written out under a comment that names the helper.  Not shared at all, and to be kept in step by hand: the
 // sample as an fmaf chain over the vertices (grep "__builtin_fmaf(w"), the 16-row leaf loop (flood_bvh.hip,
-// flood_finish.hip, flood_sorted.hip, flood_cell.hip), the frontier walk of the four sweeps and the stack walk of the
-// two witness kernels.  The double sweep of flood_f64.hip shares no rounding with any of this.
+// flood_finish.hip, flood_sorted.hip, flood_cell.hip), the frontier walk of the six sweeps (sweep_knn_ids_kernel's is a
+// copy of sweep_knn_kernel's with strict culls) and the stack walk of the two witness kernels.  For those two k-nearest
+// kernels one shared body under an IDS template flag was tried at compile level, in two wordings: it moved the
+// registers of nearly every instantiation of flood_knn.hip, those of the untouched value path included.  No such build
+// has been timed, so the copy stands (the note above sweep_knn_ids_kernel has the figures).  The double sweep of
+// flood_f64.hip shares no rounding with any of this.
 
 // Culling margin: a box, a leaf or a level is skipped only when !(lb * SAFE < bound).  lb is a float32 LOWER bound
 // of a squared distance whose rounding error is a few ulp; 1e-5 relative is far above that, so a cull never removes a

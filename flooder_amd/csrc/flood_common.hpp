@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/flooder_hip.h"
 
 namespace flooder {
@@ -21,6 +23,8 @@ constexpr uint32_t INF_BITS = 0x7f800000u;
 int launch_simplex_planes(int dim, const float* verts, int k1, int64_t n_simplices, float* tab, hipStream_t st);
 char* err_buf();
 int fail(int code, const char* msg);
+// fail with a formatted message (internal: the library's list of exported symbols stays what it was)
+int failf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3), visibility("hidden")));
 int check_launch(const char* what);
 
 __host__ __device__ constexpr int padded_dim(int dim) { return dim <= 2 ? 2 : (dim <= 4 ? 4 : 8); }
@@ -388,6 +392,30 @@ int take(const T* p, T& out, const char* who) {
   if (p->abi != FLOODER_PARAMS_ABI || p->size < 2 * sizeof(uint32_t) || p->size > sizeof(T)) return fail(FLOODER_E_ARG, who);
   memset(&out, 0, sizeof(T));
   memcpy(&out, p, p->size);
+  return 0;
+}
+
+// ---- the k-nearest family (flood_knn.hip, flood_knn_merge.hip, flooder_witness_knn in flood_grad.hip), host side.
+// A lane keeps its k best in K registers, K = k rounded up to 2, 4, 8, 16 or 32, one kernel instantiation each:
+// f(std::integral_constant<int, K>{}) for the K that holds k.
+template <class F>
+void with_knn_slots(int k, F&& f) {
+  if (k <= 2) f(std::integral_constant<int, 2>{});
+  else if (k <= 4) f(std::integral_constant<int, 4>{});
+  else if (k <= 8) f(std::integral_constant<int, 8>{});
+  else if (k <= 16) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, 32>{});
+}
+
+// The range checks the entries share, in the order each of them makes them: k, dim, stat, then fewer points than k
+// (`needs_k_points`: flooder_witness_knn - the sweeps report that with their pointer check, behind "nothing to do") and
+// more points than 32-bit ids hold (`ids`: the entries that report ids).  `who`, the entry's name, opens every message.
+inline int knn_check_ranges(const char* who, int k, int dim, int stat, int64_t n_pts, bool needs_k_points, bool ids) {
+  if (k < 1 || k > FLOODER_KNN_MAX) return failf(FLOODER_E_ARG, "%s: k must be in 1..32", who);
+  if (dim < 2 || dim > FLOODER_MAX_DIM) return failf(FLOODER_E_ARG, "%s: dim must be in 2..8", who);
+  if (stat != 0 && stat != 1) return failf(FLOODER_E_ARG, "%s: stat must be 0 (kth) or 1 (dtm)", who);
+  if (needs_k_points && n_pts < k) return failf(FLOODER_E_ARG, "%s: fewer points than k", who);
+  if (ids && n_pts > 0x7fffffffLL) return failf(FLOODER_E_ARG, "%s: more than 2^31 - 1 points", who);
   return 0;
 }
 

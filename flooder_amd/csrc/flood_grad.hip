@@ -396,11 +396,7 @@ int flooder_witness_search(const flooder_witness_search_t* p, void* stream) {
 int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream) {
   flooder_witness_knn_t a;
   if (int rc = take(p, a, "flooder_witness_knn: bad parameter block (abi / size)")) return rc;
-  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_witness_knn: k must be in 1..32");
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
-  if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_witness_knn: stat must be 0 (kth) or 1 (dtm)");
-  if (a.n_pts < a.k) return fail(FLOODER_E_ARG, "flooder_witness_knn: fewer points than k");
-  if (a.n_pts > 0x7fffffffLL) return fail(FLOODER_E_ARG, "flooder_witness_knn: more than 2^31 - 1 points");
+  if (int rc = knn_check_ranges("flooder_witness_knn", a.k, a.dim, a.stat, a.n_pts, true, true)) return rc;
   if (a.n_queries == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.order || !a.verts || !a.weights || !a.q_simplex || !a.q_row || !a.q_stat ||
       !a.out_ids || !a.not_found || a.k1 < 1 || a.R < 1 || a.n_queries < 0)

@@ -21,6 +21,7 @@
 // Work is pulled from device-side queues (atomic head) so heavy-tailed candidate counts balance.
 
 #include <limits.h>
+#include <stdarg.h>
 
 #include "flood_common.hpp"
 
@@ -31,6 +32,14 @@ char* err_buf() { return g_err; }
 
 int fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
+  return code;
+}
+
+int failf(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
   return code;
 }
 

@@ -48,8 +48,6 @@
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
 
-#include <type_traits>
-
 using namespace flooder;
 
 namespace {
@@ -262,7 +260,11 @@ __global__ __launch_bounds__(256) void sweep_knn_kernel(
 // ---------------------------------------------------------------------------------------------- neighbour ids
 // flooder_knn_ids_sorted_f32: the sweep over sorted tiles keeping KEYS (d2 word, original id) instead of d2 words - WHICH
 // points the k nearest are, under the tie rule of flooder_witness_knn (flood_grad.hip).  A sibling of sweep_knn_kernel,
-// not a flag of it: the value sweeps keep their code.  The walk is the one above (keep in step); what differs:
+// not a flag of it: the value sweeps keep their code.  The walk is the one above (keep in step); what differs is listed
+// below.  One shared body (a __forceinline__ function with an IDS template flag under two thin kernels, the culls behind
+// lambdas or the value path kept token for token under `if constexpr`) was tried at compile level: it moved the
+// registers of 138 to 140 of the file's 142 kernel symbols, the value kernels' included (<7, 4, false, false>: 58 -> 72
+// VGPRs; the parent's table is profiles/knn_ids_kernel_resources.txt).  Nobody has timed such a build, so the copy stands.
 //
 //   the list   K (hi, lo) register pairs per lane, hi the d2 word compared as a signed int as above, lo the id compared
 //              unsigned.  The K - k front slots hold (-inf, 0), the
@@ -521,178 +523,140 @@ __global__ __launch_bounds__(256) void sweep_knn_ids_kernel(
   }
 }
 
-template <int DIM>
-struct KnnIdsOp {
-  static int run(const flooder_knn_ids_t& a, const Levels& lv, hipStream_t st) {
-    if constexpr (DIM < 2) {
-      return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: dim must be in 2..8");
-    } else {
-      const int64_t n_items = (a.n_simplices * (int64_t)a.R + 63) / 64;
-      int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
-      if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
-      auto launch = [&](auto kc) {
-        hipLaunchKernelGGL((sweep_knn_ids_kernel<DIM, decltype(kc)::value>), dim3((unsigned)grid), dim3(256), 0, st,
-                           a.pts_sorted, a.n_pts, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat,
-                           a.queue, reinterpret_cast<const uint32_t*>(a.sample_order),
-                           reinterpret_cast<const uint32_t*>(a.order), reinterpret_cast<uint32_t*>(a.out_ids), a.out_d2,
-                           a.out_bits, reinterpret_cast<unsigned long long*>(a.stats));
-      };
-      if (a.k <= 2) launch(std::integral_constant<int, 2>{});
-      else if (a.k <= 4) launch(std::integral_constant<int, 4>{});
-      else if (a.k <= 8) launch(std::integral_constant<int, 8>{});
-      else if (a.k <= 16) launch(std::integral_constant<int, 16>{});
-      else launch(std::integral_constant<int, 32>{});
-      return check_launch("knn_ids_sorted");
-    }
-  }
-};
+// ---- host side: one block, one set of checks, one launch.
+// flooder_knn_sweep_t is a prefix of flooder_knn_sorted_t and that one of flooder_knn_ids_t - same names, types and
+// offsets, stated below.  Every entry takes ITS block by its own size rule and lays it over a zeroed flooder_knn_ids_t:
+// the fields its block does not have read as NULL, as `take` reads the tail of a short block.  knn_sweep<FORM> makes the
+// checks of the form in the entry's order and holds the launch.
+#define FLOODER_KNN_SWEEP_FIELDS(X)                                                                                  \
+  X(size) X(abi) X(pts_sorted) X(n_pts) X(dim) X(k1) X(nodes) X(verts) X(weights) X(R) X(k) X(n_simplices) X(stat) \
+  X(reserved) X(queue) X(out_bits) X(stats)
+template <typename Short, typename Long>
+constexpr bool knn_sweep_fields_match() {
+#define X(f) && offsetof(Short, f) == offsetof(Long, f) && std::is_same<decltype(Short::f), decltype(Long::f)>::value
+  return true FLOODER_KNN_SWEEP_FIELDS(X);
+#undef X
+}
+static_assert(knn_sweep_fields_match<flooder_knn_sweep_t, flooder_knn_sorted_t>() &&
+                  sizeof(flooder_knn_sweep_t) == offsetof(flooder_knn_sorted_t, sample_order),
+              "flooder_knn_sweep_t must be a prefix of flooder_knn_sorted_t");
+static_assert(knn_sweep_fields_match<flooder_knn_sorted_t, flooder_knn_ids_t>() &&
+                  offsetof(flooder_knn_sorted_t, sample_order) == offsetof(flooder_knn_ids_t, sample_order) &&
+                  sizeof(flooder_knn_sorted_t) == offsetof(flooder_knn_ids_t, order),
+              "flooder_knn_sorted_t must be a prefix of flooder_knn_ids_t");
 
-// the sorted order of a block that has one
-inline const int32_t* order_of(const flooder_knn_sorted_t& a) { return a.sample_order; }
-template <typename Args>
-inline const int32_t* order_of(const Args&) { return nullptr; }
-
-// The launch of sweep_knn_kernel<DIM, K, PROFILE, SORTED> at K = the smallest of 2, 4, 8, 16, 32 that holds k; SORTED
-// for the block that carries a sample order.
-// (the tree sweeps exist for one ambient dimension as well; the k-nearest sweep is defined for 2 .. 8: `who_dim`)
-template <int DIM, bool PROFILE, typename Args>
-int launch_sweep_knn(const Args& a, int k, int stat, const KnnProfileCols& cols, const Levels& lv, hipStream_t st,
-                     const char* what, const char* who_dim) {
-  if constexpr (DIM < 2) {
-    return fail(FLOODER_E_ARG, who_dim);
-  } else {
-    constexpr bool SORTED = std::is_same<Args, flooder_knn_sorted_t>::value;
-    const int64_t n_items = SORTED ? (a.n_simplices * (int64_t)a.R + 63) / 64 : a.n_simplices * ((a.R + 63) / 64);
-    int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
-    if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
-    auto launch = [&](auto kc) {
-      hipLaunchKernelGGL((sweep_knn_kernel<DIM, decltype(kc)::value, PROFILE, SORTED>), dim3((unsigned)grid), dim3(256), 0, st,
-                         a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, k, stat, a.queue,
-                         a.out_bits, reinterpret_cast<unsigned long long*>(a.stats), cols,
-                         reinterpret_cast<const uint32_t*>(order_of(a)));
-    };
-    if (k <= 2) launch(std::integral_constant<int, 2>{});
-    else if (k <= 4) launch(std::integral_constant<int, 4>{});
-    else if (k <= 8) launch(std::integral_constant<int, 8>{});
-    else if (k <= 16) launch(std::integral_constant<int, 16>{});
-    else launch(std::integral_constant<int, 32>{});
-    return check_launch(what);
-  }
+template <typename Block>
+flooder_knn_ids_t widened(const Block& a) {
+  flooder_knn_ids_t w;
+  memset(&w, 0, sizeof(w));
+  memcpy(&w, &a, sizeof(a));
+  return w;
 }
 
-template <int DIM>
-struct SweepKnnOp {
-  static int run(const flooder_knn_sweep_t& a, const Levels& lv, hipStream_t st) {
-    return launch_sweep_knn<DIM, false>(a, a.k, a.stat, KnnProfileCols{}, lv, st, "sweep_knn",
-                                        "flooder_sweep_knn_f32: dim must be in 2..8");
-  }
+// per-simplex tiles / tiles of the sorted order / sorted tiles keeping ids / per-simplex tiles, a plane per column
+enum class KnnForm { simplex, sorted, ids, profile };
+
+// The launch at K = the smallest of 2, 4, 8, 16, 32 that holds k: sweep_knn_ids_kernel for the ids form, else
+// sweep_knn_kernel<DIM, K, PROFILE, SORTED>.  (the tree sweeps exist for one ambient dimension as well; the k-nearest
+// sweep is defined for 2 .. 8 and knn_sweep has refused the rest)
+template <KnnForm FORM>
+struct KnnLaunch {
+  template <int DIM>
+  struct Op {
+    static int run(const flooder_knn_ids_t& a, const KnnProfileCols& cols, const Levels& lv, const char* what,
+                   hipStream_t st) {
+      if constexpr (DIM < 2) {
+        return fail(FLOODER_E_ARG, "dim must be in 2..8");
+      } else {
+        constexpr bool SORTED = FORM == KnnForm::sorted || FORM == KnnForm::ids;
+        const int64_t n_items = SORTED ? (a.n_simplices * (int64_t)a.R + 63) / 64 : a.n_simplices * ((a.R + 63) / 64);
+        int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
+        if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+        auto* stats = reinterpret_cast<unsigned long long*>(a.stats);
+        auto* order = reinterpret_cast<const uint32_t*>(a.sample_order);
+        with_knn_slots(a.k, [&](auto kc) {
+          constexpr int K = decltype(kc)::value;
+          if constexpr (FORM == KnnForm::ids)
+            hipLaunchKernelGGL((sweep_knn_ids_kernel<DIM, K>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted,
+                               a.n_pts, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices, a.k, a.stat, a.queue,
+                               order, reinterpret_cast<const uint32_t*>(a.order), reinterpret_cast<uint32_t*>(a.out_ids),
+                               a.out_d2, a.out_bits, stats);
+          else
+            hipLaunchKernelGGL((sweep_knn_kernel<DIM, K, FORM == KnnForm::profile, SORTED>), dim3((unsigned)grid),
+                               dim3(256), 0, st, a.pts_sorted, a.nodes, lv, a.verts, a.weights, a.k1, a.R, a.n_simplices,
+                               a.k, a.stat, a.queue, a.out_bits, stats, cols, order);
+        });
+        return check_launch(what);
+      }
+    }
+  };
 };
 
-template <int DIM>
-struct SweepKnnSortedOp {
-  static int run(const flooder_knn_sorted_t& a, const Levels& lv, hipStream_t st) {
-    return launch_sweep_knn<DIM, false>(a, a.k, a.stat, KnnProfileCols{}, lv, st, "sweep_knn_sorted",
-                                        "flooder_sweep_knn_sorted_f32: dim must be in 2..8");
+// `who`: the entry's name, in front of every message; `what`: the launch's name for check_launch.  The profile form comes
+// with k = the largest k of its columns and stat 0 (both in range by construction).
+template <KnnForm FORM>
+int knn_sweep(const flooder_knn_ids_t& a, const KnnProfileCols& cols, const char* who, const char* what, void* stream) {
+  constexpr bool IDS = FORM == KnnForm::ids, PROFILE = FORM == KnnForm::profile;
+  if (int rc = knn_check_ranges(who, a.k, a.dim, a.stat, a.n_pts, false, IDS)) return rc;
+  if (PROFILE && a.n_pts < a.k) return failf(FLOODER_E_ARG, "%s: fewer points than the largest k", who);
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || (!a.out_bits && !IDS) || a.n_pts < a.k ||
+      a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return failf(FLOODER_E_ARG, PROFILE ? "%s: bad argument (null pointer, k1, R)"
+                                        : "%s: bad argument (null pointer, fewer points than k, k1, R)", who);
+  if constexpr (FORM == KnnForm::sorted || IDS) {
+    if (!a.sample_order) return failf(FLOODER_E_ARG, "%s: sample_order is NULL", who);
+    if (IDS && !a.order) return failf(FLOODER_E_ARG, "%s: order is NULL", who);
+    if (IDS && !a.out_ids) return failf(FLOODER_E_ARG, "%s: out_ids is NULL", who);
+    if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
+      return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
   }
-};
-
-struct KnnProfileLaunch {   // the checked block and what the host derives from it
-  flooder_knn_profile_t a;
-  int k_max;
-  KnnProfileCols cols;
-};
-
-template <int DIM>
-struct SweepKnnProfileOp {
-  static int run(const KnnProfileLaunch& p, const Levels& lv, hipStream_t st) {
-    return launch_sweep_knn<DIM, true>(p.a, p.k_max, 0, p.cols, lv, st, "sweep_knn_profile",
-                                       "flooder_sweep_knn_profile_f32: dim must be in 2..8");
-  }
-};
+  return dispatch_dim<KnnLaunch<FORM>::template Op>(a.dim, a, cols, make_levels(a.n_pts), what, (hipStream_t)stream);
+}
 
 }  // namespace
 
 extern "C" int flooder_sweep_knn_f32(const flooder_knn_sweep_t* p, void* stream) {
   flooder_knn_sweep_t a;
   if (int rc = take(p, a, "flooder_sweep_knn_f32: bad parameter block (abi / size)")) return rc;
-  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: k must be in 1..32");
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: dim must be in 2..8");
-  if (a.stat != 0 && a.stat != 1) return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: stat must be 0 (kth) or 1 (dtm)");
-  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
-  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.n_pts < a.k || a.k1 < 1 ||
-      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_f32: bad argument (null pointer, fewer points than k, k1, R)");
-  const Levels lv = make_levels(a.n_pts);
-  return dispatch_dim<SweepKnnOp>(a.dim, a, lv, (hipStream_t)stream);
+  return knn_sweep<KnnForm::simplex>(widened(a), KnnProfileCols{}, "flooder_sweep_knn_f32", "sweep_knn", stream);
 }
 
 extern "C" int flooder_sweep_knn_sorted_f32(const flooder_knn_sorted_t* p, void* stream) {
   flooder_knn_sorted_t a;
   if (int rc = take(p, a, "flooder_sweep_knn_sorted_f32: bad parameter block (abi / size)")) return rc;
-  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: k must be in 1..32");
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: dim must be in 2..8");
-  if (a.stat != 0 && a.stat != 1)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: stat must be 0 (kth) or 1 (dtm)");
-  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
-  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.n_pts < a.k || a.k1 < 1 ||
-      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: bad argument (null pointer, fewer points than k, k1, R)");
-  if (!a.sample_order) return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: sample_order is NULL");
-  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_sorted_f32: n_simplices * R must be below 2^32 - 2");
-  const Levels lv = make_levels(a.n_pts);
-  return dispatch_dim<SweepKnnSortedOp>(a.dim, a, lv, (hipStream_t)stream);
+  return knn_sweep<KnnForm::sorted>(widened(a), KnnProfileCols{}, "flooder_sweep_knn_sorted_f32", "sweep_knn_sorted",
+                                    stream);
 }
 
 extern "C" int flooder_knn_ids_sorted_f32(const flooder_knn_ids_t* p, void* stream) {
   flooder_knn_ids_t a;
   if (int rc = take(p, a, "flooder_knn_ids_sorted_f32: bad parameter block (abi / size)")) return rc;
-  if (a.k < 1 || a.k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: k must be in 1..32");
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: dim must be in 2..8");
-  if (a.stat != 0 && a.stat != 1)
-    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: stat must be 0 (kth) or 1 (dtm)");
-  if (a.n_pts > 0x7fffffffLL) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: more than 2^31 - 1 points");
-  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
-  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || a.n_pts < a.k || a.k1 < 1 ||
-      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
-    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: bad argument (null pointer, fewer points than k, k1, R)");
-  if (!a.sample_order) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: sample_order is NULL");
-  if (!a.order) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: order is NULL");
-  if (!a.out_ids) return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: out_ids is NULL");
-  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
-    return fail(FLOODER_E_ARG, "flooder_knn_ids_sorted_f32: n_simplices * R must be below 2^32 - 2");
-  const Levels lv = make_levels(a.n_pts);
-  return dispatch_dim<KnnIdsOp>(a.dim, a, lv, (hipStream_t)stream);
+  return knn_sweep<KnnForm::ids>(a, KnnProfileCols{}, "flooder_knn_ids_sorted_f32", "knn_ids_sorted", stream);
 }
 
 extern "C" int flooder_sweep_knn_profile_f32(const flooder_knn_profile_t* p, void* stream) {
-  KnnProfileLaunch L;
-  flooder_knn_profile_t& a = L.a;
+  flooder_knn_profile_t a;
   if (int rc = take(p, a, "flooder_sweep_knn_profile_f32: bad parameter block (abi / size)")) return rc;
   if (a.n_cols < 1 || a.n_cols > FLOODER_KNN_COLS_MAX)
     return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: n_cols must be in 1..64");
+  KnnProfileCols cols;
   for (int s = 0; s < 2; ++s)
-    for (int t = 0; t < FLOODER_KNN_MAX; ++t) L.cols.col_of[s][t] = -1;
-  L.k_max = 0;
+    for (int t = 0; t < FLOODER_KNN_MAX; ++t) cols.col_of[s][t] = -1;
+  flooder_knn_ids_t w;   // the sweep at k = the largest k of the columns
+  memset(&w, 0, sizeof(w));
   for (int c = 0; c < a.n_cols; ++c) {
     const int k = a.col_k[c], s = a.col_stat[c];
     if (k < 1 || k > FLOODER_KNN_MAX) return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: col_k must be in 1..32");
     if (s != 0 && s != 1)
       return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: col_stat must be 0 (kth) or 1 (dtm)");
-    if (L.cols.col_of[s][k - 1] >= 0)
+    if (cols.col_of[s][k - 1] >= 0)
       return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: a (k, stat) column is listed twice");
-    L.cols.col_of[s][k - 1] = c;
-    if (k > L.k_max) L.k_max = k;
+    cols.col_of[s][k - 1] = c;
+    if (k > w.k) w.k = k;
   }
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: dim must be in 2..8");
-  if (a.n_pts < L.k_max)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: fewer points than the largest k");
-  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
-  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || a.k1 < 1 ||
-      a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
-    return fail(FLOODER_E_ARG, "flooder_sweep_knn_profile_f32: bad argument (null pointer, k1, R)");
-  const Levels lv = make_levels(a.n_pts);
-  return dispatch_dim<SweepKnnProfileOp>(a.dim, L, lv, (hipStream_t)stream);
+  w.pts_sorted = a.pts_sorted, w.n_pts = a.n_pts, w.dim = a.dim, w.k1 = a.k1, w.nodes = a.nodes, w.verts = a.verts;
+  w.weights = a.weights, w.R = a.R, w.n_simplices = a.n_simplices, w.queue = a.queue, w.out_bits = a.out_bits;
+  w.stats = a.stats;
+  return knn_sweep<KnnForm::profile>(w, cols, "flooder_sweep_knn_profile_f32", "sweep_knn_profile", stream);
 }

@@ -90,15 +90,9 @@ extern "C" int flooder_knn_merge_f32(const flooder_knn_merge_t* p, void* stream)
   if (!a.lists || !a.out_bits || a.n_cells > 0xffffff00LL)   // (a launch holds fewer than 2^32 threads)
     return fail(FLOODER_E_ARG, "flooder_knn_merge_f32: bad argument (null pointer, more than 2^32 - 256 cells)");
   const int64_t blocks = (a.n_cells + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
-#define FLOODER_LAUNCH_KNN_MERGE(K_)                                                                                 \
-  hipLaunchKernelGGL((knn_merge_kernel<K_>), dim3((unsigned)blocks), dim3(256), 0, st, a.lists, a.n_lists, a.k, a.stat, \
-                     a.n_cells, a.out_bits)
-  if (a.k <= 2) FLOODER_LAUNCH_KNN_MERGE(2);
-  else if (a.k <= 4) FLOODER_LAUNCH_KNN_MERGE(4);
-  else if (a.k <= 8) FLOODER_LAUNCH_KNN_MERGE(8);
-  else if (a.k <= 16) FLOODER_LAUNCH_KNN_MERGE(16);
-  else FLOODER_LAUNCH_KNN_MERGE(32);
-#undef FLOODER_LAUNCH_KNN_MERGE
+  with_knn_slots(a.k, [&](auto kc) {
+    hipLaunchKernelGGL((knn_merge_kernel<decltype(kc)::value>), dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, a.lists, a.n_lists, a.k, a.stat, a.n_cells, a.out_bits);
+  });
   return check_launch("knn_merge");
 }

@@ -91,7 +91,8 @@ def neighbor_distance(points: torch.Tensor, queries: Optional[torch.Tensor] = No
     if torch.is_grad_enabled() and (points.requires_grad or queries.requires_grad):
         return _NeighborDistance.apply(points, None if own else queries, neighbors, neighbor_stat, bool(squared), index)
     if points.is_cuda:
-        return _neighbor_distance_hip(points, queries, neighbors, neighbor_stat, squared, index)
+        _, _, bits = _query_sweep_hip(points, queries, neighbors, neighbor_stat, index, False, False, True)
+        return _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
     dist, _ = _kdtree_query(points, queries, neighbors)
     return _cpu_statistic(dist, neighbors, neighbor_stat, squared).to(points.dtype)
 
@@ -161,12 +162,14 @@ def _index_of(points: torch.Tensor, index: Optional[core.PointIndex]) -> core.Po
     return index
 
 
-def _neighbor_distance_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, squared: bool,
-                           index: Optional[core.PointIndex]) -> torch.Tensor:
+def _query_sweep_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
+                     want_ids: bool, want_d2: bool, want_bits: bool):
     """Keys of the queries inside the cloud's box (queries outside it get clamped keys: order only) -> radix sort ->
-    ``flooder_sweep_knn_sorted_f32`` with k1 = R = 1 (fma(1.0f, q, 0.0f) is q) -> square root by
-    ``flooder_face_values_f32``, the root of the dimension pass's face epilogue.  Groups of queries keep the keys, the
-    orders and the sort's scratch (24 B per query) within ``core.SORTED_WORKSPACE_BYTES``."""
+    the k-nearest sweep over sorted tiles in its query form, k1 = R = 1 (fma(1.0f, q, 0.0f) is q):
+    ``flooder_sweep_knn_sorted_f32``, or with ``want_ids`` ``flooder_knn_ids_sorted_f32`` -> (ids (Q, k) int32 or None,
+    their d2 words (Q, k) int32 or None, the words of the squared statistic (Q,) int32 or None).  Groups of queries keep
+    the keys, the orders and the sort's scratch (24 B per query) and, in the ids form, their share of its outputs within
+    ``core.SORTED_WORKSPACE_BYTES``."""
     lib = _native.load()
     dev = points.device
     torch.cuda.set_device(dev)
@@ -175,19 +178,32 @@ def _neighbor_distance_hip(points: torch.Tensor, queries: torch.Tensor, k: int, 
     q = queries.detach().contiguous()
     Q, dim = q.shape
     one = torch.ones((1, 1), dtype=torch.float32, device=dev)
-    bits = torch.empty(Q, dtype=torch.int32, device=dev)
+    ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids else None
+    d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids and want_d2 else None
+    bits = torch.empty(Q, dtype=torch.int32, device=dev) if want_bits else None
     key_bits = int(lib.flooder_sample_key_bits(dim))
-    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // 24, (1 << 32) - 3))
+    per_query = 24 + ((4 * k * (2 if want_d2 else 1) + (4 if want_bits else 0)) if want_ids else 0)
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
+    entry, block = (("flooder_knn_ids_sorted_f32", _native.KnnIds) if want_ids
+                    else ("flooder_sweep_knn_sorted_f32", _native.KnnSorted))
     for a in range(0, Q, per_group):
         b = min(Q, a + per_group)
         verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
         queue, sort_state = core._zeroed_queue(lib, dev, b - a)
         order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
-        blk = _native.KnnSorted(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=1, nodes=index.nodes, verts=verts,
-                                weights=one, R=1, k=k, n_simplices=b - a, stat=core.NEIGHBOR_STATS.index(stat),
-                                queue=queue, out_bits=bits[a:b], sample_order=order)
-        _native.check(lib.flooder_sweep_knn_sorted_f32(ctypes.byref(blk), st), "flooder_sweep_knn_sorted_f32")
-    return _root_of_bits(lib, bits, squared, st)
+        outs = dict(out_bits=None if bits is None else bits[a:b])
+        if want_ids:
+            outs.update(order=index.order32, out_ids=ids[a:b], out_d2=None if d2 is None else d2[a:b])
+        blk = block(k=k, stat=core.NEIGHBOR_STATS.index(stat), queue=queue, sample_order=order, **outs,
+                    **core._knn_block_fields(index, verts, one))
+        _native.check(getattr(lib, entry)(ctypes.byref(blk), st), entry)
+    return ids, d2, bits
+
+
+def _knn_ids_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
+                 want_d2: bool, want_bits: bool):
+    """The ids form of ``_query_sweep_hip``: what ``nearest_neighbors`` and a forward with grad run."""
+    return _query_sweep_hip(points, queries, k, stat, index, True, want_d2, want_bits)
 
 
 def _root_of_bits(lib, bits: torch.Tensor, squared: bool, st) -> torch.Tensor:
@@ -197,38 +213,6 @@ def _root_of_bits(lib, bits: torch.Tensor, squared: bool, st) -> torch.Tensor:
     _native.check(lib.flooder_face_values_f32(_native.ptr(bits), bits.shape[0], _native.ptr(out), st),
                   "flooder_face_values_f32")
     return out
-
-
-def _knn_ids_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
-                 want_d2: bool, want_bits: bool):
-    """``_neighbor_distance_hip``'s stages with ``flooder_knn_ids_sorted_f32`` as the sweep -> (ids (Q, k) int32, the
-    d2 words (Q, k) int32 or None, the words of the squared statistic (Q,) int32 or None).  A group's share of the
-    (Q, k) outputs counts towards ``core.SORTED_WORKSPACE_BYTES`` with the 24 B per query of the sort stage."""
-    lib = _native.load()
-    dev = points.device
-    torch.cuda.set_device(dev)
-    st = _native.current_stream_ptr(dev)
-    index = _index_of(points, index)
-    q = queries.detach().contiguous()
-    Q, dim = q.shape
-    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
-    ids = torch.empty((Q, k), dtype=torch.int32, device=dev)
-    d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_d2 else None
-    bits = torch.empty(Q, dtype=torch.int32, device=dev) if want_bits else None
-    key_bits = int(lib.flooder_sample_key_bits(dim))
-    per_query = 24 + 4 * k * (2 if want_d2 else 1) + (4 if want_bits else 0)
-    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
-    for a in range(0, Q, per_group):
-        b = min(Q, a + per_group)
-        verts = q[a:b].unsqueeze(1)
-        queue, sort_state = core._zeroed_queue(lib, dev, b - a)
-        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
-        blk = _native.KnnIds(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=1, nodes=index.nodes, verts=verts,
-                             weights=one, R=1, k=k, n_simplices=b - a, stat=core.NEIGHBOR_STATS.index(stat),
-                             queue=queue, out_bits=None if bits is None else bits[a:b], sample_order=order,
-                             order=index.order32, out_ids=ids[a:b], out_d2=None if d2 is None else d2[a:b])
-        _native.check(lib.flooder_knn_ids_sorted_f32(ctypes.byref(blk), st), "flooder_knn_ids_sorted_f32")
-    return ids, d2, bits
 
 
 class _NeighborDistance(torch.autograd.Function):
