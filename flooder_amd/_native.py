@@ -143,6 +143,14 @@ class KnnMerge(_Block):
         p out_bits""")
 
 
+class KnnWide(_Block):
+    """``flooder_knn_wide_t``: the k nearest points of every cell for k up to 1024, one wave per cell, the list in LDS
+    (``flood_complex(neighbor_mass=m)``, ``distance_to_measure``)."""
+
+    _fields_ = _fields("""u32 size; u32 abi; p pts_sorted; i64 n_pts; i32 dim; i32 k1; p nodes; p verts; p weights; i32 R;
+        i32 k; i64 n_simplices; i32 stat; i32 reserved; p order; p sample_order; p out_bits; p out_ids; p out_d2""")
+
+
 # The control words of the fused sweep (include/flooder_hip.h, FLOODER_<name>: int32 word offsets into finish_ctl,
 # defer_ctl and the queue areas); tests/test_host.py compiles the header and compares
 QUEUE_WORDS = 512
@@ -261,6 +269,8 @@ SIGNATURES = {
     "flooder_witness_knn": (c_int, [ctypes.POINTER(WitnessKnn), c_void_p]),
     # ... and the k best of the union of the point shards' k best (flood_complex(neighbor_reduce_hook=...))
     "flooder_knn_merge_f32": (c_int, [ctypes.POINTER(KnnMerge), c_void_p]),
+    # ... and the k nearest for k up to 1024, one wave per cell (flood_complex(neighbor_mass=m), distance_to_measure)
+    "flooder_knn_wide_f32": (c_int, [ctypes.POINTER(KnnWide), c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

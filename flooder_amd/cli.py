@@ -9,7 +9,8 @@ Mirrors the reference's console script (``flooder/cli.py``: options :185-297, st
 Differences, all on the device side: ``cuda:N`` means ROCm device N and is accepted only when it is a gfx950
 (MI355X) whose HIP library loads - the reference's compute-capability gate (:313-317) has no meaning here;
 ``--no-triton`` is accepted and ignored (there is one device path); ``--neighbors K`` / ``--neighbor-stat`` (not in
-the reference) select the robust filtration of ``flood_complex(neighbors=K, neighbor_stat=...)``; the tables are plain text (``rich`` is not a
+the reference) select the robust filtration of ``flood_complex(neighbors=K, neighbor_stat=...)``, ``--neighbor-mass M`` the one by mass
+(``neighbor_mass=M``: up to 1024 neighbours); the tables are plain text (``rich`` is not a
 dependency).  Persistence comes from gudhi when it is importable and from the package's own Z/2 reduction
 otherwise (``flooder_amd/simplex_tree.py``).
 """
@@ -64,6 +65,7 @@ class RunMeta:
     ambient_dim: int
     neighbors: int = 1              # the robust filtration's k and statistic (1 / "kth": the plain filtration)
     neighbor_stat: str = "kth"
+    neighbor_mass: Optional[float] = None   # ... or the share of the cloud that fixes k (--neighbor-mass)
 
 
 class StepTimer:
@@ -155,6 +157,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--neighbors", metavar="K", type=int, default=1,
                    help="Robust filtration: the K nearest points of every sample instead of the nearest "
                         "(1..32; default: %(default)s, the plain filtration)")
+    g.add_argument("--neighbor-mass", metavar="M", type=float, default=None,
+                   help="Robust filtration by mass: K = ceil(M * number of points) nearest points of every sample, up to "
+                        "1024 (0 < M <= 1; not together with --neighbors; default: off)")
     g.add_argument("--neighbor-stat", choices=("kth", "dtm"), default="kth",
                    help="Statistic of the K nearest: kth (K-distance) or dtm (distance to the empirical measure) "
                         "(default: %(default)s)")
@@ -255,7 +260,10 @@ def dump_stats_json(steps: Sequence[StepStats], out_path: Optional[str]) -> None
 def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import flood_complex
 
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.neighbor_mass is not None and args.neighbors != 1:
+        parser.error("--neighbor-mass cannot be combined with --neighbors: the mass fixes the number of neighbours")
     if args.verbose:
         print(vars(args))
     device = validate_device(args.device)
@@ -277,7 +285,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                               batch_size=args.batch_size, fps_h=args.fps_height,
                               use_triton=use_triton if device.type == "cuda" else None,
                               return_simplex_tree=True, num_rand=num_rand, neighbors=args.neighbors,
-                              neighbor_stat=args.neighbor_stat)
+                              neighbor_stat=args.neighbor_stat, neighbor_mass=args.neighbor_mass)
     steps.append(t.stats)
     print(f"Building Flood complex with {stree.num_simplices()} simplices done")
 
@@ -292,7 +300,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                        max_dimension=max_dim, fps_height=args.fps_height, batch_size=args.batch_size,
                        device=str(device), points_per_edge=points_per_edge, num_rand=num_rand,
                        seed=args.seed if num_rand is not None else None, use_triton=use_triton,
-                       n_points=n_pts, ambient_dim=dim, neighbors=args.neighbors, neighbor_stat=args.neighbor_stat)
+                       n_points=n_pts, ambient_dim=dim, neighbors=args.neighbors, neighbor_stat=args.neighbor_stat,
+                       neighbor_mass=args.neighbor_mass)
         save_output(Path(args.output_file), diagrams, meta)
 
     print(format_stats_table(steps))

@@ -31,10 +31,11 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import math
 import os
 import weakref
 import warnings
-from numbers import Integral
+from numbers import Integral, Real
 from typing import Callable, Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
@@ -1485,6 +1486,60 @@ def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, red
     return neighbors, method
 
 
+# Most neighbours per sample of the robust filtration BY MASS (``flood_complex(neighbor_mass=m)``,
+# ``distance_to_measure``; FLOODER_KNN_WIDE_MAX): above ``KNN_MAX`` a wave of csrc/flood_knn_wide.hip keeps the k best of
+# one sample in LDS, 8 KB at 1024.  ``KNN_MAX`` and the register family are what they were.
+KNN_WIDE_MAX = 1024
+
+
+def mass_neighbors(mass, n: int) -> int:
+    """The number of neighbours that the share ``mass`` of ``n`` points is: max(1, ceil(mass * n - 1e-6)) - the k of
+    the distance to a measure at mass m = k / n (the slack keeps 0.1 * 30 at 3).  ``mass``: a real number in (0, 1]."""
+    if isinstance(mass, bool) or not isinstance(mass, Real):
+        raise TypeError(f"mass must be a real number in (0, 1], got {mass!r}")
+    mass = float(mass)
+    if not 0.0 < mass <= 1.0:
+        raise ValueError(f"mass must be in (0, 1] (a share of the cloud), got {mass!r}")
+    return max(1, int(math.ceil(mass * int(n) - 1e-6)))
+
+
+def _check_neighbor_mass(points: torch.Tensor, neighbor_mass, neighbors, method, reduce_hook=None, shard_blocks=False,
+                         neighbor_reduce_hook=None):
+    """``flood_complex(neighbor_mass=m)`` as it is judged before any work is done -> k = ``mass_neighbors(m, N)``.  Up
+    to ``KNN_MAX`` the call then IS ``flood_complex(neighbors=k)`` (``_check_neighbors`` judges the rest); above it the
+    refusals of the wide sweep are made here."""
+    if not (isinstance(neighbors, Integral) and not isinstance(neighbors, bool) and int(neighbors) == 1):
+        raise ValueError(f"neighbor_mass cannot be combined with neighbors={neighbors!r}: the mass fixes the number of "
+                         "neighbours (leave neighbors at 1)")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0:
+        got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
+        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
+    n = points.shape[0]
+    k = mass_neighbors(neighbor_mass, n)
+    if reduce_hook is not None or neighbor_reduce_hook is not None:
+        raise ValueError("neighbor_mass cannot be combined with reduce_hook or neighbor_reduce_hook: a mass is a share "
+                         "of the WHOLE cloud, and a shard of the points does not know how many there are (pass "
+                         "neighbors=k to the sharded call)")
+    if shard_blocks:
+        raise ValueError("neighbor_mass cannot be combined with shard_blocks=True: a mass is a share of the WHOLE "
+                         "cloud, and a block's sub-cloud holds only the points inside its simplices' bounding balls")
+    if k > KNN_WIDE_MAX:
+        raise ValueError(f"neighbor_mass={float(neighbor_mass)!r} is {k} neighbours of {n} points, above KNN_WIDE_MAX = "
+                         f"{KNN_WIDE_MAX} (the k best of a sample live in the LDS of one wave): the largest mass that "
+                         f"fits this cloud is {KNN_WIDE_MAX / n:.6g}")
+    if k > n:
+        raise ValueError(f"neighbor_mass={float(neighbor_mass)!r} is {k} neighbours, which exceeds the number of points ({n})")
+    if k > KNN_MAX:
+        if method in ("cell", "ball"):
+            raise ValueError(f"neighbor_mass needs the tree sweep: method {method!r} evaluates the nearest point only "
+                             "(use method=None, 'auto' or 'bvh')")
+        if points.is_cuda and points.dtype is torch.float64:
+            raise ValueError("neighbor_mass on ROCm tensors needs float32: the wide k-nearest sweep has no float64 kernel")
+        if points.is_cuda and not 2 <= points.shape[1] <= 8:
+            raise ValueError("neighbor_mass on ROCm tensors needs ambient dimension 2 to 8")
+    return k
+
+
 # The k-nearest sweep over tiles of the sorted sample order (``flooder_sweep_knn_sorted_f32``) instead of one simplex per
 # tile: None = where ``bvh_sorts_samples`` says so (above 3 dimensions), True / False = always / never (within the sorted
 # sweeps' limits).  A Python constant for A/B runs and tests, the twin of ``BVH_SORTED_SAMPLES``; the values do not
@@ -1554,6 +1609,27 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     if keep is not None:
         keep(d2)
     return out_face, None
+
+
+def _sweep_dimension_knn_wide(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                              k: int, stat: str, plan: Optional["SamplePlan"] = None,
+                              timer: Optional[_KernelTimer] = None):
+    """``_sweep_dimension_knn`` for ``KNN_MAX`` < k <= ``KNN_WIDE_MAX``: one ``flooder_knn_wide_f32`` launch (a wave per
+    sample, its k best in LDS) writes the SQUARED statistic's bits into the same (S, R) buffer, samples in the order of
+    ``plan.w_perm`` -> face max + sqrt.  Cell order (consecutive waves take consecutive samples of a simplex, which are
+    neighbours in space); no host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, R = verts.shape[0], weights.shape[0]
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
+    blk = _native.KnnWide(k=int(k), stat=NEIGHBOR_STATS.index(stat), out_bits=d2,
+                          **_knn_block_fields(index, verts, plan.w_perm))
+    with _span(timer, "sweep"):
+        _native.check(lib.flooder_knn_wide_f32(ctypes.byref(blk), st), "flooder_knn_wide_f32")
+    return _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer)
 
 
 def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
@@ -2079,6 +2155,7 @@ def flood_complex(
     neighbors: int = 1,
     neighbor_stat: str = "kth",
     neighbor_reduce_hook: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
+    neighbor_mass: Optional[float] = None,
 ):
     """Flood complex of ``points`` over the Delaunay triangulation of ``landmarks``.
 
@@ -2149,10 +2226,35 @@ def flood_complex(
     ``KNN_MERGE_WORKSPACE_BYTES``.  Refused with ``neighbors=1`` (``reduce_hook`` is the tool), together with
     ``reduce_hook`` or ``shard_blocks=True``, on CPU and float64 tensors and with ``method`` ``"cell"`` / ``"ball"``;
     every rank must pass the same ``sort_axis``; ``simplex_shard`` without blocks composes with it.
+
+    ``neighbor_mass=m`` (keyword-only): the robust filtration BY MASS - k = ``mass_neighbors(m, N)`` =
+    max(1, ceil(m * N - 1e-6)) neighbours, the parametrisation of the distance to a measure (``neighbor_stat="dtm"``;
+    ``"kth"`` is the k-distance at that k).  ``neighbors`` must be left at 1.  Up to k = ``KNN_MAX`` the call is
+    ``flood_complex(neighbors=k, neighbor_stat=...)`` itself.  Above it, up to ``KNN_WIDE_MAX`` (1024): CPU tensors
+    query the kd-tree with ``k``; ROCm float32 tensors in 2 to 8 dimensions run ``flooder_knn_wide_f32`` (one wave per
+    sample, its k best in LDS; exact, the tie rules of the k <= 32 sweeps), where ``"dtm"`` adds the k squared distances
+    in the strided order stated in ``include/flooder_hip.h`` (within 78 * 2^-24 relative of the exact mean).  Refused:
+    a mass that is more than ``KNN_WIDE_MAX`` neighbours, ``method`` ``"cell"`` / ``"ball"``, ROCm float64 tensors, and
+    ``reduce_hook``, ``neighbor_reduce_hook`` and ``shard_blocks=True`` (a mass is a share of the whole cloud, which a
+    shard does not know); ``simplex_shard`` works.
     """
     # ---- the robust filtration's arguments, before any work is done
+    wide_k = None
+    if neighbor_mass is not None:
+        k_mass = _check_neighbor_mass(points, neighbor_mass, neighbors, method, reduce_hook, shard_blocks,
+                                      neighbor_reduce_hook)
+        if k_mass <= KNN_MAX:
+            neighbors = k_mass            # the call with neighbors=k, from here on
+        else:
+            wide_k = k_mass
+            if neighbor_stat not in NEIGHBOR_STATS:
+                raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
+            if method is None or method == "auto":
+                method = "bvh"
     neighbors, method = _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks,
                                          neighbor_reduce_hook)
+    if wide_k is not None:
+        neighbors = wide_k                # (above KNN_MAX: the wide sweep on ROCm tensors, the kd-tree on CPU tensors)
     if use_triton is None:
         use_triton = HAS_HIP_KERNELS
     if use_triton and not _has_hip_kernels():
@@ -2303,6 +2405,8 @@ def flood_complex(
         elif on_gpu and neighbors > 1 and neighbor_reduce_hook is not None:
             face_dev, _ = _sweep_dimension_knn_sharded(index, sv, weights, faces, neighbors, neighbor_stat,
                                                        neighbor_reduce_hook, plan=plan)
+        elif on_gpu and neighbors > KNN_MAX:
+            face_dev, _ = _sweep_dimension_knn_wide(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu and neighbors > 1:
             face_dev, _ = _sweep_dimension_knn(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu:

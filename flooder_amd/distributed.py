@@ -190,13 +190,21 @@ def flood_complex_sharded(points: torch.Tensor, landmarks: torch.Tensor, *args, 
     together must hold k (one small all-reduce sums their sizes, and every rank raises ``flood_complex``'s "neighbors
     exceeds the number of points" otherwise).  On CPU tensors and ROCm float64 tensors ``mode="points"`` with k > 1
     raises ``flood_complex``'s refusal of ``reduce_hook`` as before, and ``mode="blocks"`` its refusal of
-    ``shard_blocks`` (a block's bounding balls bound the nearest point only)."""
+    ``shard_blocks`` (a block's bounding balls bound the nearest point only).
+
+    ``neighbor_mass`` (the robust filtration by mass, up to 1024 neighbours) is forwarded by ``mode="simplices"``;
+    ``mode="points"`` and ``mode="blocks"`` refuse it: a mass is a share of the whole cloud, which a shard does not
+    know."""
     if not isinstance(landmarks, torch.Tensor):
         raise TypeError("flood_complex_sharded needs explicit landmark coordinates (identical on every "
                         "rank); run generate_landmarks on the full cloud first")
     num_rand = kwargs.get("num_rand", args[2] if len(args) > 2 else None)
     if num_rand is not None:
         sync_cpu_rng(points.device, group, always=always_reduce)
+    if kwargs.get("neighbor_mass") is not None and mode in ("points", "blocks"):
+        raise ValueError(f"neighbor_mass cannot be combined with mode={mode!r}: a mass is a share of the WHOLE cloud, and "
+                         "a shard of the points (a block's sub-cloud) does not know how many there are - use "
+                         "mode='simplices', or pass neighbors=k")
     if mode == "points":
         axis = global_widest_axis(points, group, always_reduce)
         k = kwargs.get("neighbors", 1)

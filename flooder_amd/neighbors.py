@@ -7,11 +7,15 @@ tiles (``flooder_sweep_knn_sorted_f32`` in its query form: every query is a "sim
 
 ``nearest_neighbors`` says WHICH points those k are (``flooder_knn_ids_sorted_f32``: the same sweep keeping (d2 word,
 original id) keys), and with them ``neighbor_distance`` is differentiable in the cloud and in the queries.
+
+``distance_to_measure`` speaks in MASS (k = mass * N, up to 1024 neighbours): ``flooder_knn_wide_f32``, one wave per query
+with its k best in LDS, values and neighbours without gradients.
 """
 
 from __future__ import annotations
 
 import ctypes
+from numbers import Integral
 from typing import Optional, Tuple
 
 import numpy as np
@@ -31,9 +35,8 @@ def _check_queries(queries: torch.Tensor, points: torch.Tensor) -> None:
         raise RuntimeError(f"queries.dtype ({queries.dtype}) != points.dtype ({points.dtype})")
 
 
-def _check_arguments(points, queries, neighbors, neighbor_stat, index) -> Tuple[torch.Tensor, int]:
-    """The argument checks of ``neighbor_distance`` and ``nearest_neighbors`` (one set of refusals, one wording) ->
-    (queries: ``points`` itself for None, neighbors as int)."""
+def _check_points(points, who: str) -> bool:
+    """``points`` as every function here takes it -> on a ROCm device?  ``who`` names the function in the refusals."""
     if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0:
         got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
         raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
@@ -43,17 +46,29 @@ def _check_arguments(points, queries, neighbors, neighbor_stat, index) -> Tuple[
         raise RuntimeError("Device not supported.")
     on_gpu = points.is_cuda
     if on_gpu and points.dtype is torch.float64:
-        raise ValueError("neighbor_distance on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
+        raise ValueError(f"{who} on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
     if on_gpu and not 2 <= points.shape[1] <= 8:
-        raise ValueError("neighbor_distance on ROCm tensors needs ambient dimension 2 to 8")
-    neighbors, _ = core._check_neighbors(points, neighbors, neighbor_stat, None)
+        raise ValueError(f"{who} on ROCm tensors needs ambient dimension 2 to 8")
+    return on_gpu
+
+
+def _check_queries_and_index(points, queries, index, on_gpu: bool) -> torch.Tensor:
+    """-> queries (``points`` itself for None)."""
     if queries is None:
         queries = points
     else:
         _check_queries(queries, points)
     if index is not None:
         core._check_index(index, points, on_gpu, "ROCm tensors")
-    return queries, neighbors
+    return queries
+
+
+def _check_arguments(points, queries, neighbors, neighbor_stat, index) -> Tuple[torch.Tensor, int]:
+    """The argument checks of ``neighbor_distance`` and ``nearest_neighbors`` (one set of refusals, one wording) ->
+    (queries: ``points`` itself for None, neighbors as int)."""
+    on_gpu = _check_points(points, "neighbor_distance")
+    neighbors, _ = core._check_neighbors(points, neighbors, neighbor_stat, None)
+    return _check_queries_and_index(points, queries, index, on_gpu), neighbors
 
 
 def neighbor_distance(points: torch.Tensor, queries: Optional[torch.Tensor] = None, neighbors: int = 1,
@@ -135,6 +150,79 @@ def nearest_neighbors(points: torch.Tensor, queries: Optional[torch.Tensor] = No
     return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)), torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype)
 
 
+def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = None, mass: Optional[float] = None, *,
+                        neighbors: Optional[int] = None, neighbor_stat: str = "dtm", squared: bool = False,
+                        return_neighbors: bool = False, index: Optional[core.PointIndex] = None):
+    """Per query the distance to the empirical measure of ``points`` at mass ``mass`` -> (Q,) tensor of ``points``'
+    dtype on its device.
+
+    The literature's parametrisation (gudhi's ``DistanceToMeasure``): with k = ``core.mass_neighbors(mass, N)`` =
+    max(1, ceil(mass * N - 1e-6)) the value is sqrt(mean of d_(1)^2 .. d_(k)^2) (``neighbor_stat="dtm"``) or the
+    k-distance d_(k) (``"kth"``); a point that occurs twice counts twice.  Exactly one of ``mass`` (a real number in
+    (0, 1]) and ``neighbors`` (k itself, 1..``core.KNN_WIDE_MAX`` = 1024, at most the number of points) is given.
+    ``squared=True`` returns the statistic before the root.  ``return_neighbors=True`` returns ``(value, ids (Q, k)
+    int64, dist (Q, k))``: the k nearest points per query, ascending by (distance, id), ``dist`` squared with
+    ``squared=True``.  ``queries`` (None: the cloud's own points), ``index`` and the checks on them are those of
+    ``neighbor_distance``; Q = 0 gives empty results.
+
+    ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_knn_wide_f32`` - one wave per query, its k best in LDS -
+    for every k: exact in the sweeps' float32 arithmetic, among points at the same float32 squared distance the smaller
+    id first.  Up to k = 32 values and neighbours are those of ``neighbor_distance`` and ``nearest_neighbors`` bit for
+    bit; above 64 ``"dtm"`` adds the k squared distances in the strided order stated in ``include/flooder_hip.h``
+    (within 78 * 2^-24 relative of the exact mean).  ``flood_complex(..., neighbor_mass=m)`` has these values at its
+    vertices.  CPU tensors (float32, float64; any dimension) query scipy's kd-tree.
+
+    Not differentiable: inputs that require grad are used detached.  ``neighbor_distance`` is, for k <= 32.
+    """
+    on_gpu = _check_points(points, "distance_to_measure")
+    if (mass is None) == (neighbors is None):
+        raise ValueError("distance_to_measure needs exactly one of mass and neighbors")
+    if neighbor_stat not in core.NEIGHBOR_STATS:
+        raise ValueError(f"neighbor_stat must be one of {core.NEIGHBOR_STATS}, got {neighbor_stat!r}")
+    n = points.shape[0]
+    if mass is not None:
+        k = core.mass_neighbors(mass, n)
+        if k > core.KNN_WIDE_MAX:
+            raise ValueError(f"mass={float(mass)!r} is {k} neighbours of {n} points, above KNN_WIDE_MAX = "
+                             f"{core.KNN_WIDE_MAX} (the k best of a query live in the LDS of one wave): the largest "
+                             f"mass that fits this cloud is {core.KNN_WIDE_MAX / n:.6g}")
+    else:
+        if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
+            raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
+        k = int(neighbors)
+        if not 1 <= k <= core.KNN_WIDE_MAX:
+            raise ValueError(f"neighbors must be in 1..{core.KNN_WIDE_MAX} (KNN_WIDE_MAX: the k best of a query live in "
+                             f"the LDS of one wave), got {k}")
+    if k > n:
+        raise ValueError(f"neighbors={k} exceeds the number of points ({n})")
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    points, queries = points.detach(), queries.detach()
+    Q = queries.shape[0]
+    if Q == 0:
+        value = torch.empty(0, dtype=points.dtype, device=points.device)
+        return (value, torch.empty((0, k), dtype=torch.int64, device=points.device),
+                torch.empty((0, k), dtype=points.dtype, device=points.device)) if return_neighbors else value
+    if on_gpu:
+        lib, st = _native.load(), _native.current_stream_ptr(points.device)
+        ids, d2, bits = _wide_query_hip(points, queries, k, neighbor_stat, index, return_neighbors)
+        value = _root_of_bits(lib, bits, squared, st)
+        if not return_neighbors:
+            return value
+        if squared:
+            return value, ids.long(), d2.view(torch.float32)
+        dist = torch.empty((Q, k), dtype=torch.float32, device=points.device)
+        _native.check(lib.flooder_face_values_f32(_native.ptr(d2), Q * k, _native.ptr(dist), st), "flooder_face_values_f32")
+        return value, ids.long(), dist
+    dist, ids = _kdtree_query(points, queries, k)
+    value = _cpu_statistic(dist, k, neighbor_stat, squared).to(points.dtype)
+    if not return_neighbors:
+        return value
+    if squared:
+        dist = np.square(dist.astype(np.float64))
+    return (value, torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)),
+            torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype))
+
+
 def _kdtree_query(points: torch.Tensor, queries: torch.Tensor, k: int):
     """(dist, ids) of scipy's kd-tree query, both (Q, k), distances ascending (scipy drops the axis at k = 1)."""
     from scipy.spatial import KDTree
@@ -197,6 +285,39 @@ def _query_sweep_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: 
         blk = block(k=k, stat=core.NEIGHBOR_STATS.index(stat), queue=queue, sample_order=order, **outs,
                     **core._knn_block_fields(index, verts, one))
         _native.check(getattr(lib, entry)(ctypes.byref(blk), st), entry)
+    return ids, d2, bits
+
+
+def _wide_query_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
+                    want_ids: bool):
+    """``_query_sweep_hip`` with the wide kernel: sample keys -> radix sort -> ``flooder_knn_wide_f32`` in its query
+    form (k1 = R = 1, weights {1.0f}) with the sorted order as ``sample_order`` (queries that follow each other walk
+    the same part of the tree) -> (ids (Q, k) int32 and their d2 words (Q, k) int32, or None, None; the words of the
+    squared statistic (Q,) int32).  Groups of queries keep the keys, the orders and the sort's scratch (24 B per query)
+    and, in the ids form, 8 * k bytes of outputs per query within ``core.SORTED_WORKSPACE_BYTES``."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    q = queries.detach().contiguous()
+    Q, dim = q.shape
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids else None
+    d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids else None
+    bits = torch.empty(Q, dtype=torch.int32, device=dev)
+    key_bits = int(lib.flooder_sample_key_bits(dim))
+    per_query = 24 + 4 + (8 * k if want_ids else 0)
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
+        _, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnWide(k=k, stat=core.NEIGHBOR_STATS.index(stat), sample_order=order, order=index.order32,
+                              out_bits=bits[a:b], out_ids=None if ids is None else ids[a:b],
+                              out_d2=None if d2 is None else d2[a:b], **core._knn_block_fields(index, verts, one))
+        _native.check(lib.flooder_knn_wide_f32(ctypes.byref(blk), st), "flooder_knn_wide_f32")
     return ids, d2, bits
 
 

@@ -1043,6 +1043,64 @@ typedef struct flooder_knn_merge_s {        /* flooder_knn_merge_f32 */
 } flooder_knn_merge_t;
 int flooder_knn_merge_f32(const flooder_knn_merge_t* p, void* stream);
 
+/*
+ * flooder_knn_wide_f32 (csrc/flood_knn_wide.hip; flood_complex(neighbor_mass=m), flooder_amd.distance_to_measure): the k
+ * nearest points of every cell for k up to FLOODER_KNN_WIDE_MAX, one WAVE per cell, the list in LDS - the robust
+ * filtration by mass, where k = mass * n_pts runs into the hundreds.  FLOODER_KNN_MAX and the entries above are
+ * untouched.  Per cell g = s * R + r (N = n_simplices * R of them) the sample p = sum_j weights[r, j] * verts[s, j, :]
+ * (p = 0, then p[c] = fma(w_j, v_j[c], p[c]) in vertex order, as every sweep), d2 = t0*t0, then fma(t, t, d2) per further
+ * axis, and the k smallest keys (d2 word, original id = order[row]) over ALL n_pts points, ascending: the rule of
+ * flooder_witness_knn and flooder_knn_ids_sorted_f32 word for word - a point that occurs twice is two ids, among equal
+ * d2 words the smaller id comes first (the k-th place included), rows of the padded last leaf are no candidates, every
+ * cull is strict (a node or leaf is skipped only when lb * SAFE > the current k-th d2; nothing before the list holds k
+ * keys), and k == n_pts works (nothing is culled, the walk ends with the tree).  Unless NULL:
+ *   out_ids[g, 0..k)   the ids (int32), ascending by key; needs order;
+ *   out_d2[g, 0..k)    their d2 words w_0 <= w_1 <= ... <= w_(k-1);
+ *   out_bits[g]        the float32 bits of the SQUARED statistic of those words:
+ *     stat 0 ("kth")   w_(k-1);
+ *     stat 1 ("dtm")   a sum fixed by the sorted words alone.  With L = min(k, 64): for l = 0 .. L-1 the partial sum
+ *                      S_l = w_l + w_(l+64) + w_(l+128) + ... over the positions < k, added left to right in float32
+ *                      (S_l starts AS w_l, not as 0 + w_l); then T = S_0 + S_1 + ... + S_(L-1), added left to right in
+ *                      float32 (T starts as S_0); the word is T / (float)k, correctly rounded.  For k <= 64 every S_l
+ *                      is w_l and T is the plain ascending sequential sum: at k <= FLOODER_KNN_MAX the word of
+ *                      flooder_sweep_knn_f32 and flooder_knn_ids_sorted_f32, bit for bit.  Above 64 it costs k / 64
+ *                      additions per lane and 64 serial ones instead of k serial ones; its rounding error is at most
+ *                      (ceil(k / 64) - 1 + 63) half-ulps, below 78 * 2^-24 relative on the squared value at k = 1024.
+ * At least one of the three must be given.  sample_order: NULL = cells in the order g = 0 .. N-1, else a permutation of
+ * 0 .. N-1 (as flooder_sweep_knn_sorted_f32 takes it) that decides only WHEN a cell is computed - neighbouring cells
+ * walk the same part of the tree -, never what is written or where; an entry >= N is skipped.  order may be NULL when
+ * out_ids is: equal d2 words are then ordered by tree row, which changes no d2 word and no statistic.
+ * Query form: k1 = 1, R = 1, weights = {1.0f}, verts = (Q, dim) query points; queries must be finite.
+ * No work queue (a grid-stride loop over the cells), no atomics, every output word written once by plain stores.
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a pointer is read: a bad block size or
+ * abi; k outside 1..FLOODER_KNN_WIDE_MAX; dim outside 2..8; stat not 0 or 1; n_pts < k; n_pts > 2^31 - 1;
+ * n_simplices * R >= 2^32 - 2; a cloud too large for the stack encoding (as flooder_witness_knn); all three outputs
+ * NULL; out_ids without order.  Then n_simplices == 0 or R == 0: FLOODER_OK, nothing is touched.
+ */
+#define FLOODER_KNN_WIDE_MAX 1024
+
+typedef struct flooder_knn_wide_s {         /* flooder_knn_wide_f32 */
+  uint32_t size, abi;
+  const float* pts_sorted;    /* PointIndex.pts: (n_pad, DP) rows in tree order */
+  int64_t n_pts;
+  int32_t dim;
+  int32_t k1;                 /* vertices of a swept simplex */
+  const float* nodes;         /* PointIndex.nodes */
+  const float* verts;         /* (n_simplices, k1, dim) */
+  const float* weights;       /* (R, k1) */
+  int32_t R;
+  int32_t k;                  /* neighbours, 1..FLOODER_KNN_WIDE_MAX */
+  int64_t n_simplices;
+  int32_t stat;               /* 0 = kth, 1 = dtm: the statistic of out_bits */
+  int32_t reserved;
+  const int32_t* order;       /* PointIndex.order32: tree row -> original id; may be NULL when out_ids is */
+  const int32_t* sample_order;  /* N = n_simplices * R entries; may be NULL */
+  uint32_t* out_bits;         /* (n_simplices, R); may be NULL */
+  int32_t* out_ids;           /* (N, k); may be NULL */
+  uint32_t* out_d2;           /* (N, k); may be NULL */
+} flooder_knn_wide_t;
+int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
