@@ -1435,6 +1435,42 @@ KNN_MAX = 32
 NEIGHBOR_STATS = ("kth", "dtm")
 
 
+# The refusals that exist in two wordings, for a count (``neighbors`` > 1) and for a mass above ``KNN_MAX``: each sentence
+# once, and what the two wordings put into it.
+_ROBUST_REFUSALS = dict(
+    method="{subject} needs the tree sweep: method {method!r} evaluates the nearest point only (use method=None, 'auto' "
+           "or 'bvh')",
+    shard_blocks="{subject} cannot be combined with shard_blocks=True: {blocks}",
+    float64="{subject} on ROCm tensors needs float32: the {sweep} has no float64 kernel",
+    dimension="{subject} on ROCm tensors needs ambient dimension 2 to 8")
+_ROBUST_WORDING = {
+    False: dict(subject="neighbors > 1", sweep="k-nearest sweep",
+                blocks="a block's sub-cloud holds the points inside its simplices' bounding balls, which bound the "
+                       "nearest point only"),
+    True: dict(subject="neighbor_mass", sweep="wide k-nearest sweep",
+               blocks="a mass is a share of the WHOLE cloud, and a block's sub-cloud holds only the points inside its "
+                      "simplices' bounding balls")}
+
+
+def _robust_refusal(which: str, by_mass: bool, **words) -> ValueError:
+    return ValueError(_ROBUST_REFUSALS[which].format(**_ROBUST_WORDING[by_mass], **words))
+
+
+def _check_knn_tensor(points: torch.Tensor, method, by_mass: bool) -> None:
+    """What a k-nearest sweep (k > 1) asks of ``method`` and of a ROCm tensor."""
+    if method in ("cell", "ball"):
+        raise _robust_refusal("method", by_mass, method=method)
+    if points.is_cuda and points.dtype is torch.float64:
+        raise _robust_refusal("float64", by_mass)
+    if points.is_cuda and points.dim() == 2 and not 2 <= points.shape[1] <= 8:
+        raise _robust_refusal("dimension", by_mass)
+
+
+def _check_neighbor_stat(neighbor_stat) -> None:
+    if neighbor_stat not in NEIGHBOR_STATS:
+        raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
+
+
 def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, reduce_hook=None, shard_blocks=False,
                      neighbor_reduce_hook=None):
     """The robust filtration's arguments as ``flood_complex`` and ``flood_filtration`` judge them, before any work is
@@ -1447,8 +1483,7 @@ def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, red
     if not 1 <= neighbors <= KNN_MAX:
         raise ValueError(f"neighbors must be in 1..{KNN_MAX} (KNN_MAX: the k best of a sample live in registers of the "
                          f"kernel), got {neighbors}")
-    if neighbor_stat not in NEIGHBOR_STATS:
-        raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
+    _check_neighbor_stat(neighbor_stat)
     if neighbor_reduce_hook is None and points.dim() == 2 and neighbors > max(points.shape[0], 1):
         raise ValueError(f"neighbors={neighbors} exceeds the number of points ({points.shape[0]})")
     if neighbor_reduce_hook is not None:
@@ -1469,18 +1504,13 @@ def _check_neighbors(points: torch.Tensor, neighbors, neighbor_stat, method, red
                              "its lists have no float64 kernel")
     if neighbors > 1:
         if method in ("cell", "ball"):
-            raise ValueError(f"neighbors > 1 needs the tree sweep: method {method!r} evaluates the nearest point only "
-                             "(use method=None, 'auto' or 'bvh')")
+            raise _robust_refusal("method", False, method=method)
         if reduce_hook is not None:
             raise ValueError("neighbors > 1 cannot be combined with reduce_hook: a MIN over point shards is not the "
                              "k-th nearest of their union")
         if shard_blocks:
-            raise ValueError("neighbors > 1 cannot be combined with shard_blocks=True: a block's sub-cloud holds the "
-                             "points inside its simplices' bounding balls, which bound the nearest point only")
-        if points.is_cuda and points.dtype is torch.float64:
-            raise ValueError("neighbors > 1 on ROCm tensors needs float32: the k-nearest sweep has no float64 kernel")
-        if points.is_cuda and points.dim() == 2 and not 2 <= points.shape[1] <= 8:
-            raise ValueError("neighbors > 1 on ROCm tensors needs ambient dimension 2 to 8")
+            raise _robust_refusal("shard_blocks", False)
+        _check_knn_tensor(points, method, False)
         if method is None or method == "auto":
             method = "bvh"   # (the tree sweep in every dimension; any other name is judged by the caller as always)
     return neighbors, method
@@ -1503,11 +1533,15 @@ def mass_neighbors(mass, n: int) -> int:
     return max(1, int(math.ceil(mass * int(n) - 1e-6)))
 
 
-def _check_neighbor_mass(points: torch.Tensor, neighbor_mass, neighbors, method, reduce_hook=None, shard_blocks=False,
-                         neighbor_reduce_hook=None):
-    """``flood_complex(neighbor_mass=m)`` as it is judged before any work is done -> k = ``mass_neighbors(m, N)``.  Up
-    to ``KNN_MAX`` the call then IS ``flood_complex(neighbors=k)`` (``_check_neighbors`` judges the rest); above it the
-    refusals of the wide sweep are made here."""
+def _check_robust(points: torch.Tensor, neighbors, neighbor_stat, neighbor_mass, method, reduce_hook=None,
+                  shard_blocks=False, neighbor_reduce_hook=None, *, queries: bool = False):
+    """The robust filtration's arguments as ``flood_complex`` judges them, before any work is done -> (k, method).
+    Without a mass this is ``_check_neighbors``.  With one, k = ``mass_neighbors(m, N)``: up to ``KNN_MAX`` the call IS
+    the one with ``neighbors=k`` (``_check_neighbors`` judges the rest, in its wording); above it, up to
+    ``KNN_WIDE_MAX``, the wide sweep's refusals are made here.  ``queries``: the wording of ``distance_to_measure``,
+    whose keyword is ``mass`` and whose k best belong to a query."""
+    if neighbor_mass is None:
+        return _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks, neighbor_reduce_hook)
     if not (isinstance(neighbors, Integral) and not isinstance(neighbors, bool) and int(neighbors) == 1):
         raise ValueError(f"neighbor_mass cannot be combined with neighbors={neighbors!r}: the mass fixes the number of "
                          "neighbours (leave neighbors at 1)")
@@ -1521,23 +1555,17 @@ def _check_neighbor_mass(points: torch.Tensor, neighbor_mass, neighbors, method,
                          "of the WHOLE cloud, and a shard of the points does not know how many there are (pass "
                          "neighbors=k to the sharded call)")
     if shard_blocks:
-        raise ValueError("neighbor_mass cannot be combined with shard_blocks=True: a mass is a share of the WHOLE "
-                         "cloud, and a block's sub-cloud holds only the points inside its simplices' bounding balls")
+        raise _robust_refusal("shard_blocks", True)
     if k > KNN_WIDE_MAX:
-        raise ValueError(f"neighbor_mass={float(neighbor_mass)!r} is {k} neighbours of {n} points, above KNN_WIDE_MAX = "
-                         f"{KNN_WIDE_MAX} (the k best of a sample live in the LDS of one wave): the largest mass that "
+        name, who = ("mass", "query") if queries else ("neighbor_mass", "sample")
+        raise ValueError(f"{name}={float(neighbor_mass)!r} is {k} neighbours of {n} points, above KNN_WIDE_MAX = "
+                         f"{KNN_WIDE_MAX} (the k best of a {who} live in the LDS of one wave): the largest mass that "
                          f"fits this cloud is {KNN_WIDE_MAX / n:.6g}")
-    if k > n:
-        raise ValueError(f"neighbor_mass={float(neighbor_mass)!r} is {k} neighbours, which exceeds the number of points ({n})")
-    if k > KNN_MAX:
-        if method in ("cell", "ball"):
-            raise ValueError(f"neighbor_mass needs the tree sweep: method {method!r} evaluates the nearest point only "
-                             "(use method=None, 'auto' or 'bvh')")
-        if points.is_cuda and points.dtype is torch.float64:
-            raise ValueError("neighbor_mass on ROCm tensors needs float32: the wide k-nearest sweep has no float64 kernel")
-        if points.is_cuda and not 2 <= points.shape[1] <= 8:
-            raise ValueError("neighbor_mass on ROCm tensors needs ambient dimension 2 to 8")
-    return k
+    if k <= KNN_MAX:
+        return _check_neighbors(points, k, neighbor_stat, method)
+    _check_knn_tensor(points, method, True)
+    _check_neighbor_stat(neighbor_stat)
+    return k, "bvh" if method is None or method == "auto" else method
 
 
 # The k-nearest sweep over tiles of the sorted sample order (``flooder_sweep_knn_sorted_f32``) instead of one simplex per
@@ -1583,53 +1611,40 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     sweep_knn (plain stores of the SQUARED statistic's bits into the (S, R) buffer, samples in the order of
     ``sample_order`` as in ``_sweep_dimension_bvh``) -> face max + sqrt.  Where ``knn_sorts_samples`` says so the sweep
     runs over tiles of the sorted sample order (sample keys -> radix sort -> ``flooder_sweep_knn_sorted_f32``, all inside
-    the ``sweep`` span) into the same buffer: the same words.  No host synchronisation.  ``keep``: a callable
-    that is handed the (S, R) int32 buffer (columns in swept order) - ``flood_filtration`` finds its witnesses there."""
+    the ``sweep`` span) into the same buffer: the same words.  ``KNN_MAX`` < k <= ``KNN_WIDE_MAX``: one
+    ``flooder_knn_wide_f32`` launch (a wave per sample, its k best in LDS; cell order - consecutive waves take
+    consecutive samples of a simplex, which are neighbours in space) writes that buffer: no queue, no sorted tiles, and
+    ``stats`` is not accepted.  No host synchronisation.  ``keep``: a callable that is handed the (S, R) int32 buffer
+    (columns in swept order) - ``flood_filtration`` finds its witnesses there."""
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
     S, R = verts.shape[0], weights.shape[0]
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
-    sorted_samples = knn_sorts_samples(index.dim, S, R)
-    queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)   # sharded work-queue heads
     d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    args = dict(_knn_block_fields(index, verts, plan.w_perm), k=int(k), stat=NEIGHBOR_STATS.index(stat), queue=queue,
-                out_bits=d2, stats=stats)
+    args = dict(_knn_block_fields(index, verts, plan.w_perm), k=int(k), stat=NEIGHBOR_STATS.index(stat), out_bits=d2)
+    wide = k > KNN_MAX
+    if wide and stats is not None:
+        raise ValueError("stats is not accepted above KNN_MAX neighbours: flooder_knn_wide_f32 counts nothing")
+    sorted_samples = not wide and knn_sorts_samples(index.dim, S, R)
+    if not wide:
+        queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)   # sharded work-queue heads
+        args.update(queue=queue, stats=stats)
     with _span(timer, "sweep"):
-        if sorted_samples:
+        if wide:
+            entry, blk = "flooder_knn_wide_f32", _native.KnnWide(**args)
+        elif sorted_samples:
             order = _sorted_sample_order(lib, st, index, verts, plan.w_perm, sort_state, None,
                                          int(lib.flooder_sample_key_bits(index.dim)))
-            blk = _native.KnnSorted(sample_order=order, **args)
-            _native.check(lib.flooder_sweep_knn_sorted_f32(ctypes.byref(blk), st), "flooder_sweep_knn_sorted_f32")
+            entry, blk = "flooder_sweep_knn_sorted_f32", _native.KnnSorted(sample_order=order, **args)
         else:
-            blk = _native.KnnSweep(**args)
-            _native.check(lib.flooder_sweep_knn_f32(ctypes.byref(blk), st), "flooder_sweep_knn_f32")
+            entry, blk = "flooder_sweep_knn_f32", _native.KnnSweep(**args)
+        _native.check(getattr(lib, entry)(ctypes.byref(blk), st), entry)
     out_face, _ = _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer)
     if keep is not None:
         keep(d2)
     return out_face, None
-
-
-def _sweep_dimension_knn_wide(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
-                              k: int, stat: str, plan: Optional["SamplePlan"] = None,
-                              timer: Optional[_KernelTimer] = None):
-    """``_sweep_dimension_knn`` for ``KNN_MAX`` < k <= ``KNN_WIDE_MAX``: one ``flooder_knn_wide_f32`` launch (a wave per
-    sample, its k best in LDS) writes the SQUARED statistic's bits into the same (S, R) buffer, samples in the order of
-    ``plan.w_perm`` -> face max + sqrt.  Cell order (consecutive waves take consecutive samples of a simplex, which are
-    neighbours in space); no host synchronisation."""
-    lib = _native.load()
-    dev = index.pts.device
-    st = _native.current_stream_ptr(dev)
-    S, R = verts.shape[0], weights.shape[0]
-    verts = verts.to(torch.float32).contiguous()
-    plan = plan if plan is not None else SamplePlan(weights, faces)
-    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
-    blk = _native.KnnWide(k=int(k), stat=NEIGHBOR_STATS.index(stat), out_bits=d2,
-                          **_knn_block_fields(index, verts, plan.w_perm))
-    with _span(timer, "sweep"):
-        _native.check(lib.flooder_knn_wide_f32(ctypes.byref(blk), st), "flooder_knn_wide_f32")
-    return _face_epilogue(lib, st, d2, faces, plan.rows_perm, timer=timer)
 
 
 def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
@@ -2132,6 +2147,12 @@ def _apply_items(stree, items: List[tuple]) -> None:
     stree._persistence = None
 
 
+def _auto_method(points: torch.Tensor) -> str:
+    """What ``method="auto"`` stands for: the cell sweep in 2-D and 3-D, the tree sweep otherwise (the cell sweep addresses
+    the cloud with 32-bit byte offsets: 16 B rows, below 2^28 points)."""
+    return "cell" if points.shape[1] in (2, 3) and points.shape[0] < (1 << 28) - 64 else "bvh"
+
+
 def flood_complex(
     points: torch.Tensor,
     landmarks: Union[int, torch.Tensor],
@@ -2238,23 +2259,10 @@ def flood_complex(
     ``reduce_hook``, ``neighbor_reduce_hook`` and ``shard_blocks=True`` (a mass is a share of the whole cloud, which a
     shard does not know); ``simplex_shard`` works.
     """
-    # ---- the robust filtration's arguments, before any work is done
-    wide_k = None
-    if neighbor_mass is not None:
-        k_mass = _check_neighbor_mass(points, neighbor_mass, neighbors, method, reduce_hook, shard_blocks,
+    # ---- the robust filtration's arguments, before any work is done (a mass above KNN_MAX neighbours: the wide sweep on
+    # ROCm tensors, the kd-tree on CPU tensors)
+    neighbors, method = _check_robust(points, neighbors, neighbor_stat, neighbor_mass, method, reduce_hook, shard_blocks,
                                       neighbor_reduce_hook)
-        if k_mass <= KNN_MAX:
-            neighbors = k_mass            # the call with neighbors=k, from here on
-        else:
-            wide_k = k_mass
-            if neighbor_stat not in NEIGHBOR_STATS:
-                raise ValueError(f"neighbor_stat must be one of {NEIGHBOR_STATS}, got {neighbor_stat!r}")
-            if method is None or method == "auto":
-                method = "bvh"
-    neighbors, method = _check_neighbors(points, neighbors, neighbor_stat, method, reduce_hook, shard_blocks,
-                                         neighbor_reduce_hook)
-    if wide_k is not None:
-        neighbors = wide_k                # (above KNN_MAX: the wide sweep on ROCm tensors, the kd-tree on CPU tensors)
     if use_triton is None:
         use_triton = HAS_HIP_KERNELS
     if use_triton and not _has_hip_kernels():
@@ -2266,8 +2274,7 @@ def flood_complex(
         raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {tuple(points.shape)}")
     method = SWEEP_METHOD if method is None else method
     if method == "auto":
-        # (the cell sweep addresses the cloud with 32-bit byte offsets: 16 B rows, below 2^28 points)
-        method = "cell" if points.shape[1] in (2, 3) and points.shape[0] < (1 << 28) - 64 else "bvh"
+        method = _auto_method(points)
     if method not in ("cell", "bvh", "ball"):
         raise ValueError(f"method must be 'cell', 'bvh' or 'ball', got {method!r}")
     if method == "cell" and points.shape[1] not in (2, 3):
@@ -2405,8 +2412,6 @@ def flood_complex(
         elif on_gpu and neighbors > 1 and neighbor_reduce_hook is not None:
             face_dev, _ = _sweep_dimension_knn_sharded(index, sv, weights, faces, neighbors, neighbor_stat,
                                                        neighbor_reduce_hook, plan=plan)
-        elif on_gpu and neighbors > KNN_MAX:
-            face_dev, _ = _sweep_dimension_knn_wide(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu and neighbors > 1:
             face_dev, _ = _sweep_dimension_knn(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
         elif on_gpu:

@@ -39,6 +39,21 @@ inline int64_t total_nodes(const Levels& lv) {
   return lv.off[t] + (lv.count[t] + FAN - 1) / FAN * FAN;
 }
 
+// ---- the stack walk, one wave per query (witness_search_kernel, witness_knn_kernel, knn_wide_kernel), host side.  A
+// stack word is (group of FAN siblings << 3 | level), at most FAN words per level.
+constexpr int WAVES_PER_BLOCK = 4;
+constexpr int STACK = FAN * MAXL;
+// The cloud's levels, or the refusal of entry `who`: the group has 27 bits, so the leaves make fewer than 2^27 groups.
+inline int stack_walk_levels(const char* who, int64_t n_pts, Levels& lv) {
+  lv = make_levels(n_pts);
+  if ((lv.count[0] + FAN - 1) / FAN < (1LL << 27)) return 0;
+  return failf(FLOODER_E_ARG, "%s: cloud too large for the search stack encoding", who);
+}
+inline dim3 stack_walk_grid(int64_t n) {   // a wave per query, grid-stride above 256 * 16 blocks
+  const int64_t blocks = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+  return dim3((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+}
+
 // ---- the float32 arithmetic of every path that promises the exhaustive minima bit for bit:
 // the tree sweep, the sorted-sample sweep, the finish, the k-nearest sweep and the witness searches of the gradient
 // call these, so a change to the margin or to the order of the fmafs is made once.  A call that changed a kernel's
@@ -46,7 +61,8 @@ inline int64_t total_nodes(const Levels& lv) {
 // arithmetic written out under a comment that names the helper.  Not shared at all, and to be kept in step by hand: the
 // sample as an fmaf chain over the vertices (grep "__builtin_fmaf(w"), the 16-row leaf loop (flood_bvh.hip,
 // flood_finish.hip, flood_sorted.hip, flood_cell.hip), the frontier walk of the six sweeps (sweep_knn_ids_kernel's is a
-// copy of sweep_knn_kernel's with strict culls) and the stack walk of the two witness kernels.  For those two k-nearest
+// copy of sweep_knn_kernel's with strict culls) and the stack walk of the two witness kernels and of knn_wide_kernel:
+// three copies on the device; the wide entry's HOST side is the family's (above; knn_check_ranges).  For the two sweep_knn
 // kernels one shared body under an IDS template flag was tried at compile level, in two wordings: it moved the
 // registers of nearly every instantiation of flood_knn.hip, those of the untouched value path included.  No such build
 // has been timed, so the copy stands (the note above sweep_knn_ids_kernel has the figures).  The double sweep of

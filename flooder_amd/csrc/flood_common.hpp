@@ -407,11 +407,12 @@ void with_knn_slots(int k, F&& f) {
   else f(std::integral_constant<int, 32>{});
 }
 
-// The range checks the entries share, in the order each of them makes them: k, dim, stat, then fewer points than k
-// (`needs_k_points`: flooder_witness_knn - the sweeps report that with their pointer check, behind "nothing to do") and
-// more points than 32-bit ids hold (`ids`: the entries that report ids).  `who`, the entry's name, opens every message.
-inline int knn_check_ranges(const char* who, int k, int dim, int stat, int64_t n_pts, bool needs_k_points, bool ids) {
-  if (k < 1 || k > FLOODER_KNN_MAX) return failf(FLOODER_E_ARG, "%s: k must be in 1..32", who);
+// The range checks the entries share, in each entry's order: k (1..`k_max`: FLOODER_KNN_MAX, FLOODER_KNN_WIDE_MAX for
+// the wide entry), dim, stat, then fewer points than k (`needs_k_points`: the witness and wide entries - the sweeps say
+// so with their pointer check, behind "nothing to do") and more points than 32-bit ids hold (`ids`).  `who` opens each.
+inline int knn_check_ranges(const char* who, int k, int k_max, int dim, int stat, int64_t n_pts, bool needs_k_points,
+                            bool ids) {
+  if (k < 1 || k > k_max) return failf(FLOODER_E_ARG, "%s: k must be in 1..%d", who, k_max);
   if (dim < 2 || dim > FLOODER_MAX_DIM) return failf(FLOODER_E_ARG, "%s: dim must be in 2..8", who);
   if (stat != 0 && stat != 1) return failf(FLOODER_E_ARG, "%s: stat must be 0 (kth) or 1 (dtm)", who);
   if (needs_k_points && n_pts < k) return failf(FLOODER_E_ARG, "%s: fewer points than k", who);

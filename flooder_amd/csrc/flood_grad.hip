@@ -57,9 +57,7 @@ __global__ __launch_bounds__(256) void face_argmax_kernel(const uint32_t* __rest
 // ------------------------------------------------------------------------------------------------ witness search
 // One wave per query.  The stack holds groups of 64 sibling nodes (level, group); a popped group is tested one node per
 // lane, the qualifying inner nodes push their child groups, the qualifying leaves are evaluated four at a time (16
-// points each, one point per lane).  DFS keeps at most 64 entries per level on the stack.
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int STACK = FAN * MAXL;
+// points each, one point per lane).  DFS keeps at most 64 entries per level on the stack (STACK: flood_bvh.hpp).
 
 template <int DIM>
 __global__ __launch_bounds__(256) void witness_search_kernel(const float* __restrict__ pts, int64_t n_pts,
@@ -169,9 +167,7 @@ __global__ __launch_bounds__(256) void witness_search_kernel(const float* __rest
 template <int DIM>
 struct WitnessOp {
   static int run(const flooder_witness_search_t& a, const Levels& lv, hipStream_t st) {
-    int64_t blocks = (a.n_queries + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(witness_search_kernel<DIM>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
+    hipLaunchKernelGGL(witness_search_kernel<DIM>, stack_walk_grid(a.n_queries), dim3(64 * WAVES_PER_BLOCK), 0, st,
                        a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
                        a.n_queries, a.q_simplex, a.q_row, a.q_d2, a.out_point, a.not_found);
     return check_launch("witness_search");
@@ -335,9 +331,7 @@ struct WitnessKnnOp {
     if constexpr (DIM < 2) {
       return fail(FLOODER_E_ARG, "flooder_witness_knn: dim must be in 2..8");
     } else {
-      int64_t blocks = (a.n_queries + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      if (blocks > 256 * 16) blocks = 256 * 16;
-      hipLaunchKernelGGL(witness_knn_kernel<DIM>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
+      hipLaunchKernelGGL(witness_knn_kernel<DIM>, stack_walk_grid(a.n_queries), dim3(64 * WAVES_PER_BLOCK), 0, st,
                          a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
                          a.n_queries, a.k, a.stat, a.q_simplex, a.q_row, a.q_stat, a.out_ids, a.out_d2, a.not_found);
       return check_launch("witness_knn");
@@ -387,23 +381,21 @@ int flooder_witness_search(const flooder_witness_search_t* p, void* stream) {
       !a.out_point || !a.not_found || a.n_pts < 1 || a.k1 < 1 || a.R < 1 || a.n_queries < 0 || a.dim < 2 || a.dim > 8 ||
       a.n_pts > 0x7fffffffLL)
     return fail(FLOODER_E_ARG, "flooder_witness_search: bad argument");
-  const Levels lv = make_levels(a.n_pts);
-  if ((lv.count[0] + FAN - 1) / FAN >= (1LL << 27))
-    return fail(FLOODER_E_ARG, "flooder_witness_search: cloud too large for the search stack encoding");
+  Levels lv;
+  if (int rc = stack_walk_levels("flooder_witness_search", a.n_pts, lv)) return rc;
   return dispatch_dim<WitnessOp>(a.dim, a, lv, (hipStream_t)stream);
 }
 
 int flooder_witness_knn(const flooder_witness_knn_t* p, void* stream) {
   flooder_witness_knn_t a;
   if (int rc = take(p, a, "flooder_witness_knn: bad parameter block (abi / size)")) return rc;
-  if (int rc = knn_check_ranges("flooder_witness_knn", a.k, a.dim, a.stat, a.n_pts, true, true)) return rc;
+  if (int rc = knn_check_ranges("flooder_witness_knn", a.k, FLOODER_KNN_MAX, a.dim, a.stat, a.n_pts, true, true)) return rc;
   if (a.n_queries == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.order || !a.verts || !a.weights || !a.q_simplex || !a.q_row || !a.q_stat ||
       !a.out_ids || !a.not_found || a.k1 < 1 || a.R < 1 || a.n_queries < 0)
     return fail(FLOODER_E_ARG, "flooder_witness_knn: bad argument (null pointer, k1, R, n_queries)");
-  const Levels lv = make_levels(a.n_pts);
-  if ((lv.count[0] + FAN - 1) / FAN >= (1LL << 27))
-    return fail(FLOODER_E_ARG, "flooder_witness_knn: cloud too large for the search stack encoding");
+  Levels lv;
+  if (int rc = stack_walk_levels("flooder_witness_knn", a.n_pts, lv)) return rc;
   return dispatch_dim<WitnessKnnOp>(a.dim, a, lv, (hipStream_t)stream);
 }
 

@@ -597,7 +597,7 @@ struct KnnLaunch {
 template <KnnForm FORM>
 int knn_sweep(const flooder_knn_ids_t& a, const KnnProfileCols& cols, const char* who, const char* what, void* stream) {
   constexpr bool IDS = FORM == KnnForm::ids, PROFILE = FORM == KnnForm::profile;
-  if (int rc = knn_check_ranges(who, a.k, a.dim, a.stat, a.n_pts, false, IDS)) return rc;
+  if (int rc = knn_check_ranges(who, a.k, FLOODER_KNN_MAX, a.dim, a.stat, a.n_pts, false, IDS)) return rc;
   if (PROFILE && a.n_pts < a.k) return failf(FLOODER_E_ARG, "%s: fewer points than the largest k", who);
   if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || (!a.out_bits && !IDS) || a.n_pts < a.k ||

@@ -42,8 +42,6 @@ using namespace flooder;
 
 namespace {
 
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int STACK = FAN * MAXL;
 constexpr int BUF = 128;                 // keys of a wave's insertion buffer (two per lane in a merge)
 constexpr unsigned long long NOKEY = ~0ull;
 typedef unsigned long long wkey_t;
@@ -273,9 +271,7 @@ template <int DIM>
 struct KnnWideOp {
   template <int SLOTS>
   static void launch(const flooder_knn_wide_t& a, const Levels& lv, int64_t n_cells, hipStream_t st) {
-    int64_t blocks = (n_cells + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL((knn_wide_kernel<DIM, SLOTS>), dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, st,
+    hipLaunchKernelGGL((knn_wide_kernel<DIM, SLOTS>), stack_walk_grid(n_cells), dim3(64 * WAVES_PER_BLOCK), 0, st,
                        a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, n_cells, a.k, a.stat,
                        a.sample_order, a.out_bits, a.out_ids, a.out_d2);
   }
@@ -300,17 +296,11 @@ extern "C" int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream) {
   static const char* who = "flooder_knn_wide_f32";
   flooder_knn_wide_t a;
   if (int rc = take(p, a, "flooder_knn_wide_f32: bad parameter block (abi / size)")) return rc;
-  // the ranges, before a pointer is looked at (knn_check_ranges keeps 1..32 for the register family: these are our own)
-  if (a.k < 1 || a.k > FLOODER_KNN_WIDE_MAX) return failf(FLOODER_E_ARG, "%s: k must be in 1..1024", who);
-  if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return failf(FLOODER_E_ARG, "%s: dim must be in 2..8", who);
-  if (a.stat != 0 && a.stat != 1) return failf(FLOODER_E_ARG, "%s: stat must be 0 (kth) or 1 (dtm)", who);
-  if (a.n_pts < a.k) return failf(FLOODER_E_ARG, "%s: fewer points than k", who);
-  if (a.n_pts > 0x7fffffffLL) return failf(FLOODER_E_ARG, "%s: more than 2^31 - 1 points", who);
+  if (int rc = knn_check_ranges(who, a.k, FLOODER_KNN_WIDE_MAX, a.dim, a.stat, a.n_pts, true, true)) return rc;
   if (a.n_simplices > 0 && a.R > 0 && a.n_simplices > ((1LL << 32) - 3) / a.R)
     return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
-  const Levels lv = make_levels(a.n_pts);
-  if ((lv.count[0] + FAN - 1) / FAN >= (1LL << 27))
-    return failf(FLOODER_E_ARG, "%s: cloud too large for the search stack encoding", who);
+  Levels lv;
+  if (int rc = stack_walk_levels(who, a.n_pts, lv)) return rc;
   if (!a.out_bits && !a.out_ids && !a.out_d2)
     return failf(FLOODER_E_ARG, "%s: no output (out_bits, out_ids and out_d2 are all NULL)", who);
   if (a.out_ids && !a.order) return failf(FLOODER_E_ARG, "%s: out_ids needs order (tree row -> original id)", who);

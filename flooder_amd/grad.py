@@ -108,7 +108,7 @@ def _check_args(points: torch.Tensor, method: Optional[str]):
         if not 2 <= dim <= 8:
             raise ValueError("flood_filtration: ROCm tensors need ambient dimension 2 to 8")
         if method in (None, "auto"):
-            method = "cell" if dim in (2, 3) and points.shape[0] < (1 << 28) - 64 else "bvh"
+            method = core._auto_method(points)
         if method == "cell" and dim not in (2, 3):
             raise ValueError("method 'cell' supports ambient dimension 2 and 3 only")
     elif points.device.type != "cpu":

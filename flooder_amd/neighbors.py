@@ -131,23 +131,13 @@ def nearest_neighbors(points: torch.Tensor, queries: Optional[torch.Tensor] = No
     the k-th place, and their order among themselves, is scipy's choice.
     """
     queries, neighbors = _check_arguments(points, queries, neighbors, "kth", index)
-    Q = queries.shape[0]
-    if Q == 0:
-        return (torch.empty((0, neighbors), dtype=torch.int64, device=points.device),
-                torch.empty((0, neighbors), dtype=points.dtype, device=points.device))
+    if queries.shape[0] == 0:
+        return _no_neighbors(points, neighbors)
     if points.is_cuda:
-        ids, d2, _ = _knn_ids_hip(points, queries, neighbors, "kth", index, want_d2=True, want_bits=False)
-        if squared:
-            return ids.long(), d2.view(torch.float32)
-        dist = torch.empty((Q, neighbors), dtype=torch.float32, device=points.device)
-        _native.check(_native.load().flooder_face_values_f32(_native.ptr(d2), Q * neighbors, _native.ptr(dist),
-                                                             _native.current_stream_ptr(points.device)),
-                      "flooder_face_values_f32")
-        return ids.long(), dist
-    dist, ids = _kdtree_query(points, queries, neighbors)
-    if squared:
-        dist = np.square(dist.astype(np.float64))
-    return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)), torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype)
+        ids, dist, _ = _knn_ids_hip(points, queries, neighbors, "kth", index, want_d2=True, want_bits=False)
+    else:
+        dist, ids = _kdtree_query(points, queries, neighbors)
+    return _neighbor_pair(points, ids, dist, squared)
 
 
 def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = None, mass: Optional[float] = None, *,
@@ -177,15 +167,10 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
     on_gpu = _check_points(points, "distance_to_measure")
     if (mass is None) == (neighbors is None):
         raise ValueError("distance_to_measure needs exactly one of mass and neighbors")
-    if neighbor_stat not in core.NEIGHBOR_STATS:
-        raise ValueError(f"neighbor_stat must be one of {core.NEIGHBOR_STATS}, got {neighbor_stat!r}")
+    core._check_neighbor_stat(neighbor_stat)
     n = points.shape[0]
     if mass is not None:
-        k = core.mass_neighbors(mass, n)
-        if k > core.KNN_WIDE_MAX:
-            raise ValueError(f"mass={float(mass)!r} is {k} neighbours of {n} points, above KNN_WIDE_MAX = "
-                             f"{core.KNN_WIDE_MAX} (the k best of a query live in the LDS of one wave): the largest "
-                             f"mass that fits this cloud is {core.KNN_WIDE_MAX / n:.6g}")
+        k, _ = core._check_robust(points, 1, neighbor_stat, mass, None, queries=True)
     else:
         if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
             raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
@@ -197,30 +182,34 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
         raise ValueError(f"neighbors={k} exceeds the number of points ({n})")
     queries = _check_queries_and_index(points, queries, index, on_gpu)
     points, queries = points.detach(), queries.detach()
-    Q = queries.shape[0]
-    if Q == 0:
+    if queries.shape[0] == 0:
         value = torch.empty(0, dtype=points.dtype, device=points.device)
-        return (value, torch.empty((0, k), dtype=torch.int64, device=points.device),
-                torch.empty((0, k), dtype=points.dtype, device=points.device)) if return_neighbors else value
+        return (value, *_no_neighbors(points, k)) if return_neighbors else value
     if on_gpu:
-        lib, st = _native.load(), _native.current_stream_ptr(points.device)
-        ids, d2, bits = _wide_query_hip(points, queries, k, neighbor_stat, index, return_neighbors)
-        value = _root_of_bits(lib, bits, squared, st)
-        if not return_neighbors:
-            return value
-        if squared:
-            return value, ids.long(), d2.view(torch.float32)
-        dist = torch.empty((Q, k), dtype=torch.float32, device=points.device)
-        _native.check(lib.flooder_face_values_f32(_native.ptr(d2), Q * k, _native.ptr(dist), st), "flooder_face_values_f32")
-        return value, ids.long(), dist
-    dist, ids = _kdtree_query(points, queries, k)
-    value = _cpu_statistic(dist, k, neighbor_stat, squared).to(points.dtype)
-    if not return_neighbors:
-        return value
+        ids, dist, bits = _query_sweep_hip(points, queries, k, neighbor_stat, index, return_neighbors, return_neighbors,
+                                           True, wide=True)
+        value = _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
+    else:
+        dist, ids = _kdtree_query(points, queries, k)
+        value = _cpu_statistic(dist, k, neighbor_stat, squared).to(points.dtype)
+    return (value, *_neighbor_pair(points, ids, dist, squared)) if return_neighbors else value
+
+
+def _no_neighbors(points: torch.Tensor, k: int):
+    """(ids, dist) of no queries."""
+    return (torch.empty((0, k), dtype=torch.int64, device=points.device),
+            torch.empty((0, k), dtype=points.dtype, device=points.device))
+
+
+def _neighbor_pair(points: torch.Tensor, ids, dist, squared: bool):
+    """(ids, their d2 words (ROCm tensors: both (Q, k) int32) or the kd-tree's distances (CPU: numpy), squared) -> the
+    (ids int64, dist of ``points``' dtype) that ``nearest_neighbors`` and ``distance_to_measure`` return."""
+    if points.is_cuda:
+        dist = _root_of_bits(_native.load(), dist, squared, _native.current_stream_ptr(points.device))
+        return ids.long(), dist
     if squared:
         dist = np.square(dist.astype(np.float64))
-    return (value, torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)),
-            torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype))
+    return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)), torch.as_tensor(np.ascontiguousarray(dist)).to(points.dtype)
 
 
 def _kdtree_query(points: torch.Tensor, queries: torch.Tensor, k: int):
@@ -251,13 +240,14 @@ def _index_of(points: torch.Tensor, index: Optional[core.PointIndex]) -> core.Po
 
 
 def _query_sweep_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
-                     want_ids: bool, want_d2: bool, want_bits: bool):
+                     want_ids: bool, want_d2: bool, want_bits: bool, wide: bool = False):
     """Keys of the queries inside the cloud's box (queries outside it get clamped keys: order only) -> radix sort ->
-    the k-nearest sweep over sorted tiles in its query form, k1 = R = 1 (fma(1.0f, q, 0.0f) is q):
-    ``flooder_sweep_knn_sorted_f32``, or with ``want_ids`` ``flooder_knn_ids_sorted_f32`` -> (ids (Q, k) int32 or None,
-    their d2 words (Q, k) int32 or None, the words of the squared statistic (Q,) int32 or None).  Groups of queries keep
-    the keys, the orders and the sort's scratch (24 B per query) and, in the ids form, their share of its outputs within
-    ``core.SORTED_WORKSPACE_BYTES``."""
+    a k-nearest sweep in its query form, k1 = R = 1 (fma(1.0f, q, 0.0f) is q), the sorted order its ``sample_order``
+    (queries that follow each other walk the same part of the tree): ``flooder_sweep_knn_sorted_f32`` over sorted tiles,
+    with ``want_ids`` ``flooder_knn_ids_sorted_f32``, with ``wide`` (k up to ``core.KNN_WIDE_MAX``, no work queue)
+    ``flooder_knn_wide_f32`` -> (ids (Q, k) int32 or None, their d2 words (Q, k) int32 or None, the words of the squared
+    statistic (Q,) int32 or None).  Groups of queries keep the keys, the orders and the sort's scratch (24 B per query)
+    and, in the ids and wide forms, their share of the outputs within ``core.SORTED_WORKSPACE_BYTES``."""
     lib = _native.load()
     dev = points.device
     torch.cuda.set_device(dev)
@@ -270,9 +260,12 @@ def _query_sweep_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: 
     d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids and want_d2 else None
     bits = torch.empty(Q, dtype=torch.int32, device=dev) if want_bits else None
     key_bits = int(lib.flooder_sample_key_bits(dim))
-    per_query = 24 + ((4 * k * (2 if want_d2 else 1) + (4 if want_bits else 0)) if want_ids else 0)
+    with_order = want_ids or wide          # the forms whose block has order, out_ids and out_d2: they count their outputs
+    out_bytes = 4 * k * ((ids is not None) + (d2 is not None)) + (4 if want_bits else 0)
+    per_query = 24 + (out_bytes if with_order else 0)
     per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
-    entry, block = (("flooder_knn_ids_sorted_f32", _native.KnnIds) if want_ids
+    entry, block = (("flooder_knn_wide_f32", _native.KnnWide) if wide
+                    else ("flooder_knn_ids_sorted_f32", _native.KnnIds) if want_ids
                     else ("flooder_sweep_knn_sorted_f32", _native.KnnSorted))
     for a in range(0, Q, per_group):
         b = min(Q, a + per_group)
@@ -280,44 +273,14 @@ def _query_sweep_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: 
         queue, sort_state = core._zeroed_queue(lib, dev, b - a)
         order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
         outs = dict(out_bits=None if bits is None else bits[a:b])
-        if want_ids:
-            outs.update(order=index.order32, out_ids=ids[a:b], out_d2=None if d2 is None else d2[a:b])
-        blk = block(k=k, stat=core.NEIGHBOR_STATS.index(stat), queue=queue, sample_order=order, **outs,
+        if not wide:
+            outs.update(queue=queue)
+        if with_order:
+            outs.update(order=index.order32, out_ids=None if ids is None else ids[a:b],
+                        out_d2=None if d2 is None else d2[a:b])
+        blk = block(k=k, stat=core.NEIGHBOR_STATS.index(stat), sample_order=order, **outs,
                     **core._knn_block_fields(index, verts, one))
         _native.check(getattr(lib, entry)(ctypes.byref(blk), st), entry)
-    return ids, d2, bits
-
-
-def _wide_query_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str, index: Optional[core.PointIndex],
-                    want_ids: bool):
-    """``_query_sweep_hip`` with the wide kernel: sample keys -> radix sort -> ``flooder_knn_wide_f32`` in its query
-    form (k1 = R = 1, weights {1.0f}) with the sorted order as ``sample_order`` (queries that follow each other walk
-    the same part of the tree) -> (ids (Q, k) int32 and their d2 words (Q, k) int32, or None, None; the words of the
-    squared statistic (Q,) int32).  Groups of queries keep the keys, the orders and the sort's scratch (24 B per query)
-    and, in the ids form, 8 * k bytes of outputs per query within ``core.SORTED_WORKSPACE_BYTES``."""
-    lib = _native.load()
-    dev = points.device
-    torch.cuda.set_device(dev)
-    st = _native.current_stream_ptr(dev)
-    index = _index_of(points, index)
-    q = queries.detach().contiguous()
-    Q, dim = q.shape
-    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
-    ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids else None
-    d2 = torch.empty((Q, k), dtype=torch.int32, device=dev) if want_ids else None
-    bits = torch.empty(Q, dtype=torch.int32, device=dev)
-    key_bits = int(lib.flooder_sample_key_bits(dim))
-    per_query = 24 + 4 + (8 * k if want_ids else 0)
-    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
-    for a in range(0, Q, per_group):
-        b = min(Q, a + per_group)
-        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
-        _, sort_state = core._zeroed_queue(lib, dev, b - a)
-        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
-        blk = _native.KnnWide(k=k, stat=core.NEIGHBOR_STATS.index(stat), sample_order=order, order=index.order32,
-                              out_bits=bits[a:b], out_ids=None if ids is None else ids[a:b],
-                              out_d2=None if d2 is None else d2[a:b], **core._knn_block_fields(index, verts, one))
-        _native.check(lib.flooder_knn_wide_f32(ctypes.byref(blk), st), "flooder_knn_wide_f32")
     return ids, d2, bits
 
 
@@ -330,8 +293,8 @@ def _knn_ids_hip(points: torch.Tensor, queries: torch.Tensor, k: int, stat: str,
 def _root_of_bits(lib, bits: torch.Tensor, squared: bool, st) -> torch.Tensor:
     if squared:
         return bits.view(torch.float32)
-    out = torch.empty(bits.shape[0], dtype=torch.float32, device=bits.device)
-    _native.check(lib.flooder_face_values_f32(_native.ptr(bits), bits.shape[0], _native.ptr(out), st),
+    out = torch.empty(bits.shape, dtype=torch.float32, device=bits.device)
+    _native.check(lib.flooder_face_values_f32(_native.ptr(bits), bits.numel(), _native.ptr(out), st),
                   "flooder_face_values_f32")
     return out
 

@@ -213,3 +213,31 @@ def run_on_mkl_compatible_branch(code, tmp_path):
     assert p.returncode == 0, p.stderr[-2000:]
     z = np.load(path)
     return {k: z[k] for k in z.files}
+
+
+def header_numbers(tmp_path, blocks=None, extra=None):
+    """Compile a C program against include/flooder_hip.h with the host C compiler and run it (skip without one) ->
+    ``{(C type, "sizeof"): bytes, (C type, field): offset}`` for every field of every ``{C type name: _native class}``
+    of ``blocks``, and ``{name: value}`` for every ``{name: C expression}`` of ``extra``."""
+    import shutil
+
+    import pytest
+
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
+             'int main(void) {']
+    for cname, cls in (blocks or {}).items():
+        lines.append(f'printf("{cname} sizeof %zu\\n", sizeof({cname}));')
+        lines += [f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
+    lines += [f'printf("{name} %lld\\n", (long long)({expr}));' for name, expr in (extra or {}).items()]
+    src, exe = tmp_path / "header_numbers.c", tmp_path / "header_numbers"
+    src.write_text("\n".join(lines + ['return 0; }']))
+    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
+    out = {}
+    for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        *key, val = line.split()
+        out[key[0] if len(key) == 1 else tuple(key)] = int(val)
+    assert len(out) == sum(len(c._fields_) + 1 for c in (blocks or {}).values()) + len(extra or {})
+    return out

@@ -11,7 +11,7 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native, core
 from flooder_amd.simplex_tree import SimplexTree, delaunay_simplices
-from helpers import GOLDEN, e2e_cases, load_e2e, dict_values, run_on_mkl_compatible_branch
+from helpers import GOLDEN, e2e_cases, header_numbers, load_e2e, dict_values, run_on_mkl_compatible_branch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -143,38 +143,34 @@ def test_native_library_loads_and_exports_header_symbols():
     assert [lib.flooder_padded_dim(d) for d in (1, 2, 3, 4, 5, 8)] == [2, 2, 4, 4, 8, 8]
 
 
-def test_parameter_blocks_have_the_layout_of_the_header(tmp_path):
-    """The ctypes Structures of ``_native`` against the C structs of include/flooder_hip.h: same size, every field at
-    the same offset (compiled with the host C compiler; a maintainer's cgo / JNA binding is checked the same way)."""
-    import shutil
-    import subprocess
+def _blocks():
+    """{C type name: class} of every parameter block of ``_native`` (the name opens the class's docstring)."""
+    out = {}
+    for cls in _native._Block.__subclasses__():
+        out[re.match(r"``(flooder_\w+_t)``", cls.__doc__).group(1)] = cls
+    return out
 
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    blocks = {"flooder_fused_sweep_t": _native.FusedSweep, "flooder_sorted_sweep_t": _native.SortedSweep,
-              "flooder_fps_batched_t": _native.FpsBatched}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
-             'int main(void) {']
-    for cname, cls in blocks.items():
-        lines.append(f'printf("{cname} sizeof %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname} {fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    seen = 0
-    for line in out:
-        if not line:
-            continue
-        cname, what, val = line.split()
-        cls = blocks[cname]
-        assert int(val) == (ctypes.sizeof(cls) if what == "sizeof" else getattr(cls, what).offset), line
-        seen += 1
-    assert seen == sum(len(c._fields_) + 1 for c in blocks.values())
+
+@pytest.mark.parametrize("cname", sorted(_blocks()))
+def test_parameter_block_has_the_layout_of_the_header(cname, tmp_path):
+    """A ctypes Structure of ``_native`` against its C struct of include/flooder_hip.h: same size, every field at the
+    same offset, ``size`` and ``abi`` first (compiled with the host C compiler; a maintainer's cgo / JNA binding is
+    checked the same way)."""
+    cls = _blocks()[cname]
+    out = header_numbers(tmp_path, {cname: cls})
+    assert out.pop((cname, "sizeof")) == ctypes.sizeof(cls)
+    assert out == {(cname, f): getattr(cls, f).offset for f, _ in cls._fields_}
+    assert [f for f, _ in cls._fields_][:2] == ["size", "abi"] and (cls.size.offset, cls.abi.offset) == (0, 4)
+
+
+def test_parameter_blocks_have_the_layout_of_the_header():
+    """The blocks of ``_native`` are the blocks of the header, no more and no fewer (each one's layout: the test
+    above), and a block is filled by name."""
+    header = open(os.path.join(ROOT, "include", "flooder_hip.h")).read()
+    declared = re.findall(r"^\} (flooder_\w+_t);", header, re.M)      # the closing line of a typedef struct
+    assert len(declared) == len(set(declared)) == len(re.findall(r"^typedef struct ", header, re.M)) == 11
+    assert set(declared) == set(_blocks())
+    assert len(_native._Block.__subclasses__()) == 11
     blk = _native.FusedSweep(n_pts=5, alpha=0.5)
     assert blk.size == ctypes.sizeof(_native.FusedSweep) and blk.abi == 1 and blk.n_pts == 5 and not blk.top
     with pytest.raises(TypeError):

@@ -1,12 +1,13 @@
 """What the entry points of the k-nearest family refuse, with which code and which message: ``flooder_sweep_knn_f32``,
 ``flooder_sweep_knn_sorted_f32``, ``flooder_knn_ids_sorted_f32``, ``flooder_sweep_knn_profile_f32``,
-``flooder_witness_knn`` and ``flooder_knn_merge_f32``.  Every call here returns before a pointer is looked at or a kernel
+``flooder_witness_knn``, ``flooder_knn_merge_f32``, ``flooder_knn_wide_f32`` and ``flooder_witness_search``.  Every call here returns before a pointer is looked at or a kernel
 is launched (no device needed; the non-null "pointers" are the number 4096).  A block that is wrong in two ways gets the
 message of the check that comes first: the order of the checks is part of the table.
 
 The expected codes and messages were recorded from the library as it was while every entry still made its own checks,
-before the three sweep entries and the witness entry came to share them: the table asserts those values, not what the
-code gives now."""
+before the three sweep entries and the witness entry came to share them (the wide entry and the witness search: before
+the wide entry took the family's range check and the three stack walks one refusal of a cloud too large for the stack
+word): the table asserts those values, not what the code gives now."""
 import ctypes
 
 from flooder_amd import _native
@@ -21,6 +22,8 @@ IDS = ("flooder_knn_ids_sorted_f32", _native.KnnIds)
 PROFILE = ("flooder_sweep_knn_profile_f32", _native.KnnProfile)
 WITNESS = ("flooder_witness_knn", _native.WitnessKnn)
 MERGE = ("flooder_knn_merge_f32", _native.KnnMerge)
+WIDE = ("flooder_knn_wide_f32", _native.KnnWide)
+SEARCH = ("flooder_witness_search", _native.WitnessSearch)
 FAMILY = (SWEEP, SORTED, IDS)
 
 # the messages, without the "<entry>: " in front of them
@@ -45,6 +48,11 @@ WITNESS_ARG = "bad argument (null pointer, k1, R, n_queries)"
 N_LISTS = "n_lists must be at least 1"
 N_CELLS = "n_cells must not be negative"
 MERGE_ARG = "bad argument (null pointer, more than 2^32 - 256 cells)"
+WIDE_K = "k must be in 1..1024"
+WIDE_NO_OUTPUT = "no output (out_bits, out_ids and out_d2 are all NULL)"
+WIDE_NO_ORDER = "out_ids needs order (tree row -> original id)"
+WIDE_ARG = "bad argument (null pointer, k1, R, n_simplices)"
+SEARCH_ARG = "bad argument"
 
 _LATTICE = dict(n_pts=1000, dim=3, k1=4, R=70, n_simplices=10)
 _POINTERS = {k: P for k in "pts_sorted nodes verts weights queue out_bits".split()}
@@ -56,6 +64,10 @@ GOOD = {   # what each entry would accept (and launch: never passed on as it is)
     WITNESS: dict(_LATTICE, k=8, stat=0, n_queries=5, **{k: P for k in (
         "pts_sorted nodes order verts weights q_simplex q_row q_stat out_ids not_found").split()}),
     MERGE: dict(n_cells=100, n_lists=2, k=8, stat=0, lists=P, out_bits=P),
+    WIDE: dict(n_pts=5000, dim=3, k1=4, R=10, n_simplices=7, k=200, stat=1,
+               **{k: P for k in "pts_sorted nodes verts weights out_bits".split()}),
+    SEARCH: dict(_LATTICE, n_queries=5, **{k: P for k in (
+        "pts_sorted nodes order verts weights q_simplex q_row q_d2 out_point not_found").split()}),
 }
 
 
@@ -216,6 +228,72 @@ def _cases():
     bad(MERGE, K, k=33, n_cells=0)
     bad(MERGE, SIZE, abi=2)
     bad(MERGE, SIZE, size=ctypes.sizeof(_native.KnnMerge) + 8)
+
+    # ---- the wide sweep (k up to 1024)
+    for k in (0, -3, 1025):
+        bad(WIDE, WIDE_K, k=k)
+    for dim in (1, 9):
+        bad(WIDE, DIM, dim=dim)
+    for stat in (2, -1):
+        bad(WIDE, STAT, stat=stat)
+    bad(WIDE, FEWER, n_pts=199)
+    bad(WIDE, TOO_MANY_POINTS, n_pts=TWO31)
+    bad(WIDE, TOO_MANY_SAMPLES, n_simplices=TWO31, R=2)
+    bad(WIDE, TOO_MANY_SAMPLES, n_simplices=(1 << 32) - 2, R=1)
+    bad(WIDE, WIDE_NO_OUTPUT, out_bits=None)
+    bad(WIDE, WIDE_NO_ORDER, out_ids=P)
+    bad(WIDE, WIDE_NO_ORDER, out_ids=P, out_bits=None)
+    for field in _pointers(WIDE, but=("out_bits",)):
+        bad(WIDE, WIDE_ARG, **{field: None})
+    for k1 in (0, -1):
+        bad(WIDE, WIDE_ARG, k1=k1)
+    bad(WIDE, WIDE_ARG, R=-1)
+    bad(WIDE, WIDE_ARG, n_simplices=-1)
+    nothing_to_do(WIDE, n_simplices=0, out_bits=P)
+    nothing_to_do(WIDE, R=0, out_bits=P)
+    nothing_to_do(WIDE, n_simplices=0, out_bits=None, out_d2=P)
+    # inside the bound: refused by a later check
+    for change in (dict(k=1), dict(k=33), dict(k=1024), dict(dim=2), dict(dim=8), dict(stat=0), dict(n_pts=200),
+                   dict(n_pts=TWO31 - 1), dict(n_simplices=(1 << 32) - 3, R=1), dict(out_ids=P, order=P),
+                   dict(out_bits=None, out_d2=P)):
+        bad(WIDE, WIDE_ARG, pts_sorted=None, **change)
+    # wrong in two ways: the first check in the entry's order speaks (fewer points than k and more than 2^31 - 1 of
+    # them cannot both hold with k in range: each is paired with the check behind it instead)
+    bad(WIDE, WIDE_K, k=0, dim=9)
+    bad(WIDE, WIDE_K, k=1025, stat=2, n_simplices=0)
+    bad(WIDE, DIM, dim=9, stat=2)
+    bad(WIDE, DIM, dim=1, R=0)
+    bad(WIDE, STAT, stat=2, n_pts=199)
+    bad(WIDE, STAT, stat=2, n_pts=TWO31)
+    bad(WIDE, FEWER, n_pts=199, n_simplices=TWO31, R=2)
+    bad(WIDE, FEWER, n_pts=-1, out_bits=None)
+    bad(WIDE, FEWER, n_pts=199, n_simplices=0)                              # before "nothing to do"
+    bad(WIDE, TOO_MANY_POINTS, n_pts=TWO31, n_simplices=TWO31, R=2)
+    bad(WIDE, TOO_MANY_POINTS, n_pts=TWO31, R=0)
+    bad(WIDE, TOO_MANY_SAMPLES, n_simplices=TWO31, R=2, out_bits=None)
+    bad(WIDE, WIDE_NO_OUTPUT, out_bits=None, out_ids=None, order=None, n_simplices=0)
+    bad(WIDE, WIDE_NO_OUTPUT, out_bits=None, pts_sorted=None)
+    bad(WIDE, WIDE_NO_ORDER, out_ids=P, n_simplices=0)
+    bad(WIDE, WIDE_NO_ORDER, out_ids=P, pts_sorted=None)
+    bad(WIDE, WIDE_NO_ORDER, out_ids=P, R=-1)
+    bad(WIDE, SIZE, abi=2)
+    bad(WIDE, SIZE, size=4)
+    bad(WIDE, SIZE, size=ctypes.sizeof(_native.KnnWide) + 8)
+    bad(WIDE, WIDE_NO_OUTPUT, size=ctypes.sizeof(_native.KnnSweep) - 24)      # a block that ends before out_bits
+
+    # ---- the witness search of the plain values: one refusal for everything behind the size rule
+    for field in _pointers(SEARCH):
+        bad(SEARCH, SEARCH_ARG, **{field: None})
+    for change in (dict(n_pts=0), dict(n_pts=TWO31), dict(k1=0), dict(R=0), dict(R=-1), dict(n_queries=-1), dict(dim=1),
+                   dict(dim=9), dict(dim=9, n_pts=0), dict(n_pts=TWO31, order=None)):
+        bad(SEARCH, SEARCH_ARG, **change)
+    for change in (dict(n_pts=1), dict(n_pts=TWO31 - 1), dict(k1=1), dict(R=1), dict(dim=2), dict(dim=8), dict(n_simplices=0)):
+        bad(SEARCH, SEARCH_ARG, pts_sorted=None, **change)
+    nothing_to_do(SEARCH, n_queries=0)
+    nothing_to_do(SEARCH, n_queries=0, dim=9, n_pts=TWO31)                  # "nothing to do" comes first
+    bad(SEARCH, SIZE, abi=2)
+    bad(SEARCH, SIZE, size=4, n_queries=0)
+    bad(SEARCH, SIZE, size=ctypes.sizeof(_native.WitnessSearch) + 8)
     return out
 
 
@@ -230,9 +308,10 @@ def _block(entry, change):
 
 def test_table_covers_what_it_must():
     cases = _cases()
-    assert {c[0] for c in cases} == set(GOOD) and len(cases) > 200
-    assert sum(1 for c in cases if c[2] == OK) == 10
-    assert sum(1 for c in cases if c[2] != OK and len(c[1]) >= 2 and "size" not in c[1]) >= 60   # wrong in two ways
+    assert {c[0] for c in cases} == set(GOOD) and len(cases) > 300
+    assert sum(1 for c in cases if c[2] == OK) == 15
+    assert sum(1 for c in cases if c[2] != OK and len(c[1]) >= 2 and "size" not in c[1]) >= 100   # wrong in two ways
+    assert sum(1 for c in cases if c[0] is WIDE) >= 55 and sum(1 for c in cases if c[0] is SEARCH) >= 30
     # the three blocks are what the size cases take them for
     assert ctypes.sizeof(_native.KnnSweep) < ctypes.sizeof(_native.KnnSorted) < ctypes.sizeof(_native.KnnIds)
 

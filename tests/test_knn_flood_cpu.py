@@ -6,8 +6,6 @@ import ctypes
 import itertools
 import math
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,7 +16,7 @@ from flooder_amd import _native, core
 from flooder_amd.persistence import persistence_pairs
 from flooder_amd.synthetic import generate_annulus_points_2d
 
-from helpers import assert_close_filtration
+from helpers import assert_close_filtration, header_numbers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -231,27 +229,9 @@ def test_simplex_shards_combine_to_the_unsharded_values_cpu():
 
 # ------------------------------------------------------------------------------------------------ 6. ABI
 def test_knn_sweep_block_has_the_layout_of_the_header(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    cname, cls = "flooder_knn_sweep_t", _native.KnnSweep
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
-             'int main(void) {', f'printf("sizeof %zu\\n", sizeof({cname}));', 'printf("knn_max %d\\n", FLOODER_KNN_MAX);']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
-    out = [ln for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if ln]
-    for line in out:
-        what, val = line.split()
-        if what == "knn_max":
-            assert int(val) == core.KNN_MAX
-        else:
-            assert int(val) == (ctypes.sizeof(cls) if what == "sizeof" else getattr(cls, what).offset), line
-    assert len(out) == len(cls._fields_) + 2
+    """(size and offsets against the header: test_host.py, test_parameter_block_has_the_layout_of_the_header)"""
+    cls = _native.KnnSweep
+    assert header_numbers(tmp_path, extra={"knn_max": "FLOODER_KNN_MAX"}) == {"knn_max": core.KNN_MAX}
     for needed in ("size", "abi", "pts_sorted", "n_pts", "dim", "nodes", "verts", "weights", "k1", "R", "n_simplices", "k",
                    "stat", "queue", "out_bits", "stats"):
         assert hasattr(cls, needed), needed

@@ -5,8 +5,6 @@ point's refusals (no device needed) and the CLI flags of the robust filtration."
 import ctypes
 import os
 import pickle
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,8 @@ import torch
 
 import flooder_amd as fa
 from flooder_amd import _native, cli, core, profile
+
+from helpers import header_numbers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KS = (1, 2, 3, 8, 17, 32)
@@ -165,31 +165,12 @@ def test_refusals_come_before_any_work(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ 4. ABI
 def test_knn_profile_block_has_the_layout_of_the_header(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
+    """(size and offsets against the header: test_host.py, test_parameter_block_has_the_layout_of_the_header)"""
     cname, cls = "flooder_knn_profile_t", _native.KnnProfile
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
-             'int main(void) {', f'printf("sizeof %zu\\n", sizeof({cname}));', 'printf("cols_max %d\\n", FLOODER_KNN_COLS_MAX);',
-             f'printf("col_k_bytes %zu\\n", sizeof((({cname}*)0)->col_k));',
-             f'printf("col_stat_bytes %zu\\n", sizeof((({cname}*)0)->col_stat));']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
-    out = [ln for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if ln]
-    for line in out:
-        what, val = line.split()
-        if what == "cols_max":
-            assert int(val) == _native.KNN_COLS_MAX == 64
-        elif what in ("col_k_bytes", "col_stat_bytes"):
-            assert int(val) == 4 * 64 == getattr(cls, what[:-6]).size
-        else:
-            assert int(val) == (ctypes.sizeof(cls) if what == "sizeof" else getattr(cls, what).offset), line
-    assert len(out) == len(cls._fields_) + 4
+    out = header_numbers(tmp_path, extra={"cols_max": "FLOODER_KNN_COLS_MAX", "col_k": f"sizeof((({cname}*)0)->col_k)",
+                                          "col_stat": f"sizeof((({cname}*)0)->col_stat)"})
+    assert out["cols_max"] == _native.KNN_COLS_MAX == 64
+    assert out["col_k"] == 4 * 64 == cls.col_k.size and out["col_stat"] == 4 * 64 == cls.col_stat.size
     names = {f for f, _ in cls._fields_}
     single = {f for f, _ in _native.KnnSweep._fields_}
     # the single sweep's fields without k and stat (and its padding word), the column list in their place

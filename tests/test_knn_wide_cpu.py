@@ -6,8 +6,6 @@ refusal, ``flood_complex_sharded``'s modes and the command line's pair of option
 
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,7 +15,7 @@ import flooder_amd as fa
 from flooder_amd import _native, cli, core, distributed
 
 import knn_wide_reference as kw
-from helpers import assert_close_filtration, tolerances
+from helpers import assert_close_filtration, header_numbers, tolerances
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "flooder_knn_wide_f32"
@@ -39,28 +37,9 @@ def test_entry_is_declared_built_and_bound():
 
 
 def test_block_has_the_layout_of_the_header(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    cname, cls = "flooder_knn_wide_t", _native.KnnWide
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
-             'int main(void) {', f'printf("sizeof %zu\\n", sizeof({cname}));',
-             'printf("wide_max %d\\n", FLOODER_KNN_WIDE_MAX);']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
-    out = [ln for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if ln]
-    for line in out:
-        what, val = line.split()
-        if what == "wide_max":
-            assert int(val) == core.KNN_WIDE_MAX
-        else:
-            assert int(val) == (ctypes.sizeof(cls) if what == "sizeof" else getattr(cls, what).offset), line
-    assert len(out) == len(cls._fields_) + 2
+    """(size and offsets against the header: test_host.py, test_parameter_block_has_the_layout_of_the_header)"""
+    cls = _native.KnnWide
+    assert header_numbers(tmp_path, extra={"wide_max": "FLOODER_KNN_WIDE_MAX"}) == {"wide_max": core.KNN_WIDE_MAX}
     for needed in ("size", "abi", "pts_sorted", "n_pts", "dim", "k1", "nodes", "verts", "weights", "R", "k", "n_simplices",
                    "stat", "order", "sample_order", "out_bits", "out_ids", "out_d2"):
         assert hasattr(cls, needed), needed

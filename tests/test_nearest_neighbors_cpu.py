@@ -13,7 +13,7 @@ import torch
 import flooder_amd as fa
 from flooder_amd import _native
 
-from helpers import ROOT, tolerances
+from helpers import ROOT, header_numbers, tolerances
 
 KS = (1, 2, 8, 32)
 STATS = ("kth", "dtm")
@@ -175,25 +175,9 @@ def test_is_a_public_name_and_bound():
 
 
 def test_block_has_the_layout_of_the_header(tmp_path):
-    """As ``test_parameter_blocks_have_the_layout_of_the_header`` (test_host.py), for ``flooder_knn_ids_t``."""
-    import shutil
-    import subprocess
-
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    cname, cls = "flooder_knn_ids_t", _native.KnnIds
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "flooder_hip.h")}"',
-             'int main(void) {', f'printf("sizeof %zu\\n", sizeof({cname}));']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += ['return 0; }']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert len(out) == len(cls._fields_) + 1
-    assert int(out.pop("sizeof")) == ctypes.sizeof(cls)
-    for fname, val in out.items():
-        assert int(val) == getattr(cls, fname).offset, fname
+    """``flooder_knn_ids_t`` is ``flooder_knn_sorted_t`` and a tail in C as well (size and offsets of each against its
+    class: test_host.py, test_parameter_block_has_the_layout_of_the_header)."""
+    out = header_numbers(tmp_path, {"flooder_knn_sorted_t": _native.KnnSorted, "flooder_knn_ids_t": _native.KnnIds})
+    for fname, _ in _native.KnnSorted._fields_:
+        assert out["flooder_knn_ids_t", fname] == out["flooder_knn_sorted_t", fname], fname
+    assert out["flooder_knn_ids_t", "order"] >= out["flooder_knn_sorted_t", "sizeof"]
