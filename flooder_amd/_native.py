@@ -271,6 +271,10 @@ SIGNATURES = {
     "flooder_knn_merge_f32": (c_int, [ctypes.POINTER(KnnMerge), c_void_p]),
     # ... and the k nearest for k up to 1024, one wave per cell (flood_complex(neighbor_mass=m), distance_to_measure)
     "flooder_knn_wide_f32": (c_int, [ctypes.POINTER(KnnWide), c_void_p]),
+    # the weighted filtration (flood_complex(point_weights=w)): the minimum of a value per tree row over every node, and
+    # the power-distance sweep on the block of the sorted k-nearest sweep (k = 1) plus the weights and their node minima
+    "flooder_node_min_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "flooder_sweep_power_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p, c_void_p, c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -163,6 +163,13 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--neighbor-stat", choices=("kth", "dtm"), default="kth",
                    help="Statistic of the K nearest: kth (K-distance) or dtm (distance to the empirical measure) "
                         "(default: %(default)s)")
+    wex = g.add_mutually_exclusive_group(required=False)
+    wex.add_argument("--point-weights", metavar="FILE", type=str, default=None,
+                     help="Weighted filtration: NumPy .npy file with one weight per point, (N,); a sample is measured by "
+                          "sqrt(min_x |p - x|^2 + w_x^2) (not together with --neighbors / --neighbor-mass; default: off)")
+    wex.add_argument("--dtm-weights", metavar="MASS", type=float, default=None,
+                     help="Weighted filtration with weights = distance_to_measure(points, mass=MASS): the DTM "
+                          "filtration (0 < MASS <= 1, at most 1024 neighbours; default: off)")
     mex = g.add_mutually_exclusive_group(required=False)
     mex.add_argument("--points-per-edge", metavar="INT", type=int, default=None,
                      help="Points per edge for Flood PH (default: 30 if neither option given)")
@@ -210,6 +217,19 @@ def load_point_cloud(path: Path):
         raise ValueError(f"Expected a 2D array (N, D); got shape {arr.shape}")
     t = torch.from_numpy(np.array(arr, dtype=np.float32, copy=True))
     return t, int(t.shape[0]), int(t.shape[1])
+
+
+def load_point_weights(path: Path, n_pts: int) -> torch.Tensor:
+    """(N,) float32 weights of ``--point-weights``; ``FileNotFoundError`` / ``ValueError`` as ``load_point_cloud``."""
+    if not path.exists():
+        raise FileNotFoundError(f"Weights file does not exist: {path}")
+    try:
+        arr = np.load(path, mmap_mode="r")
+    except Exception as e:
+        raise ValueError(f"Failed to load NumPy file '{path}': {e}") from e
+    if arr.shape != (n_pts,):
+        raise ValueError(f"Expected one weight per point, shape ({n_pts},); got shape {arr.shape}")
+    return torch.from_numpy(np.array(arr, dtype=np.float32, copy=True))
 
 
 def effective_max_dim(user_max: Optional[int], ambient_dim: int) -> int:
@@ -281,7 +301,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
 
     with StepTimer("Flood complex", device, args.cuda_events) as t:
         cloud = cloud_cpu.to(device, non_blocking=True)
+        point_weights = None
+        if args.point_weights is not None:
+            point_weights = load_point_weights(Path(args.point_weights), n_pts).to(device, non_blocking=True)
+        elif args.dtm_weights is not None:
+            from . import distance_to_measure
+
+            point_weights = distance_to_measure(cloud, mass=args.dtm_weights)
         stree = flood_complex(cloud, args.num_landmarks, max_dimension=max_dim, points_per_edge=points_per_edge,
+                              point_weights=point_weights,
                               batch_size=args.batch_size, fps_h=args.fps_height,
                               use_triton=use_triton if device.type == "cuda" else None,
                               return_simplex_tree=True, num_rand=num_rand, neighbors=args.neighbors,

@@ -1647,6 +1647,97 @@ def _sweep_dimension_knn(index: PointIndex, verts: torch.Tensor, weights: torch.
     return out_face, None
 
 
+# ------------------------------------------------------------------------------ weighted filtration (power distance)
+_POWER_REFUSALS = dict(
+    robust="point_weights cannot be combined with neighbors > 1, neighbor_mass or neighbor_reduce_hook: the weighted "
+           "filtration is a minimum over points with one value per sample (weights from distance_to_measure carry the "
+           "k nearest already)",
+    method="point_weights needs the tree sweep: method {method!r} evaluates the unweighted nearest point only (use "
+           "method=None, 'auto' or 'bvh')",
+    float64="point_weights on ROCm tensors needs float32: the power-distance sweep has no float64 kernel",
+    dimension="point_weights on ROCm tensors needs ambient dimension 2 to 8",
+    shard_blocks="point_weights cannot be combined with shard_blocks=True: a block's sub-cloud holds the points inside "
+                 "its simplices' bounding balls, which bound the nearest point and not the power-nearest",
+    finite="point_weights must be finite")
+
+
+def _check_point_weights(points: torch.Tensor, point_weights, method, shard_blocks=False, neighbors=1,
+                         neighbor_mass=None, neighbor_reduce_hook=None):
+    """The weighted filtration's arguments as ``flood_complex`` and ``power_distance`` judge them, before any work is
+    done -> method (``"bvh"`` in place of None / "auto").  On ROCm tensors finite weights are the caller's contract (a
+    check would synchronise with the host); on CPU tensors non-finite weights are refused."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0:
+        got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
+        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
+    if not isinstance(point_weights, torch.Tensor) or tuple(point_weights.shape) != (points.shape[0],):
+        got = tuple(point_weights.shape) if isinstance(point_weights, torch.Tensor) else type(point_weights).__name__
+        raise ValueError(f"point_weights must be a ({points.shape[0]},) tensor, one weight per point, got {got}")
+    if point_weights.dtype != points.dtype:
+        raise ValueError(f"point_weights.dtype ({point_weights.dtype}) != points.dtype ({points.dtype})")
+    if point_weights.device != points.device:
+        raise ValueError(f"point_weights.device ({point_weights.device}) != points.device ({points.device})")
+    if (not (isinstance(neighbors, Integral) and not isinstance(neighbors, bool) and int(neighbors) == 1)
+            or neighbor_mass is not None or neighbor_reduce_hook is not None):
+        raise ValueError(_POWER_REFUSALS["robust"])
+    if method in ("cell", "ball"):
+        raise ValueError(_POWER_REFUSALS["method"].format(method=method))
+    if points.is_cuda and points.dtype is torch.float64:
+        raise ValueError(_POWER_REFUSALS["float64"])
+    if points.is_cuda and not 2 <= points.shape[1] <= 8:
+        raise ValueError(_POWER_REFUSALS["dimension"])
+    if shard_blocks:
+        raise ValueError(_POWER_REFUSALS["shard_blocks"])
+    if not points.is_cuda and not bool(torch.isfinite(point_weights).all()):
+        raise ValueError(_POWER_REFUSALS["finite"])
+    return "bvh" if method is None or method == "auto" else method
+
+
+def _power_weights(index: PointIndex, point_weights: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Once per call: (``w_sorted`` (n_pad,) = |w| in tree-row order, the rows of the padded last leaf +inf; ``node_w`` =
+    ``flooder_node_min_f32`` of it: the smallest weight below every node of the box tree).  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    w_sorted = torch.full((index.pts.shape[0],), float("inf"), dtype=torch.float32, device=dev)
+    w_sorted[:index.n] = point_weights.detach().to(torch.float32).abs()[index.order32.long()]
+    node_w = torch.empty(index.nodes.shape[0], dtype=torch.float32, device=dev)
+    _native.check(lib.flooder_node_min_f32(_native.ptr(w_sorted), index.n, _native.ptr(node_w),
+                                           _native.current_stream_ptr(dev)), "flooder_node_min_f32")
+    return w_sorted, node_w
+
+
+def _sweep_dimension_power(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                           w_sorted: torch.Tensor, node_w: torch.Tensor,
+                           reduce_hook: Optional[Callable[[torch.Tensor], None]] = None,
+                           plan: Optional["SamplePlan"] = None, timer: Optional[_KernelTimer] = None,
+                           stats: Optional[torch.Tensor] = None):
+    """All simplices of one dimension against an indexed WEIGHTED point set -> (S, F) face maxima of the power distance
+    sqrt(min_x |p - x|^2 + w_x^2).  ``w_sorted``, ``node_w``: ``_power_weights`` of the call.
+
+    sweep_power (plain stores of the squared minimum's bits into the (S, R) buffer, samples in the order of
+    ``sample_order`` as in ``_sweep_dimension_bvh``; over tiles of the sorted sample order where ``knn_sorts_samples``
+    says so, else in the identity order, a simplex's rows per tile: the same words) -> [reduce_hook: cross-shard MIN,
+    exact here - the minimum over a union is the minimum of the minima] -> face max + sqrt.  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, R = verts.shape[0], weights.shape[0]
+    if S == 0:
+        return _no_simplices(faces, R, dev, False)
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    d2 = torch.empty((S, R), dtype=torch.int32, device=dev)
+    sorted_samples = knn_sorts_samples(index.dim, S, R)
+    queue, sort_state = _zeroed_queue(lib, dev, S * R if sorted_samples else 0)   # sharded work-queue heads
+    with _span(timer, "sweep"):
+        order = (_sorted_sample_order(lib, st, index, verts, plan.w_perm, sort_state, None,
+                                      int(lib.flooder_sample_key_bits(index.dim))) if sorted_samples else None)
+        blk = _native.KnnSorted(k=1, stat=0, out_bits=d2, queue=queue, stats=stats, sample_order=order,
+                                **_knn_block_fields(index, verts, plan.w_perm))
+        _native.check(lib.flooder_sweep_power_f32(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w), st),
+                      "flooder_sweep_power_f32")
+    return _face_epilogue(lib, st, d2, faces, plan.rows_perm, reduce_hook=reduce_hook, timer=timer)
+
+
 def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                                  columns, plan: Optional["SamplePlan"] = None,
                                  stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None):
@@ -2173,6 +2264,7 @@ def flood_complex(
     index: Optional["PointIndex"] = None,
     shard_blocks: bool = False,
     landmarks_in_cloud: Optional[bool] = None,
+    point_weights: Optional[torch.Tensor] = None,
     neighbors: int = 1,
     neighbor_stat: str = "kth",
     neighbor_reduce_hook: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
@@ -2258,9 +2350,28 @@ def flood_complex(
     a mass that is more than ``KNN_WIDE_MAX`` neighbours, ``method`` ``"cell"`` / ``"ball"``, ROCm float64 tensors, and
     ``reduce_hook``, ``neighbor_reduce_hook`` and ``shard_blocks=True`` (a mass is a share of the whole cloud, which a
     shard does not know); ``simplex_shard`` works.
+
+    ``point_weights=w`` (keyword-only): the WEIGHTED filtration.  ``w``: an (N,) tensor of the points' dtype on their
+    device, one weight per point; a sample p is measured by the power distance sqrt(min_x |p - x|^2 + w_x^2) instead of
+    min_x |p - x| (the weighted Cech / DTM filtration; the weight enters squared, so its sign does not matter, and
+    w = 0 gives the plain filtration's values).  With ``w = distance_to_measure(points, mass=m)`` the value approximates
+    the distance to the measure at every sample from N numbers (README, "Weighted filtration").  ``None`` is the code
+    path of a call without the argument.  ROCm float32 tensors in 2 to 8 dimensions run the power-distance tree sweep
+    (``flooder_sweep_power_f32``; ``method`` ``None`` / ``"auto"`` / ``"bvh"``; ``index=`` and the remembered index are
+    reused as they are) and must hold finite weights (not checked: the check would synchronise with the host); CPU
+    tensors query a kd-tree over the lifted cloud ``[points, |w|]`` with ``[samples, 0]`` and refuse non-finite weights.
+    The vertex values are ``power_distance(points, w, landmarks)``, bit for bit on ROCm tensors.  ``reduce_hook`` works
+    and is exact (the minimum over a union of point shards is the minimum of their minima; each shard passes its own
+    weights), as do ``simplex_shard`` with ``face_reduce_hook`` (every ``world``-th simplex), ``num_rand``,
+    ``max_dimension`` and ``sort_axis``.  Refused: ``method`` ``"cell"`` / ``"ball"``, ROCm float64 tensors,
+    ``shard_blocks=True`` (the bounding balls bound the nearest point, not the power-nearest), ``neighbors`` > 1,
+    ``neighbor_mass`` and ``neighbor_reduce_hook``, and a wrong shape, dtype or device.
     """
-    # ---- the robust filtration's arguments, before any work is done (a mass above KNN_MAX neighbours: the wide sweep on
+    # ---- the weighted filtration's arguments, then the robust filtration's arguments, before any work is done (a mass above KNN_MAX neighbours: the wide sweep on
     # ROCm tensors, the kd-tree on CPU tensors)
+    if point_weights is not None:
+        method = _check_point_weights(points, point_weights, method, shard_blocks, neighbors, neighbor_mass,
+                                      neighbor_reduce_hook)
     neighbors, method = _check_robust(points, neighbors, neighbor_stat, neighbor_mass, method, reduce_hook, shard_blocks,
                                       neighbor_reduce_hook)
     if use_triton is None:
@@ -2317,7 +2428,9 @@ def flood_complex(
     else:
         from scipy.spatial import KDTree
 
-        kdtree = KDTree(np.asarray(points))
+        # (weighted: |p - x|^2 + w_x^2 is the squared distance from (p, 0) to the lifted point (x, |w_x|))
+        kdtree = KDTree(np.asarray(points) if point_weights is None
+                        else np.concatenate([np.asarray(points), np.asarray(point_weights.detach().abs())[:, None]], axis=1))
 
     index = None
     use_f64 = on_gpu and dtype is torch.float64 and method != "ball"
@@ -2352,6 +2465,8 @@ def flood_complex(
                                                        _native.ptr(index.order32), _native.ptr(pts64_sorted),
                                                        index.pts.shape[0], _native.current_stream_ptr(device)),
                           "flooder_gather_rows_f64")
+    if on_gpu and point_weights is not None:   # the weights in tree-row order and their node minima, once per call
+        w_sorted, node_w = _power_weights(index, point_weights)
     stree, simplices = _build_complex(landmarks, max_dimension)
     LAST_STATS.reset()
     LAST_STATS.n_points = points.shape[0]
@@ -2386,7 +2501,7 @@ def flood_complex(
             if blocks:   # a contiguous block of the queue (the simplices are ordered along the widest axis)
                 mine = torch.arange(num_simplices * sh_rank // sh_world, num_simplices * (sh_rank + 1) // sh_world,
                                     device=device)
-            elif (on_gpu and not use_f64 and reduce_hook is None and neighbors == 1
+            elif (on_gpu and not use_f64 and reduce_hook is None and neighbors == 1 and point_weights is None
                   and shards_sorted_tiles(dim, num_simplices, weights.shape[0], method)):
                 mine = None          # all simplices, a contiguous run of the TILES of the sorted sample order
                 tile_shard = (sh_rank, sh_world)
@@ -2414,6 +2529,8 @@ def flood_complex(
                                                        neighbor_reduce_hook, plan=plan)
         elif on_gpu and neighbors > 1:
             face_dev, _ = _sweep_dimension_knn(index, sv, weights, faces, neighbors, neighbor_stat, plan=plan)
+        elif on_gpu and point_weights is not None:
+            face_dev, _ = _sweep_dimension_power(index, sv, weights, faces, w_sorted, node_w, reduce_hook, plan=plan)
         elif on_gpu:
             if method == "ball":
                 face_dev, _ = _sweep_dimension_hip(pts_pad, search, axis, dim, sv,
@@ -2434,6 +2551,8 @@ def flood_complex(
                                      faces)
         else:
             samples = weights.unsqueeze(0) @ sv
+            if point_weights is not None:   # the lifted samples (p, 0)
+                samples = torch.cat([samples, samples.new_zeros(samples.shape[:-1] + (1,))], dim=-1)
             # (the reference queries with scipy's default of ONE worker, core.py:198; the distances do not depend on
             # the number of workers)
             dist, _ = kdtree.query(np.asarray(samples), workers=CPU_WORKERS)

@@ -1,0 +1,295 @@
+// flood_power.hip - the weighted (power-distance) tree sweep (gfx950): flood_complex(point_weights=w).
+//
+// Every point x of the cloud carries a weight w_x >= 0 and a sample p is measured by
+//     f(p)^2 = min_x ( |p - x|^2 + w_x^2 ),
+// the power distance of the weighted Cech / DTM filtration.  flooder_sweep_power_f32 writes the float32 bits of that
+// minimum into the (S, R) buffer that flooder_face_max_f32 reads - the square root and the face maxima stay there.
+//
+//   sweep_power<DIM>   sweep_knn_kernel<DIM, K, false, SORTED> at one value per lane: one wave owns 64 consecutive
+//                      entries of the sample order - NULL: the identity order g = 0 .. N-1 cut simplex by simplex, a tile
+//                      is 64 consecutive rows of ONE simplex as in flooder_sweep_knn_f32 (flat tiles of 64 straddle the
+//                      compact 64-row runs of the lattice whenever R is no multiple of 64: 3x the leaf tests at cfg 2,
+//                      DESIGN.md 10) -, one sample per lane rebuilt in registers (fma in vertex order), the nearest-
+//                      first wave-uniform walk over the same nodes with the LDS level stack, the 16 rows of a leaf AND
+//                      its 16 weights through the scalar cache.  The word of a pair is
+//                          fmaf(w, w, dist2<DIM>(p, x))
+//                      - the project's squared distance followed by ONE fma with the weight itself - and a lane keeps
+//                      the smallest.
+//
+// Bounds.  node_w[c] (flooder_node_min_f32 of the weights) is the smallest weight below node c, so
+//     child:  fmaf(node_w[c], node_w[c], box_gap2(box of c, box of the tile))
+//     leaf:   fmaf(node_w[leaf], node_w[leaf], box_gap2(p, box of the leaf))
+// are the Euclidean bounds of the family with the node's weight added the way a pair adds its own.  Rounded fma is
+// monotone in each non-negative argument, the gap is a lower bound of every distance below the node up to a few ulp
+// and the node's weight is <= every weight below it: both are lower bounds of every pair word below the node within
+// the margin SAFE, as the Euclidean ones are.  A child, a leaf or a level is skipped only when !(lb * SAFE < bound),
+// bound = the largest running minimum of the wave (levels, children) or the lane's own (leaf test).
+//
+// Exactness.  A minimum does not depend on the order in which its elements are offered, and what is skipped cannot
+// lower any lane's minimum - so the word written is the minimum over ALL points, bit for bit, whatever the tree and
+// whichever samples share a wave.  Zero weights give fmaf(0, 0, d2) = d2: the words of the k = 1 sweeps.  The lift
+// (x, w) in DIM + 1 dimensions swept by flooder_sweep_knn_sorted_f32 at k = 1 against (p, 0) ends its dist2 chain in
+// fmaf(0 - w, 0 - w, d2) - the same word: the oracle of tests/test_gpu_power_kernel.py, not the path.
+//
+// flooder_node_min_f32 builds node_w: the minimum of a value per tree row over every node of the box tree, in the
+// layout of the node array (Levels), padding slots +inf.  One launch per level, plain vector stores, no atomics.
+
+#include "flood_common.hpp"
+#include "flood_bvh.hpp"
+
+using namespace flooder;
+
+namespace {
+
+// level 0: node i = min over the LEAF rows of leaf i; `padded` = the level's slot count (x64), slots past `count` +inf
+__global__ __launch_bounds__(256) void node_min_leaf_kernel(const float* __restrict__ vals, int64_t count, int64_t padded,
+                                                            float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= padded) return;
+  float m = __builtin_inff();
+  if (i < count) {
+    static_assert(LEAF % 4 == 0, "a leaf's values are read as float4");
+    const float4* v = reinterpret_cast<const float4*>(vals + i * LEAF);
+#pragma unroll
+    for (int q = 0; q < LEAF / 4; ++q) {
+      const float4 t = v[q];
+      m = __builtin_fminf(m, __builtin_fminf(__builtin_fminf(t.x, t.y), __builtin_fminf(t.z, t.w)));
+    }
+  }
+  out[i] = m;
+}
+
+// level l > 0: one wave per node, lane j reads child j (the child level is padded to x64 with +inf)
+__global__ __launch_bounds__(256) void node_min_inner_kernel(const float* __restrict__ child, int64_t count, int64_t padded,
+                                                             float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= padded) return;
+  float m = __builtin_inff();
+  if (i < count) m = wave_min_f32(child[i * FAN + lane]);
+  if (lane == 0) out[i] = m;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void sweep_power_kernel(
+    const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
+    const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int32_t* __restrict__ queue,
+    uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats, const uint32_t* __restrict__ order,
+    const float* __restrict__ w_sorted, const float* __restrict__ node_w) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ float s_lb[4][MAXL][FAN];
+  __shared__ int64_t s_grp[4][MAXL];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int tiles = (R + 63) / 64;
+  const int64_t n_samples = n_simplices * (int64_t)R;
+  const int64_t n_items = order ? (n_samples + 63) / 64 : n_simplices * tiles;
+  const int top = lv.n_levels - 1;
+  unsigned long long n_leaf_eval = 0, n_leaf_test = 0, n_node_test = 0, max_item_tests = 0;
+
+  int q_shard = (int)(((int64_t)blockIdx.x * 4 + wv) % QSHARDS), q_tried = 0;
+  for (;;) {
+    const int64_t g = queue_pop(queue, q_shard, q_tried, n_items, lane);  // sharded heads (flood_common.hpp)
+    if (g < 0) break;
+    const unsigned long long tests_before = n_leaf_test + n_node_test;
+    // ---- this lane's sample (s, r): entry `lane` of the item's run of the order, or (order NULL: the identity order
+    // simplex by simplex) of the item's simplex - the rows of a simplex come in compact runs of 64 (sample_order), and
+    // a tile that straddled two runs or two simplices would search for both
+    int64_t s;
+    int r;
+    bool live;
+    if (order) {
+      const int64_t pos = g * 64 + lane;
+      live = pos < n_samples;
+      const uint32_t id = order[live ? pos : n_samples - 1];  // duplicate of the last entry, never stored
+      const uint32_t si = id / (uint32_t)R;
+      s = (int64_t)si;
+      r = (int)(id - si * (uint32_t)R);
+    } else {
+      s = g / tiles;
+      r = (int)(g - s * tiles) * 64 + lane;
+      live = r < R;
+      if (!live) r = R - 1;  // duplicate of the last sample, never stored
+    }
+    // p = sum_j w[r,j] * v[s,j,:], as sweep_bvh builds it
+    float p[DIM];
+    const float* vs = verts + s * (int64_t)k1 * DIM;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) p[c] = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) p[c] = __builtin_fmaf(w, vs[j * DIM + c], p[c]);
+    }
+    // (the int32 word of the float: never negative and never NaN, so the signed integer order is the value order)
+    int best = (int)INF_BITS;
+
+    // ---- bounding box of the tile (wave-uniform)
+    float tlo[DIM], thi[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      tlo[c] = wave_min_f32(p[c]);
+      thi[c] = wave_max_f32(p[c]);
+    }
+    float M = __builtin_inff();  // largest running minimum of the tile (wave-uniform)
+
+    // child `lane` of group `grp` at level `lvl`: its box (registers) and the lower bound of every pair word below it
+    // against the tile box (a lane past the end of the level: +inf; its slot of node_w is padding, +inf as well)
+    float c_lo[DIM], c_hi[DIM];
+    auto child_bounds = [&](int lvl, int64_t grp) -> float {
+      const float gap2 = child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
+      const float nw = node_w[lv.off[lvl] + grp * FAN + lane];
+      return __builtin_fmaf(nw, nw, gap2);
+    };
+
+    // inner levels keep their per-lane bounds in LDS; the leaf level runs in registers (lb0, c_lo / c_hi)
+    int lvl = top;
+    float lb0 = child_bounds(top, 0);
+    int64_t grp0 = 0;
+    ++n_node_test;
+    if (top > 0) {
+      s_lb[wv][top][lane] = lb0;
+      if (lane == 0) s_grp[wv][top] = 0;
+    }
+    for (;;) {
+      if (lvl > 0) {
+        const float lbv = s_lb[wv][lvl][lane];
+        const float mn = wave_min_f32(lbv);
+        if (!(mn * SAFE < M)) {  // nothing left at this level can lower a minimum of the tile
+          if (++lvl > top) break;
+          continue;
+        }
+        const int j = __builtin_ctzll(__ballot(lbv == mn));
+        if (lane == j) s_lb[wv][lvl][lane] = __builtin_inff();  // visited
+        const int64_t c = wave_uniform64(s_grp[wv][lvl]) * FAN + j;
+        --lvl;
+        const float lb = child_bounds(lvl, c);
+        ++n_node_test;
+        if (lvl > 0) {
+          s_lb[wv][lvl][lane] = lb;
+          if (lane == 0) s_grp[wv][lvl] = c;
+        } else {
+          lb0 = lb;
+          grp0 = c;
+        }
+        continue;
+      }
+      // ---- leaf level: nearest unvisited leaf of the current group
+      const float mn = wave_min_f32(lb0);
+      if (!(mn * SAFE < M)) {
+        if (++lvl > top) break;
+        continue;
+      }
+      const int j = __builtin_ctzll(__ballot(lb0 == mn));
+      if (lane == j) lb0 = __builtin_inff();  // visited
+      const int64_t c = grp0 * FAN + j;
+      ++n_leaf_test;
+      // can the minimum of any lane still drop against leaf c?  (its box comes from lane j, its weight is wave-uniform)
+      float lbp = 0.f;  // (readlane_row + box_gap2 of flood_bvh.hpp, axis by axis, as sweep_knn_kernel has it)
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const float blo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[a]), j));
+        const float bhi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[a]), j));
+        const float gap = __builtin_fmaxf(__builtin_fmaxf(blo - p[a], p[a] - bhi), 0.f);
+        lbp = __builtin_fmaf(gap, gap, lbp);
+      }
+      const float wl = node_w[c];   // level 0 starts the node array: the smallest weight of leaf c
+      lbp = __builtin_fmaf(wl, wl, lbp);
+      if (__ballot(lbp * SAFE < __int_as_float(best)) == 0ull) continue;
+      ++n_leaf_eval;
+      const float* cp = pts + c * (int64_t)LEAF * DP;
+      const float* cw = w_sorted + c * (int64_t)LEAF;
+      constexpr int NB = DP == 8 ? 4 : 8;   // rows in SGPRs at a time (32 scalar registers at most) and their weights
+      // (8-float rows: not unrolled - unrolled, DIM 5..8 take 82..119 vector registers instead of 62..87 and lose one
+      // to two waves per SIMD; 2- and 4-float rows: both halves of the leaf in flight, fewer scalar registers moved
+      // to vector lanes - profiles/power_kernel_resources.txt)
+      constexpr int UNROLL = DP == 8 ? 1 : LEAF / NB;
+#pragma unroll UNROLL
+      for (int h = 0; h < LEAF; h += NB) {
+        typename RowVec<DP>::type cc[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) cc[u] = load_uniform_row<DP>(cp + (h + u) * DP);
+        const typename RowVec<NB>::type ww = load_uniform_row<NB>(cw + h);
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          float d;  // (dist2 of flood_bvh.hpp written out, then the weight)
+#pragma unroll
+          for (int a = 0; a < DIM; ++a) {
+            const float t = p[a] - cc[u][a];
+            d = a == 0 ? t * t : __builtin_fmaf(t, t, d);
+          }
+          d = __builtin_fmaf(ww[u], ww[u], d);
+          const int di = __float_as_int(d);
+          best = di < best ? di : best;
+        }
+      }
+      M = wave_max_f32(__int_as_float(best));
+    }
+
+    if (live) out_bits[s * (int64_t)R + r] = (uint32_t)best;
+    const unsigned long long item_tests = n_leaf_test + n_node_test - tests_before;
+    max_item_tests = item_tests > max_item_tests ? item_tests : max_item_tests;
+  }
+  if (stats && lane == 0 && (n_node_test | n_leaf_test) != 0ull) {
+    atomicMax(&stats[3], max_item_tests);
+    atomicAdd(&stats[0], n_leaf_eval);
+    atomicAdd(&stats[1], n_leaf_test);
+    atomicAdd(&stats[2], n_node_test);
+  }
+}
+
+template <int DIM>
+struct PowerLaunch {
+  static int run(const flooder_knn_sorted_t& a, const float* w_sorted, const float* node_w, const Levels& lv,
+                 hipStream_t st) {
+    if constexpr (DIM < 2) {
+      return fail(FLOODER_E_ARG, "dim must be in 2..8");
+    } else {
+      const int64_t n_items = a.sample_order ? (a.n_simplices * (int64_t)a.R + 63) / 64
+                                             : a.n_simplices * ((a.R + 63) / 64);
+      int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
+      if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+      hipLaunchKernelGGL((sweep_power_kernel<DIM>), dim3((unsigned)grid), dim3(256), 0, st, a.pts_sorted, a.nodes, lv,
+                         a.verts, a.weights, a.k1, a.R, a.n_simplices, a.queue, a.out_bits,
+                         reinterpret_cast<unsigned long long*>(a.stats),
+                         reinterpret_cast<const uint32_t*>(a.sample_order), w_sorted, node_w);
+      return check_launch("sweep_power");
+    }
+  }
+};
+
+}  // namespace
+
+extern "C" int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream) {
+  if (!leaf_vals || !node_min || n_pts < 1)
+    return fail(FLOODER_E_ARG, "flooder_node_min_f32: bad argument (null pointer, n_pts < 1)");
+  const Levels lv = make_levels(n_pts);
+  hipStream_t st = (hipStream_t)stream;
+  for (int l = 0; l < lv.n_levels; ++l) {
+    const int64_t padded = (lv.count[l] + FAN - 1) / FAN * FAN;
+    float* out = node_min + lv.off[l];
+    if (l == 0)
+      hipLaunchKernelGGL(node_min_leaf_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, leaf_vals,
+                         lv.count[0], padded, out);
+    else
+      hipLaunchKernelGGL(node_min_inner_kernel, dim3((unsigned)((padded + 3) / 4)), dim3(256), 0, st,
+                         node_min + lv.off[l - 1], lv.count[l], padded, out);
+  }
+  return check_launch("node_min");
+}
+
+extern "C" int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const float* w_sorted, const float* node_w,
+                                       void* stream) {
+  static const char* who = "flooder_sweep_power_f32";
+  flooder_knn_sorted_t a;
+  if (int rc = take(p, a, "flooder_sweep_power_f32: bad parameter block (abi / size)")) return rc;
+  if (int rc = knn_check_ranges(who, a.k, 1, a.dim, a.stat, a.n_pts, false, false)) return rc;
+  if (a.stat != 0 || a.reserved != 0) return failf(FLOODER_E_ARG, "%s: stat and reserved must be 0", who);
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || !w_sorted || !node_w ||
+      a.n_pts < 1 || a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return failf(FLOODER_E_ARG, "%s: bad argument (null pointer, no points, k1, R)", who);
+  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
+    return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
+  return dispatch_dim<PowerLaunch>(a.dim, a, w_sorted, node_w, make_levels(a.n_pts), (hipStream_t)stream);
+}

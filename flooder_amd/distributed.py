@@ -194,10 +194,20 @@ def flood_complex_sharded(points: torch.Tensor, landmarks: torch.Tensor, *args, 
 
     ``neighbor_mass`` (the robust filtration by mass, up to 1024 neighbours) is forwarded by ``mode="simplices"``;
     ``mode="points"`` and ``mode="blocks"`` refuse it: a mass is a share of the whole cloud, which a shard does not
-    know."""
+    know.
+
+    ``point_weights`` (the weighted filtration) is forwarded by ``mode="simplices"`` (the full cloud's weights on every
+    rank) and by ``mode="points"``, where the caller passes the weights of ITS shard, cut by the rule of
+    ``shard_points`` (``shard_points(w, rank, world)``): the MIN of the shards' minima is exact, the minimum over a
+    union being the minimum of the minima.  ``mode="blocks"`` raises ``flood_complex``'s refusal of ``shard_blocks``
+    (a block's bounding balls bound the nearest point, not the power-nearest)."""
     if not isinstance(landmarks, torch.Tensor):
         raise TypeError("flood_complex_sharded needs explicit landmark coordinates (identical on every "
                         "rank); run generate_landmarks on the full cloud first")
+    if kwargs.get("point_weights") is not None and mode == "blocks":
+        from .core import _POWER_REFUSALS
+
+        raise ValueError(_POWER_REFUSALS["shard_blocks"])
     num_rand = kwargs.get("num_rand", args[2] if len(args) > 2 else None)
     if num_rand is not None:
         sync_cpu_rng(points.device, group, always=always_reduce)

@@ -195,6 +195,61 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
     return (value, *_neighbor_pair(points, ids, dist, squared)) if return_neighbors else value
 
 
+def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: Optional[torch.Tensor] = None, *,
+                   squared: bool = False, index: Optional[core.PointIndex] = None) -> torch.Tensor:
+    """Per query the power distance sqrt(min_x |q - x|^2 + w_x^2) to the weighted cloud -> (Q,) tensor of ``points``'
+    dtype on its device: the function whose sublevel sets ``flood_complex(points, landmarks, point_weights=w)``
+    filters (its vertex values are ``power_distance(points, w, landmarks)``, bit for bit on ROCm tensors).
+
+    ``point_weights``: (N,) of the points' dtype and device, one weight per point; it enters squared, so its sign does
+    not matter.  With ``w = distance_to_measure(points, mass=m)`` this is the witnessed k-distance, an approximation of
+    the distance to the measure from N numbers.  ``queries`` (None: the cloud's own points), ``index`` and the checks on
+    them are those of ``neighbor_distance``; ``squared=True`` returns the value before the root; Q = 0 gives an empty
+    tensor.
+
+    ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_sweep_power_f32`` in its query form (k1 = R = 1, sorted
+    query keys as ``neighbor_distance``); the weights must be finite (not checked on the device).  CPU tensors
+    (float32, float64; any dimension) query scipy's kd-tree over the lifted cloud ``[points, |w|]`` with ``[q, 0]`` and
+    refuse non-finite weights.  Not differentiable: inputs that require grad are used detached.
+    """
+    on_gpu = _check_points(points, "power_distance")
+    core._check_point_weights(points, point_weights, None)
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    points, point_weights, queries = points.detach(), point_weights.detach(), queries.detach()
+    Q = queries.shape[0]
+    if Q == 0:
+        return torch.empty(0, dtype=points.dtype, device=points.device)
+    if not on_gpu:
+        from scipy.spatial import KDTree
+
+        lifted = np.concatenate([np.asarray(points), np.asarray(point_weights.abs())[:, None]], axis=1)
+        q = np.concatenate([np.asarray(queries), np.zeros((Q, 1), dtype=lifted.dtype)], axis=1)
+        dist, _ = KDTree(lifted).query(q, workers=core.CPU_WORKERS)
+        dist = np.asarray(dist, dtype=np.float64).reshape(Q)
+        return torch.as_tensor(np.square(dist) if squared else dist).to(points.dtype)
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    w_sorted, node_w = core._power_weights(index, point_weights)
+    q = queries.contiguous()
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    bits = torch.empty(Q, dtype=torch.int32, device=dev)
+    key_bits = int(lib.flooder_sample_key_bits(q.shape[1]))
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // 24, (1 << 32) - 3))   # as _query_sweep_hip
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
+        queue, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnSorted(k=1, stat=0, sample_order=order, queue=queue, out_bits=bits[a:b],
+                                **core._knn_block_fields(index, verts, one))
+        _native.check(lib.flooder_sweep_power_f32(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w), st),
+                      "flooder_sweep_power_f32")
+    return _root_of_bits(lib, bits, squared, st)
+
+
 def _no_neighbors(points: torch.Tensor, k: int):
     """(ids, dist) of no queries."""
     return (torch.empty((0, k), dtype=torch.int64, device=points.device),

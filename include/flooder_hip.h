@@ -1101,6 +1101,41 @@ typedef struct flooder_knn_wide_s {         /* flooder_knn_wide_f32 */
 } flooder_knn_wide_t;
 int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream);
 
+/*
+ * ---- Weighted filtration: the power distance (csrc/flood_power.hip; flood_complex(point_weights=w)) ----------------
+ * Every point x carries a weight w_x >= 0 and a sample p is measured by f(p)^2 = min_x ( |p - x|^2 + w_x^2 ).
+ *
+ * flooder_node_min_f32: the minimum of one value per tree row over every node of the box tree.
+ *   leaf_vals  (n_pad,) values in tree-row order, n_pad = n_pts rounded up to FLOODER_BVH_LEAF; the rows of the padded
+ *              last leaf hold +inf.
+ *   node_min   flooder_bvh_node_count of n_pts floats in the layout of PointIndex.nodes: leaves first, then one level
+ *              per factor FLOODER_BVH_FANOUT, every level padded to a multiple of 64 slots.  Level 0 = the minimum over a
+ *              leaf's 16 rows, level l = the minimum over the up-to-64 children; padding slots receive +inf.
+ * One launch per level, plain vector stores, no atomics.  Refused: a NULL pointer, n_pts < 1.
+ *
+ * flooder_sweep_power_f32: the tree sweep of flooder_sweep_knn_sorted_f32 at k = 1 with the word of a pair
+ *     fmaf(w, w, d2),   d2 = t0*t0, then fma(t, t, d2) per further axis (t = p - x), w the weight ITSELF (not w^2),
+ * and out_bits[s, r] = the float32 bits of the minimum of that word over ALL n_pts points (squared, non-negative:
+ * integer order == value order; flooder_face_max_f32 takes the roots and the face maxima unchanged).  The block is
+ * that of the sorted k-nearest sweep: k must be 1, stat 0, reserved 0; sample_order NULL = the identity order
+ * g = 0 .. N - 1, cut into tiles simplex by simplex (64 consecutive rows of one simplex share a wave, as in
+ * flooder_sweep_knn_f32), else any permutation of it in tiles of 64 consecutive entries (a performance input only:
+ * the same words).
+ *   w_sorted   (n_pad,) |w| in tree-row order (w gathered by PointIndex.order32), pad rows +inf;
+ *   node_w     flooder_node_min_f32 of w_sorted.
+ * A child of the walk is worth fmaf(node_w[c], node_w[c], gap2 of its box to the tile's box), a leaf against a lane's
+ * own sample fmaf(node_w[leaf], node_w[leaf], gap2 of the sample to its box): lower bounds of every pair word below
+ * the node, culled only when !(lb * SAFE < bound) as in every tree sweep - so the words do not depend on the tree, on
+ * the order or on which samples share a wave.  Zero weights give the words of the k = 1 sweeps.  Weights must be
+ * finite (not checked).  queue: FLOODER_QUEUE_WORDS zeroed int32; stats as flooder_sweep_knn_f32.
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), before a pointer is read: a bad block size or
+ * abi; k != 1; dim outside 2..8; stat != 0; reserved != 0.  Then n_simplices == 0 or R == 0: FLOODER_OK, nothing is
+ * touched.  Then: a NULL pointer (w_sorted and node_w included; sample_order and stats may be NULL), n_pts < 1, k1,
+ * n_simplices * R >= 2^32 - 2.
+ */
+int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream);
+int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const float* w_sorted, const float* node_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
