@@ -10,9 +10,9 @@ from .core import (flood_complex, generate_landmarks, generate_grid, generate_un
                    index_from_host, forget_index)
 from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
-from .grad import FloodFiltration, flood_filtration
+from .grad import FloodFiltration, flood_filtration, power_filtration
 from .profile import FloodProfile, flood_profile
-from .neighbors import neighbor_distance, nearest_neighbors, distance_to_measure, power_distance
+from .neighbors import neighbor_distance, nearest_neighbors, distance_to_measure, power_distance, power_nearest
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -25,6 +25,7 @@ __version__ = "0.1"
 __all__ = [
     "flood_complex",
     "flood_filtration",
+    "power_filtration",
     "FloodFiltration",
     "flood_profile",
     "FloodProfile",
@@ -32,6 +33,7 @@ __all__ = [
     "nearest_neighbors",
     "distance_to_measure",
     "power_distance",
+    "power_nearest",
     "generate_landmarks",
     "generate_grid",
     "generate_uniform_weights",

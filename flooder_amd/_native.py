@@ -275,6 +275,8 @@ SIGNATURES = {
     # the power-distance sweep on the block of the sorted k-nearest sweep (k = 1) plus the weights and their node minima
     "flooder_node_min_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "flooder_sweep_power_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p, c_void_p, c_void_p]),
+    # ... and which point attains a power word: the witness search's block plus the same two pointers (power_filtration)
+    "flooder_witness_power": (c_int, [ctypes.POINTER(WitnessSearch), c_void_p, c_void_p, c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -1709,19 +1709,23 @@ def _sweep_dimension_power(index: PointIndex, verts: torch.Tensor, weights: torc
                            w_sorted: torch.Tensor, node_w: torch.Tensor,
                            reduce_hook: Optional[Callable[[torch.Tensor], None]] = None,
                            plan: Optional["SamplePlan"] = None, timer: Optional[_KernelTimer] = None,
-                           stats: Optional[torch.Tensor] = None):
+                           stats: Optional[torch.Tensor] = None, keep=None):
     """All simplices of one dimension against an indexed WEIGHTED point set -> (S, F) face maxima of the power distance
     sqrt(min_x |p - x|^2 + w_x^2).  ``w_sorted``, ``node_w``: ``_power_weights`` of the call.
 
     sweep_power (plain stores of the squared minimum's bits into the (S, R) buffer, samples in the order of
     ``sample_order`` as in ``_sweep_dimension_bvh``; over tiles of the sorted sample order where ``knn_sorts_samples``
     says so, else in the identity order, a simplex's rows per tile: the same words) -> [reduce_hook: cross-shard MIN,
-    exact here - the minimum over a union is the minimum of the minima] -> face max + sqrt.  No host synchronisation."""
+    exact here - the minimum over a union is the minimum of the minima] -> face max + sqrt.  No host synchronisation.
+    ``keep``: a callable that is handed the (S, R) int32 buffer (columns in swept order) - ``power_filtration`` finds its
+    witnesses there."""
     lib = _native.load()
     dev = index.pts.device
     st = _native.current_stream_ptr(dev)
     S, R = verts.shape[0], weights.shape[0]
     if S == 0:
+        if keep is not None:
+            keep(torch.empty((0, R), dtype=torch.int32, device=dev))
         return _no_simplices(faces, R, dev, False)
     verts = verts.to(torch.float32).contiguous()
     plan = plan if plan is not None else SamplePlan(weights, faces)
@@ -1735,7 +1739,10 @@ def _sweep_dimension_power(index: PointIndex, verts: torch.Tensor, weights: torc
                                 **_knn_block_fields(index, verts, plan.w_perm))
         _native.check(lib.flooder_sweep_power_f32(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w), st),
                       "flooder_sweep_power_f32")
-    return _face_epilogue(lib, st, d2, faces, plan.rows_perm, reduce_hook=reduce_hook, timer=timer)
+    out = _face_epilogue(lib, st, d2, faces, plan.rows_perm, reduce_hook=reduce_hook, timer=timer)
+    if keep is not None:
+        keep(d2)
+    return out
 
 
 def _sweep_dimension_knn_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,

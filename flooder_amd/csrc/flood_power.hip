@@ -33,6 +33,19 @@
 //
 // flooder_node_min_f32 builds node_w: the minimum of a value per tree row over every node of the box tree, in the
 // layout of the node array (Levels), padding slots +inf.  One launch per level, plain vector stores, no atomics.
+//
+//   witness_power<DIM> WHICH point attains a power word (flooder_witness_power; power_filtration, power_nearest): one
+//                      wave per query, the LDS group stack of witness_search_kernel (flood_grad.hip).  The sample p* is
+//                      rebuilt with the sweeps' fma in vertex order; a node of level lvl, slot idx is opened iff
+//                          fmaf(nw, nw, box_gap2(p*, box)) * SAFE <= target,   nw = node_w[lv.off[lvl] + idx]
+//                      - the leaf bound above against the KNOWN minimum, non-strict: a box exactly at the target is
+//                      opened -, leaves are evaluated four at a time, one point per lane, with the word of the sweep,
+//                      fmaf(w, w, dist2(p*, x)), and the witness is the smallest original id whose word has exactly
+//                      the target bits.  Every pair word below a node is at least the node's bound within SAFE (Bounds),
+//                      so a skipped node holds no point at the target: the search is exhaustive over the points that
+//                      can match.  Padding rows (coordinates and weight +inf) never match and rw < n_pts guards them
+//                      as well.  Zero weights: fmaf(0, 0, x) = x in the bound and in the word - node for node and
+//                      point for point the tests of witness_search_kernel, the same outputs.
 
 #include "flood_common.hpp"
 #include "flood_bvh.hpp"
@@ -258,6 +271,131 @@ struct PowerLaunch {
   }
 };
 
+// One wave per query; the stack holds groups of 64 sibling nodes (level, group) as in witness_search_kernel
+// (flood_grad.hip: the pop, the push and the four-leaf step are its steps; keep in step).
+template <int DIM>
+__global__ __launch_bounds__(256) void witness_power_kernel(const float* __restrict__ pts, int64_t n_pts,
+                                                            const float* __restrict__ nodes, Levels lv,
+                                                            const int32_t* __restrict__ order,
+                                                            const float* __restrict__ verts,
+                                                            const float* __restrict__ weights, int k1, int R,
+                                                            int64_t n_simplices, int64_t n_queries,
+                                                            const int32_t* __restrict__ q_simplex,
+                                                            const int32_t* __restrict__ q_row,
+                                                            const uint32_t* __restrict__ q_word,
+                                                            int64_t* __restrict__ out_point,
+                                                            int32_t* __restrict__ not_found,
+                                                            const float* __restrict__ w_sorted,
+                                                            const float* __restrict__ node_w) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ int32_t s_stack[WAVES_PER_BLOCK][STACK];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
+  const int64_t n_waves = (int64_t)gridDim.x * WAVES_PER_BLOCK;
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int top = lv.n_levels - 1;
+  for (int64_t q = wave; q < n_queries; q += n_waves) {
+    const int64_t s = q_simplex[q];
+    const int64_t r = q_row[q];
+    const uint32_t target = q_word[q];
+    const float tf = __uint_as_float(target);
+    if (s < 0 || s >= n_simplices || r < 0 || r >= R) {   // (not a swept sample: no witness)
+      if (lane == 0) {
+        out_point[q] = -1;
+        atomicAdd(not_found, 1);
+      }
+      continue;
+    }
+    // p* exactly as the sweeps build a sample: p = 0; p[k] = fma(w_j, v_j[k], p[k]) in vertex order
+    float p[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) p[k] = 0.f;
+    const float* vs = verts + s * (int64_t)k1 * DIM;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[r * k1 + j];
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) p[k] = __builtin_fmaf(w, vs[j * DIM + k], p[k]);
+    }
+    uint32_t best = 0xffffffffu;
+    int sp = 1;
+    if (lane == 0) s_stack[wv][0] = top;   // (level top, group 0): the <= 64 top nodes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    while (sp > 0) {
+      --sp;
+      const int e = s_stack[wv][sp];
+      const int lvl = e & 7;
+      const int64_t grp = e >> 3;
+      const int64_t idx = grp * FAN + lane;
+      bool ok = false;
+      if (idx < lv.count[lvl]) {
+        float lo[DP], hi[DP];
+        const float* nb = nodes + (lv.off[lvl] + idx) * 2 * DP;
+        load_row<DP>(nb, lo);
+        load_row<DP>(nb + DP, hi);
+        const float nw = node_w[lv.off[lvl] + idx];   // the smallest weight below the node
+        ok = __builtin_fmaf(nw, nw, box_gap2<DIM>(p, lo, hi)) * SAFE <= tf;
+      }
+      unsigned long long mask = __ballot(ok);
+      __builtin_amdgcn_wave_barrier();   // (every lane has read the popped entry before a push may overwrite it)
+      if (lvl == 0) {
+        while (mask) {
+          int64_t leaf[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (mask) {
+              const int j = __builtin_ctzll(mask);
+              mask &= mask - 1;
+              leaf[u] = grp * FAN + j;
+            } else {
+              leaf[u] = -1;
+            }
+          }
+          const int u = lane >> 4;
+          const int64_t lf = u == 0 ? leaf[0] : (u == 1 ? leaf[1] : (u == 2 ? leaf[2] : leaf[3]));
+          const int64_t rw = lf * LEAF + (lane & 15);
+          if (lf >= 0 && rw < n_pts) {   // (rows of the padded last leaf are never candidates)
+            float x[DP];
+            load_row<DP>(pts + rw * DP, x);
+            const float w = w_sorted[rw];
+            const float word = __builtin_fmaf(w, w, dist2<DIM>(p, x));   // the word of sweep_power_kernel
+            if (__float_as_uint(word) == target) {
+              const uint32_t id = (uint32_t)order[rw];
+              best = id < best ? id : best;
+            }
+          }
+        }
+      } else {
+        if (ok) s_stack[wv][sp + __popcll(mask & below)] = (int)((idx << 3) | (lvl - 1));
+        sp += __popcll(mask);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+    best = wave_min_u32(best);
+    if (lane == 0) {
+      out_point[q] = best == 0xffffffffu ? -1 : (int64_t)best;
+      if (best == 0xffffffffu) atomicAdd(not_found, 1);
+    }
+  }
+}
+
+template <int DIM>
+struct WitnessPowerOp {
+  static int run(const flooder_witness_search_t& a, const float* w_sorted, const float* node_w, const Levels& lv,
+                 hipStream_t st) {
+    if constexpr (DIM < 2) {
+      return fail(FLOODER_E_ARG, "flooder_witness_power: dim must be in 2..8");
+    } else {
+      hipLaunchKernelGGL(witness_power_kernel<DIM>, stack_walk_grid(a.n_queries), dim3(64 * WAVES_PER_BLOCK), 0, st,
+                         a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, a.n_simplices,
+                         a.n_queries, a.q_simplex, a.q_row, a.q_d2, a.out_point, a.not_found, w_sorted, node_w);
+      return check_launch("witness_power");
+    }
+  }
+};
+
 }  // namespace
 
 extern "C" int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream) {
@@ -292,4 +430,18 @@ extern "C" int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const floa
   if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
     return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
   return dispatch_dim<PowerLaunch>(a.dim, a, w_sorted, node_w, make_levels(a.n_pts), (hipStream_t)stream);
+}
+
+extern "C" int flooder_witness_power(const flooder_witness_search_t* p, const float* w_sorted, const float* node_w,
+                                     void* stream) {
+  flooder_witness_search_t a;
+  if (int rc = take(p, a, "flooder_witness_power: bad parameter block (abi / size)")) return rc;
+  if (a.n_queries == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.order || !a.verts || !a.weights || !a.q_simplex || !a.q_row || !a.q_d2 ||
+      !a.out_point || !a.not_found || !w_sorted || !node_w || a.n_pts < 1 || a.k1 < 1 || a.R < 1 || a.n_queries < 0 ||
+      a.dim < 2 || a.dim > 8 || a.n_pts > 0x7fffffffLL)
+    return fail(FLOODER_E_ARG, "flooder_witness_power: bad argument");
+  Levels lv;
+  if (int rc = stack_walk_levels("flooder_witness_power", a.n_pts, lv)) return rc;
+  return dispatch_dim<WitnessPowerOp>(a.dim, a, w_sorted, node_w, lv, (hipStream_t)stream);
 }

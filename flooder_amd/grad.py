@@ -15,6 +15,10 @@ from the indices of the kd-tree query.  The values themselves are the ones ``flo
 id) - on ROCm tensors recovered exactly by ``flooder_witness_knn`` from the bits of the k-nearest sweep's statistic.
 ``"kth"``: f = |p* - x_(k)|, the formulas above at x_(k); ``"dtm"``: f = sqrt(mean_i |p* - x_(i)|^2),
 df/dpoints[id_(i)] = -(p* - x_(i)) / (k f), df/dL_j = w*_j (p* - mean x) / f.
+
+``power_filtration`` (the weighted filtration, ``flood_complex(point_weights=w)``): f = sqrt(|p* - x*|^2 + w*^2) with x*
+the POWER-nearest point of p* - on ROCm tensors recovered exactly by ``flooder_witness_power`` from the bits of the
+power-distance sweep -, u = (p* - x*) / f: df/dpoints[j*] = -u, df/dL_i = w*_i u, df/dpoint_weights[j*] = w_j* / f.
 """
 
 from __future__ import annotations
@@ -32,11 +36,11 @@ from . import core
 from .persistence import persistence_pairs_simplices
 from .simplex_tree import SimplexTree, delaunay_cells
 
-__all__ = ["FloodFiltration", "flood_filtration"]
+__all__ = ["FloodFiltration", "flood_filtration", "power_filtration"]
 
 
 class FloodFiltration:
-    """Result of ``flood_filtration``: per dimension d (lists indexed by d)
+    """Result of ``flood_filtration`` and ``power_filtration``: per dimension d (lists indexed by d)
 
     ``simplices[d]``        (n_d, d+1) int64 CPU: the rows of ``tree.simplices_of_dimension(d)`` (vertex ids ascending)
     ``values[d]``           (n_d,) on the points' device and dtype, differentiable w.r.t. points and landmarks
@@ -45,11 +49,14 @@ class FloodFiltration:
     ``witness_neighbors[d]`` (n_d, k) int64: the ``neighbors`` = k nearest points of the witness sample, ascending by
                             (distance, id) (-1: none); its last column is ``witness_point[d]``, the k-th nearest
     ``neighbors``, ``neighbor_stat``  the robust filtration's arguments (1, "kth": the plain filtration)
+    ``point_weights``       the weighted filtration's (N,) tensor (``power_filtration``: ``witness_point`` is then the
+                            POWER-nearest point of the witness sample); None from every other producer
     ``tree``                the ``flooder_amd.SimplexTree`` with the (detached) values
     """
 
     def __init__(self, tree: SimplexTree, simplices, values, witness_point, witness_weights, landmark_ids,
-                 faces_not_found: int = 0, witness_neighbors=None, neighbors: int = 1, neighbor_stat: str = "kth"):
+                 faces_not_found: int = 0, witness_neighbors=None, neighbors: int = 1, neighbor_stat: str = "kth",
+                 point_weights: Optional[torch.Tensor] = None):
         self.tree = tree
         self.simplices: List[torch.Tensor] = simplices
         self.values: List[torch.Tensor] = values
@@ -61,6 +68,7 @@ class FloodFiltration:
                                                       else [p.unsqueeze(1) for p in witness_point])
         self.neighbors = neighbors
         self.neighbor_stat = neighbor_stat
+        self.point_weights = point_weights
 
     def to_dict(self) -> Dict[tuple, float]:
         """``{simplex: value}``, what ``flood_complex`` returns for the same arguments."""
@@ -138,6 +146,41 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
     the argument, whichever statistic is named."""
     neighbors, method = core._check_neighbors(points, neighbors, neighbor_stat, method)
     method = _check_args(points, method)
+    return _filtration(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx, method, index, neighbors,
+                       neighbor_stat)
+
+
+def power_filtration(points: torch.Tensor, landmarks, point_weights: torch.Tensor, max_dimension: Optional[int] = None,
+                     points_per_edge: int = 30, num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *,
+                     method: Optional[str] = None, index: Optional["core.PointIndex"] = None) -> FloodFiltration:
+    """Weighted Flood filtration with exact witnesses: the values of ``flood_complex(points, landmarks, max_dimension,
+    points_per_edge, num_rand, start_idx=start_idx, method=method, index=index, point_weights=point_weights)``,
+    differentiable w.r.t. ``points``, ``landmarks`` AND ``point_weights``.  With ``point_weights =
+    neighbor_distance(points, neighbors=k, neighbor_stat="dtm")`` (differentiable itself) the robust filtration of the
+    literature sits in a loss end to end at the cost of a k = 1 sweep.
+
+    The arguments are judged as ``flood_complex(point_weights=...)`` judges them, with the same messages
+    (``core._check_point_weights``): ``method`` None / "auto" / "bvh"; CPU tensors (float32, float64, any dimension) and
+    ROCm float32 in ambient dimension 2 to 8.  Integer ``landmarks``: farthest-point sampling as ``flood_filtration``
+    does it (their gradient flows into ``points``).
+
+    The witness of a value is the sample p* with the largest power distance (among equal ones the smallest sample row)
+    and j* = ``witness_point``, the point that attains min_x |p* - x|^2 + w_x^2.  With f = sqrt(|p* - x*|^2 + w*^2) and
+    u = (p* - x*) / f: df/dpoints[j*] = -u, df/dL_i = lambda_i u over the barycentric weights of p*,
+    df/dpoint_weights[j*] = w_j* / f with the caller's signed weight; all 0 where f = 0.  On ROCm tensors j* is the
+    smallest id among the points whose word fmaf(w, w, d2), in the sweep's float32 arithmetic, has the bits of the
+    minimum (``flooder_witness_power``), and the three gradients are summed in a fixed order: bit-identical run to run.
+    On CPU tensors j* is the index scipy's kd-tree over the lifted cloud ``[points, |w|]`` returns for ``[p*, 0]``: which of
+    several tied points is scipy's choice."""
+    method = core._check_point_weights(points, point_weights, method)
+    method = _check_args(points, method)
+    return _filtration(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx, method, index, 1, "kth",
+                       point_weights)
+
+
+def _filtration(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx, method, index, neighbors,
+                neighbor_stat, point_weights=None) -> FloodFiltration:
+    """The checked call of ``flood_filtration`` (``point_weights`` None) or ``power_filtration``."""
     if index is not None:
         core._check_index(index, points, points.is_cuda, "ROCm tensors")
     dim = points.shape[1]
@@ -174,9 +217,9 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
         not_found = 0
         if points.is_cuda:
             not_found = _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, index,
-                                   own_val, own_pt, own_w, knn)
+                                   own_val, own_pt, own_w, knn, point_weights)
         else:
-            _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn)
+            _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn, point_weights)
         for d in range(n_dims):
             vals = tree.filtrations_of_dimension(d)
             if vals.shape[0]:
@@ -190,13 +233,16 @@ def flood_filtration(points: torch.Tensor, landmarks, max_dimension: Optional[in
     F = FloodFiltration(tree, [torch.as_tensor(s) for s in simplices], None,
                         [torch.as_tensor(p).to(dev) for p in wp], [torch.as_tensor(w, dtype=dt).to(dev) for w in ww],
                         landmark_ids, not_found, None if wn is None else [torch.as_tensor(n).to(dev) for n in wn],
-                        neighbors, neighbor_stat)
+                        neighbors, neighbor_stat, point_weights)
     # (the context keeps the witness tensors, not F: F holds the outputs of this very node - a cycle through autograd's
     # C++ graph that the garbage collector cannot break)
     witnesses = (F.simplices, F.witness_point, F.witness_weights)
     if neighbors > 1 and neighbor_stat == "dtm":    # ("kth": the gradient sits at witness_point, the k-th nearest)
         witnesses += (F.witness_neighbors,)
-    flat = _FloodValues.apply(points, landmarks, torch.cat(vals_t), witnesses)
+    if point_weights is not None:
+        flat = _PowerValues.apply(points, landmarks, point_weights, torch.cat(vals_t), witnesses)
+    else:
+        flat = _FloodValues.apply(points, landmarks, torch.cat(vals_t), witnesses)
     F.values = list(torch.split(flat, [v.shape[0] for v in vals_t]))
     return F
 
@@ -246,7 +292,8 @@ def _grad_face_rows(plan: "core.SamplePlan"):
     return got
 
 
-def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, index, own_val, own_pt, own_w, knn=None):
+def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, index, own_val, own_pt, own_w, knn=None,
+               point_weights=None):
     lib = _native.load()
     dev = pts.device
     torch.cuda.set_device(dev)
@@ -257,6 +304,8 @@ def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, ind
     axis = core._widest_axis(pts, index.box)
     st = _native.current_stream_ptr(dev)
     not_found = torch.zeros(1, dtype=torch.int32, device=dev)
+    if point_weights is not None:   # the weights in tree-row order and their node minima, once per call
+        w_sorted, node_w = core._power_weights(index, point_weights)
     for p in core._dimension_passes(simplices, lms.to(torch.float32), axis, points_per_edge, num_rand, "tree"):
         d, sv, weights, faces = p.d, p.verts, p.weights, p.faces
         plan = p.plan if p.plan is not None else core.SamplePlan(weights, faces)   # (random samples: the gather below needs it)
@@ -264,6 +313,9 @@ def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, ind
         got = []
         if knn is not None:    # (S, R) bits of the squared statistic instead of the minimum d2
             face_dev, _ = core._sweep_dimension_knn(index, sv, weights, faces, knn[0], knn[1], plan=plan, keep=got.append)
+        elif point_weights is not None:    # (S, R) bits of the squared power distance
+            face_dev, _ = core._sweep_dimension_power(index, sv, weights, faces, w_sorted, node_w, plan=plan,
+                                                      keep=got.append)
         else:
             sweep = core._sweep_dimension_cell if method == "cell" else core._sweep_dimension_bvh
             face_dev, _ = sweep(index, sv, weights, faces, got.append, plan=plan)
@@ -315,7 +367,11 @@ def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, ind
                 blk = _native.WitnessSearch(pts_sorted=index.pts, n_pts=index.n, dim=dim, k1=d + 1, nodes=index.nodes,
                                             order=index.order32, verts=sv, weights=plan.w_perm, R=R, n_simplices=S, n_queries=n_q,
                                             q_simplex=q_s, q_row=q_r, q_d2=q_b, out_point=out_pt, not_found=not_found)
-                _native.check(lib.flooder_witness_search(ctypes.byref(blk), st), "flooder_witness_search")
+                if point_weights is not None:
+                    _native.check(lib.flooder_witness_power(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w),
+                                                            st), "flooder_witness_power")
+                else:
+                    _native.check(lib.flooder_witness_search(ctypes.byref(blk), st), "flooder_witness_search")
             own_val[k - 1][cov] = val[win].cpu().numpy().astype(np.float64)
             own_pt[k - 1][cov] = out_pt.cpu().numpy()
             w_full = plan.w_perm[r_q.clamp(min=0)]           # (n_q, d+1) over the swept simplex's vertices
@@ -323,18 +379,23 @@ def _sweep_gpu(pts, lms, tree, simplices, points_per_edge, num_rand, method, ind
             own_w[k - 1][cov] = torch.gather(w_full, 1, vi).cpu().numpy().astype(np.float64)
     missing = int(not_found.item())
     if missing:
-        raise RuntimeError(f"flood_filtration: the witness search found no point at the exact distance for "
-                           f"{missing} faces")
+        who = "flood_filtration" if point_weights is None else "power_filtration"
+        raise RuntimeError(f"{who}: the witness search found no point at the exact distance for {missing} faces")
     return missing
 
 
-def _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn=None):
+def _sweep_cpu(pts, lms, tree, simplices, points_per_edge, num_rand, own_val, own_pt, own_w, knn=None,
+               point_weights=None):
     from scipy.spatial import KDTree
 
-    kdtree = KDTree(np.asarray(pts))
+    # (weighted: |p - x|^2 + w_x^2 is the squared distance from (p, 0) to the lifted point (x, |w_x|), as flood_complex)
+    kdtree = KDTree(np.asarray(pts) if point_weights is None
+                    else np.concatenate([np.asarray(pts), np.asarray(point_weights.detach().abs())[:, None]], axis=1))
     for p in core._dimension_passes(simplices, lms, core._widest_axis(pts), points_per_edge, num_rand, "ball"):
         weights, faces, S = p.weights, p.faces, p.verts.shape[0]
         samples = weights.unsqueeze(0) @ p.verts
+        if point_weights is not None:   # the lifted samples (p, 0)
+            samples = torch.cat([samples, samples.new_zeros(samples.shape[:-1] + (1,))], dim=-1)
         if knn is not None:
             dist_k, idx_k = kdtree.query(np.asarray(samples), k=knn[0], workers=core.CPU_WORKERS)   # (S, R, k), ascending
             dist = core._robust_stat(dist_k, knn[0], knn[1])
@@ -439,6 +500,21 @@ class _FloodValues(torch.autograd.Function):
         return (gp if ctx.needs_input_grad[0] else None), (gl if ctx.needs_input_grad[1] else None), None, None
 
 
+class _PowerValues(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, landmarks, point_weights, values, witnesses):
+        ctx.witnesses = witnesses
+        ctx.save_for_backward(points, landmarks, point_weights)
+        return values.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        points, landmarks, point_weights = ctx.saved_tensors
+        got = power_witness_backward(*ctx.witnesses, points.detach(), landmarks.detach(), point_weights.detach(), grad)
+        return tuple(g if need else None for g, need in zip(got, ctx.needs_input_grad)) + (None, None)
+
+
 def witness_backward(simplices, witness_point, witness_weights, points: torch.Tensor, landmarks: torch.Tensor,
                      grad: torch.Tensor, witness_neighbors=None):
     """(grad_points (n, dim), grad_landmarks (L, dim)) of sum(grad * values), in the input dtype.  ROCm tensors: the
@@ -446,9 +522,24 @@ def witness_backward(simplices, witness_point, witness_weights, points: torch.Te
     ``witness_neighbors`` (per dimension (n_d, k)): the values are distances to the empirical measure of those k
     points, f = sqrt(mean_i |p* - x_(i)|^2); without it f = |p* - points[witness_point]| (the nearest point, or the
     k-th nearest of the k-distance)."""
+    return _witness_backward(simplices, witness_point, witness_weights, points, landmarks, grad, witness_neighbors)[:2]
+
+
+def power_witness_backward(simplices, witness_point, witness_weights, points: torch.Tensor, landmarks: torch.Tensor,
+                           point_weights: torch.Tensor, grad: torch.Tensor):
+    """``witness_backward`` of the weighted filtration -> (grad_points (n, dim), grad_landmarks (L, dim),
+    grad_point_weights (n,)): f = sqrt(|p* - x*|^2 + w*^2) at x* = points[witness_point], the power-nearest point,
+    u = (p* - x*) / f; a value adds -g u to row j* of the points, g lambda_i u to landmark i and g w_j* / f to weight j*
+    (the caller's signed weight: d(w^2)/dw = 2 w); nothing where f = 0.  ROCm tensors: all three summed in a fixed order."""
+    return _witness_backward(simplices, witness_point, witness_weights, points, landmarks, grad, None, point_weights)
+
+
+def _witness_backward(simplices, witness_point, witness_weights, points, landmarks, grad, witness_neighbors=None,
+                      point_weights=None):
+    """(grad_points, grad_landmarks, grad_point_weights or None): the body of the two functions above."""
     dev, dt = points.device, points.dtype
     dim = points.shape[1]
-    tg_p, vl_p, tg_l, vl_l = [], [], [], []
+    tg_p, vl_p, tg_l, vl_l, vl_w = [], [], [], [], []
     off = 0
     for d, simp in enumerate(simplices):
         n = simp.shape[0]
@@ -480,6 +571,12 @@ def witness_backward(simplices, witness_point, witness_weights, points: torch.Te
         else:
             diff = p - points[jp]
             f = diff.norm(dim=1, keepdim=True)
+            if point_weights is not None:
+                # (where w = 0 f stays the norm itself, not the root of its square: the plain filtration's bits)
+                wj = point_weights[jp].unsqueeze(1)
+                f = torch.where(wj == 0, f, torch.sqrt(f * f + wj * wj))
+                vl_w.append(torch.where(f > 0, g.unsqueeze(1) * wj / torch.where(f > 0, f, torch.ones_like(f)),
+                                        torch.zeros_like(f)))
             u = torch.where(f > 0, diff / torch.where(f > 0, f, torch.ones_like(f)), torch.zeros_like(diff))
             gu = g.unsqueeze(1) * u
             tg_p.append(jp)
@@ -490,7 +587,8 @@ def witness_backward(simplices, witness_point, witness_weights, points: torch.Te
         vl_l.append(W[rows_i, cols_i].unsqueeze(1) * gu[rows_i])
     gp = _scatter_rows(tg_p, vl_p, points.shape[0], dim, dev, dt)
     gl = _scatter_rows(tg_l, vl_l, landmarks.shape[0], dim, dev, dt)
-    return gp, gl
+    gw = None if point_weights is None else _scatter_rows(tg_p, vl_w, points.shape[0], 1, dev, dt).reshape(-1)
+    return gp, gl, gw
 
 
 def _scatter_rows(targets, vals, n_out: int, dim: int, dev, dt) -> torch.Tensor:

@@ -8,6 +8,10 @@ tiles (``flooder_sweep_knn_sorted_f32`` in its query form: every query is a "sim
 ``nearest_neighbors`` says WHICH points those k are (``flooder_knn_ids_sorted_f32``: the same sweep keeping (d2 word,
 original id) keys), and with them ``neighbor_distance`` is differentiable in the cloud and in the queries.
 
+``power_distance`` is the weighted filtration's function, min_x |q - x|^2 + w_x^2, ``power_nearest`` says WHICH point
+attains it (``flooder_witness_power``), and with it ``power_distance`` is differentiable in the cloud, the weights and
+the queries.
+
 ``distance_to_measure`` speaks in MASS (k = mass * N, up to 1024 neighbours): ``flooder_knn_wide_f32``, one wave per query
 with its k best in LDS, values and neighbours without gradients.
 """
@@ -210,23 +214,60 @@ def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: O
     ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_sweep_power_f32`` in its query form (k1 = R = 1, sorted
     query keys as ``neighbor_distance``); the weights must be finite (not checked on the device).  CPU tensors
     (float32, float64; any dimension) query scipy's kd-tree over the lifted cloud ``[points, |w|]`` with ``[q, 0]`` and
-    refuse non-finite weights.  Not differentiable: inputs that require grad are used detached.
+    refuse non-finite weights.
+
+    Differentiable: when ``points``, ``point_weights`` or ``queries`` requires grad (and grad mode is on) the result
+    carries a ``grad_fn``.  With f the value, x* = points[j*] the power-nearest point of a query q (``power_nearest``)
+    and w* its weight: df/dq = (q - x*) / f, the negative goes to x*, df/dw* = w* / f with the caller's signed weight;
+    ``squared=True`` has 2 in place of 1 / f; the gradient is 0 where f is 0; with ``queries=None`` both roles
+    accumulate into ``points.grad``.  The values are bit for bit those of the call without grad and the backward on
+    ROCm tensors is bit-identical run to run.  Without grad nothing changes: no witness is searched.
     """
+    own = queries is None
     on_gpu = _check_points(points, "power_distance")
     core._check_point_weights(points, point_weights, None)
     queries = _check_queries_and_index(points, queries, index, on_gpu)
+    if queries.shape[0] == 0:
+        return torch.empty(0, dtype=points.dtype, device=points.device)
+    if torch.is_grad_enabled() and (points.requires_grad or point_weights.requires_grad or queries.requires_grad):
+        return _PowerDistance.apply(points, point_weights, None if own else queries, bool(squared), index)
+    return _power_query(points, point_weights, queries, index, squared, False)[1]
+
+
+def power_nearest(points: torch.Tensor, point_weights: torch.Tensor, queries: Optional[torch.Tensor] = None, *,
+                  index: Optional[core.PointIndex] = None):
+    """The power-nearest point of the weighted cloud per query -> (``ids`` (Q,) int64: the row of ``points`` that
+    attains min_x |q - x|^2 + w_x^2, ``dist`` (Q,) of ``points``' dtype: ``power_distance(points, point_weights,
+    queries)``, bit for bit), both on the device of ``points``.  Arguments and checks as ``power_distance``; Q = 0
+    gives empty tensors.
+
+    ROCm tensors: the query-form sweep of ``power_distance`` for the bits of the minimum, then
+    ``flooder_witness_power`` in the same groups of queries - exact in the sweep's float32 arithmetic, among points
+    whose word fmaf(w, w, d2) has the minimum's bits the smallest id, the rule of ``power_filtration``'s witnesses (its
+    vertex witnesses are ``power_nearest(points, w, landmarks)[0]``).  CPU tensors: the index scipy's kd-tree over the
+    lifted cloud returns; which of several tied points is scipy's choice."""
+    on_gpu = _check_points(points, "power_distance")
+    core._check_point_weights(points, point_weights, None)
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    if queries.shape[0] == 0:
+        return (torch.empty(0, dtype=torch.int64, device=points.device),
+                torch.empty(0, dtype=points.dtype, device=points.device))
+    return _power_query(points, point_weights, queries, index, False, True)
+
+
+def _power_query(points, point_weights, queries, index, squared: bool, want_ids: bool):
+    """(ids (Q,) int64 or None, the power distance (Q,), squared with ``squared``) of Q > 0 checked queries."""
     points, point_weights, queries = points.detach(), point_weights.detach(), queries.detach()
     Q = queries.shape[0]
-    if Q == 0:
-        return torch.empty(0, dtype=points.dtype, device=points.device)
-    if not on_gpu:
+    if not points.is_cuda:
         from scipy.spatial import KDTree
 
         lifted = np.concatenate([np.asarray(points), np.asarray(point_weights.abs())[:, None]], axis=1)
         q = np.concatenate([np.asarray(queries), np.zeros((Q, 1), dtype=lifted.dtype)], axis=1)
-        dist, _ = KDTree(lifted).query(q, workers=core.CPU_WORKERS)
+        dist, ids = KDTree(lifted).query(q, workers=core.CPU_WORKERS)
         dist = np.asarray(dist, dtype=np.float64).reshape(Q)
-        return torch.as_tensor(np.square(dist) if squared else dist).to(points.dtype)
+        ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(Q)) if want_ids else None
+        return ids, torch.as_tensor(np.square(dist) if squared else dist).to(points.dtype)
     lib = _native.load()
     dev = points.device
     torch.cuda.set_device(dev)
@@ -236,8 +277,11 @@ def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: O
     q = queries.contiguous()
     one = torch.ones((1, 1), dtype=torch.float32, device=dev)
     bits = torch.empty(Q, dtype=torch.int32, device=dev)
+    ids = torch.empty(Q, dtype=torch.int64, device=dev) if want_ids else None
+    not_found = torch.zeros(1, dtype=torch.int32, device=dev) if want_ids else None
     key_bits = int(lib.flooder_sample_key_bits(q.shape[1]))
-    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // 24, (1 << 32) - 3))   # as _query_sweep_hip
+    # (as _query_sweep_hip; the witness names a query by an int32)
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // 24, (1 << 31) - 1))
     for a in range(0, Q, per_group):
         b = min(Q, a + per_group)
         verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
@@ -247,7 +291,18 @@ def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: O
                                 **core._knn_block_fields(index, verts, one))
         _native.check(lib.flooder_sweep_power_f32(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w), st),
                       "flooder_sweep_power_f32")
-    return _root_of_bits(lib, bits, squared, st)
+        if want_ids:   # the witness search in its query form: query i is sample (i, 0) with the word just written
+            q_s = torch.arange(b - a, dtype=torch.int32, device=dev)
+            blk = _native.WitnessSearch(pts_sorted=index.pts, n_pts=index.n, dim=index.dim, k1=1, nodes=index.nodes,
+                                        order=index.order32, verts=verts, weights=one, R=1, n_simplices=b - a,
+                                        n_queries=b - a, q_simplex=q_s, q_row=torch.zeros_like(q_s), q_d2=bits[a:b],
+                                        out_point=ids[a:b], not_found=not_found)
+            _native.check(lib.flooder_witness_power(ctypes.byref(blk), _native.ptr(w_sorted), _native.ptr(node_w), st),
+                          "flooder_witness_power")
+    if want_ids and int(not_found.item()):
+        raise RuntimeError(f"power_nearest: the witness search found no point at the exact power distance for "
+                           f"{int(not_found.item())} queries")
+    return ids, _root_of_bits(lib, bits, squared, st)
 
 
 def _no_neighbors(points: torch.Tensor, k: int):
@@ -404,3 +459,43 @@ class _NeighborDistance(torch.autograd.Function):
                 vals.append(grad_q)
         grad_p = _scatter_rows(targets, vals, points.shape[0], dim, dev, dt) if need_p else None
         return grad_p, (None if own or not ctx.needs_input_grad[1] else grad_q), None, None, None, None
+
+
+class _PowerDistance(torch.autograd.Function):
+    """``power_distance`` with its closed-form backward.  ``queries`` None: the cloud's own points (both roles of a
+    point accumulate into the gradient of ``points``)."""
+
+    @staticmethod
+    def forward(ctx, points, point_weights, queries, squared, index):
+        own = queries is None
+        qs = points if own else queries
+        ids, value = _power_query(points, point_weights, qs, index, squared, True)
+        ctx.save_for_backward(points, point_weights, qs, ids, value)
+        ctx.own, ctx.squared = own, squared
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        from .grad import _scatter_rows
+
+        points, point_weights, qs, ids, value = ctx.saved_tensors
+        own, squared = ctx.own, ctx.squared
+        need_p, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_q = own or ctx.needs_input_grad[2]
+        Q, dim = qs.shape
+        dt, dev = points.dtype, points.device
+        # coefficient of (q - x*) and of w*: grad_out * (1 / f, 0 where f == 0; or 2)
+        coef = grad_out * 2.0 if squared else torch.where(value > 0, grad_out / value, torch.zeros_like(value))
+        grad_q = (qs.detach() - points.detach()[ids]) * coef.unsqueeze(1)      # (Q, dim)
+        grad_p = grad_w = None
+        if need_p:
+            targets, vals = [ids], [-grad_q]
+            if own:
+                targets.append(torch.arange(Q, dtype=torch.int64, device=dev))
+                vals.append(grad_q)
+            grad_p = _scatter_rows(targets, vals, points.shape[0], dim, dev, dt)
+        if need_w:
+            grad_w = _scatter_rows([ids], [(point_weights.detach()[ids] * coef).unsqueeze(1)], points.shape[0], 1, dev,
+                                   dt).reshape(-1)
+        return grad_p, grad_w, (grad_q if need_q and not own else None), None, None

@@ -1132,7 +1132,19 @@ int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream);
  * abi; k != 1; dim outside 2..8; stat != 0; reserved != 0.  Then n_simplices == 0 or R == 0: FLOODER_OK, nothing is
  * touched.  Then: a NULL pointer (w_sorted and node_w included; sample_order and stats may be NULL), n_pts < 1, k1,
  * n_simplices * R >= 2^32 - 2.
+ *
+ * flooder_witness_power: WHICH point attains a power word (power_filtration, power_nearest).  The block and its
+ * meaning are flooder_witness_search's, with q_d2[q] = the target POWER word - the bits flooder_sweep_power_f32 wrote
+ * for the sample (q_simplex[q], q_row[q]) - and w_sorted, node_w as above.  out_point[q] = the smallest original id
+ * (order[row]) among the points whose word fmaf(w, w, d2) has exactly the target bits, -1 if there is none or if
+ * (q_simplex[q], q_row[q]) is no swept sample; each such query adds 1 to *not_found (one zeroed word, the only atomic).
+ * One wave per query walks the box tree with a stack of sibling groups; a node is opened iff
+ * fmaf(node_w[node], node_w[node], gap2 of p* to its box) * SAFE <= target (non-strict), the sweep's leaf bound: a
+ * skipped node holds no point at the target.  Zero weights: the outputs of flooder_witness_search on the same block.
+ * Refused (FLOODER_E_ARG), the outputs untouched: a bad block size or abi; then n_queries == 0 is FLOODER_OK; then a
+ * NULL pointer (w_sorted and node_w included), dim outside 2..8, n_pts < 1 or above 2^31 - 1, k1 < 1, R < 1.
  */
+int flooder_witness_power(const flooder_witness_search_t* p, const float* w_sorted, const float* node_w, void* stream);
 int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream);
 int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const float* w_sorted, const float* node_w, void* stream);
 
