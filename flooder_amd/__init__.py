@@ -10,7 +10,7 @@ from .core import (flood_complex, generate_landmarks, generate_grid, generate_un
                    index_from_host, forget_index)
 from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
-from .grad import FloodFiltration, flood_filtration, power_filtration
+from .grad import FloodFiltration, flood_filtration, power_filtration, dtm_filtration
 from .profile import FloodProfile, flood_profile
 from .neighbors import neighbor_distance, nearest_neighbors, distance_to_measure, power_distance, power_nearest
 from .synthetic import (
@@ -26,6 +26,7 @@ __all__ = [
     "flood_complex",
     "flood_filtration",
     "power_filtration",
+    "dtm_filtration",
     "FloodFiltration",
     "flood_profile",
     "FloodProfile",

@@ -277,6 +277,12 @@ SIGNATURES = {
     "flooder_sweep_power_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p, c_void_p, c_void_p]),
     # ... and which point attains a power word: the witness search's block plus the same two pointers (power_filtration)
     "flooder_witness_power": (c_int, [ctypes.POINTER(WitnessSearch), c_void_p, c_void_p, c_void_p]),
+    # the backward of the distance to a measure (distance_to_measure(differentiable=True)): per query the sum over its
+    # listed neighbours, and its transpose over the entries sorted by target
+    "flooder_dtm_grad_queries_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
+                                             c_void_p, c_void_p, c_void_p]),
+    "flooder_dtm_grad_points_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

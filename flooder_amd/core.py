@@ -1829,6 +1829,7 @@ BVH_SORTED_SAMPLES: Optional[bool] = None
 SORTED_WORKSPACE_BYTES = 16 << 30   # scratch the sorted-sample sweep may take (288 GB of HBM per GPU)
 PROFILE_WORKSPACE_BYTES = SORTED_WORKSPACE_BYTES   # plane buffer of one profile sweep (4 B x columns x S x R); above it: groups of simplices
 KNN_MERGE_WORKSPACE_BYTES = PROFILE_WORKSPACE_BYTES   # a shard's list buffer and the gathered lists of a point-sharded k-nearest pass (4 B x k x S x R x (ranks + 1)); above it: groups of simplices
+DTM_GRAD_WORKSPACE_BYTES = 4 << 30   # the sorted (target, query row) list of one group of distance_to_measure's backward (64 B x entries: the keys, torch.sort's values, indices and scratch); above it: groups of query rows, the same bits
 SORTED_FUSED_FACES = False  # the sorted sweep delivers the face maxima itself and drops what cannot raise one (measured SLOWER at cfg 4: 116 vs 87 ms - in 6-D the distances of a triangle's samples concentrate, 83 % of the leaves are still evaluated; kept as an option)
 BVH_SORTED_MIN_SAMPLES = 64 * 1024   # below this the sort costs more than it saves
 EMPTY_CACHE_ABOVE_BYTES = 1 << 30   # flood_complex releases the allocator's cache when more than this is cached unused

@@ -19,6 +19,9 @@ df/dpoints[id_(i)] = -(p* - x_(i)) / (k f), df/dL_j = w*_j (p* - mean x) / f.
 ``power_filtration`` (the weighted filtration, ``flood_complex(point_weights=w)``): f = sqrt(|p* - x*|^2 + w*^2) with x*
 the POWER-nearest point of p* - on ROCm tensors recovered exactly by ``flooder_witness_power`` from the bits of the
 power-distance sweep -, u = (p* - x*) / f: df/dpoints[j*] = -u, df/dL_i = w*_i u, df/dpoint_weights[j*] = w_j* / f.
+
+``dtm_filtration`` (the DTM filtration by mass): ``power_filtration`` with w = ``distance_to_measure(points, mass=m,
+differentiable=True)``, whose gradient chains on into the points for every k up to 1024.
 """
 
 from __future__ import annotations
@@ -36,11 +39,11 @@ from . import core
 from .persistence import persistence_pairs_simplices
 from .simplex_tree import SimplexTree, delaunay_cells
 
-__all__ = ["FloodFiltration", "flood_filtration", "power_filtration"]
+__all__ = ["FloodFiltration", "flood_filtration", "power_filtration", "dtm_filtration"]
 
 
 class FloodFiltration:
-    """Result of ``flood_filtration`` and ``power_filtration``: per dimension d (lists indexed by d)
+    """Result of ``flood_filtration``, ``power_filtration`` and ``dtm_filtration``: per dimension d (lists indexed by d)
 
     ``simplices[d]``        (n_d, d+1) int64 CPU: the rows of ``tree.simplices_of_dimension(d)`` (vertex ids ascending)
     ``values[d]``           (n_d,) on the points' device and dtype, differentiable w.r.t. points and landmarks
@@ -50,7 +53,8 @@ class FloodFiltration:
                             (distance, id) (-1: none); its last column is ``witness_point[d]``, the k-th nearest
     ``neighbors``, ``neighbor_stat``  the robust filtration's arguments (1, "kth": the plain filtration)
     ``point_weights``       the weighted filtration's (N,) tensor (``power_filtration``: ``witness_point`` is then the
-                            POWER-nearest point of the witness sample); None from every other producer
+                            POWER-nearest point of the witness sample; ``dtm_filtration``: the distance to the measure
+                            at every point, with grad when the points require it); None from ``flood_filtration``
     ``tree``                the ``flooder_amd.SimplexTree`` with the (detached) values
     """
 
@@ -176,6 +180,32 @@ def power_filtration(points: torch.Tensor, landmarks, point_weights: torch.Tenso
     method = _check_args(points, method)
     return _filtration(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx, method, index, 1, "kth",
                        point_weights)
+
+
+def dtm_filtration(points: torch.Tensor, landmarks, mass: Optional[float] = None, max_dimension: Optional[int] = None,
+                   points_per_edge: int = 30, num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *,
+                   neighbors: Optional[int] = None, neighbor_stat: str = "dtm", method: Optional[str] = None,
+                   index: Optional["core.PointIndex"] = None) -> FloodFiltration:
+    """The DTM filtration by mass, differentiable end to end: ``power_filtration(points, landmarks, w, ...)`` with
+    ``w = distance_to_measure(points, mass=mass, neighbors=neighbors, neighbor_stat=neighbor_stat, differentiable=True,
+    index=index)`` at the cloud's own points - the literature's robust filtration (k = mass * N up to 1024 neighbours)
+    at the cost of one wide k-nearest sweep over the cloud and a k = 1 sweep over the samples.
+
+    The arguments are judged by those two functions' own checks, with their messages (exactly one of ``mass`` and
+    ``neighbors``).  The values are those of ``flood_complex(points, landmarks, ..., point_weights=
+    distance_to_measure(points, mass=mass))``, on ROCm tensors bit for bit.  ``F.point_weights`` is w and carries grad
+    when ``points`` requires it: one backward adds the three gradients of ``power_filtration`` into ``points`` (as
+    witness points, as landmarks taken from the cloud, and through the weights, chained through the closed form of
+    ``distance_to_measure``).  On ROCm tensors the ``PointIndex`` is built once (or recalled, or ``index``) and serves
+    both steps and the landmark selection; every sum has a fixed order: bit-identical run to run."""
+    from .neighbors import _check_points, _index_of, distance_to_measure
+
+    if _check_points(points, "distance_to_measure") and index is None:
+        index = _index_of(points.detach(), None)
+    w = distance_to_measure(points, None, mass, neighbors=neighbors, neighbor_stat=neighbor_stat, differentiable=True,
+                            index=index)
+    return power_filtration(points, landmarks, w, max_dimension, points_per_edge, num_rand, start_idx, method=method,
+                            index=index)
 
 
 def _filtration(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx, method, index, neighbors,

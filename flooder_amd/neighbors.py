@@ -13,7 +13,8 @@ attains it (``flooder_witness_power``), and with it ``power_distance`` is differ
 the queries.
 
 ``distance_to_measure`` speaks in MASS (k = mass * N, up to 1024 neighbours): ``flooder_knn_wide_f32``, one wave per query
-with its k best in LDS, values and neighbours without gradients.
+with its k best in LDS, values and neighbours; detached by default, with ``differentiable=True`` the closed form of
+``neighbor_distance`` for every k, its backward two kernels of ``csrc/flood_dtm_grad.hip`` over the sweep's int32 ids.
 """
 
 from __future__ import annotations
@@ -146,7 +147,8 @@ def nearest_neighbors(points: torch.Tensor, queries: Optional[torch.Tensor] = No
 
 def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = None, mass: Optional[float] = None, *,
                         neighbors: Optional[int] = None, neighbor_stat: str = "dtm", squared: bool = False,
-                        return_neighbors: bool = False, index: Optional[core.PointIndex] = None):
+                        return_neighbors: bool = False, index: Optional[core.PointIndex] = None,
+                        differentiable: bool = False):
     """Per query the distance to the empirical measure of ``points`` at mass ``mass`` -> (Q,) tensor of ``points``'
     dtype on its device.
 
@@ -166,7 +168,16 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
     (within 78 * 2^-24 relative of the exact mean).  ``flood_complex(..., neighbor_mass=m)`` has these values at its
     vertices.  CPU tensors (float32, float64; any dimension) query scipy's kd-tree.
 
-    Not differentiable: inputs that require grad are used detached.  ``neighbor_distance`` is, for k <= 32.
+    By default inputs that require grad are used detached.  ``differentiable=True``: when ``points`` or ``queries``
+    requires grad (and grad mode is on) the value carries a ``grad_fn`` with the closed form of ``neighbor_distance``
+    over m terms, m = k for ``"dtm"`` and m = 1 (x_(k) alone) for ``"kth"``: with f the value, (q - x_(i)) has the
+    coefficient grad_out / (f m), 0 where f = 0, and grad_out * 2 / m with ``squared=True``; dq is their sum, its
+    negative goes term by term to the x_(i); with ``queries=None`` both roles accumulate into ``points.grad``.  The
+    values (and ``ids``, ``dist`` of ``return_neighbors=True``; ``dist`` is detached) are bit for bit those of the call
+    without grad; without an input that requires grad the keyword changes nothing.  ROCm tensors keep the wide sweep's
+    int32 ids and run ``flooder_dtm_grad_queries_f32`` and ``flooder_dtm_grad_points_f32`` (csrc/flood_dtm_grad.hip): no
+    (Q, k, dim) tensor, no float atomics, groups of query rows within ``core.DTM_GRAD_WORKSPACE_BYTES`` - the gradient
+    is bit-identical run to run and does not depend on the groups.  CPU tensors: the kd-tree's ids and ``index_add_``.
     """
     on_gpu = _check_points(points, "distance_to_measure")
     if (mass is None) == (neighbors is None):
@@ -184,18 +195,25 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
                              f"the LDS of one wave), got {k}")
     if k > n:
         raise ValueError(f"neighbors={k} exceeds the number of points ({n})")
+    own = queries is None
     queries = _check_queries_and_index(points, queries, index, on_gpu)
+    with_grad = bool(differentiable) and torch.is_grad_enabled() and (points.requires_grad or queries.requires_grad)
+    grad_points, grad_queries = points, queries
     points, queries = points.detach(), queries.detach()
     if queries.shape[0] == 0:
         value = torch.empty(0, dtype=points.dtype, device=points.device)
         return (value, *_no_neighbors(points, k)) if return_neighbors else value
     if on_gpu:
-        ids, dist, bits = _query_sweep_hip(points, queries, k, neighbor_stat, index, return_neighbors, return_neighbors,
-                                           True, wide=True)
+        ids, dist, bits = _query_sweep_hip(points, queries, k, neighbor_stat, index, return_neighbors or with_grad,
+                                           return_neighbors, True, wide=True)
         value = _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
     else:
         dist, ids = _kdtree_query(points, queries, k)
         value = _cpu_statistic(dist, k, neighbor_stat, squared).to(points.dtype)
+    if with_grad:   # (ROCm tensors: the sweep's int32 ids as they are)
+        saved = ids if on_gpu else torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64))
+        value = _DistanceToMeasure.apply(grad_points, None if own else grad_queries, value, saved, neighbor_stat,
+                                         bool(squared))
     return (value, *_neighbor_pair(points, ids, dist, squared)) if return_neighbors else value
 
 
@@ -459,6 +477,96 @@ class _NeighborDistance(torch.autograd.Function):
                 vals.append(grad_q)
         grad_p = _scatter_rows(targets, vals, points.shape[0], dim, dev, dt) if need_p else None
         return grad_p, (None if own or not ctx.needs_input_grad[1] else grad_q), None, None, None, None
+
+
+class _DistanceToMeasure(torch.autograd.Function):
+    """``distance_to_measure(differentiable=True)``: the computed ``value`` with the closed-form backward of
+    ``_NeighborDistance`` over the ``ids`` (Q, k) the forward found (int32 on ROCm tensors, int64 on CPU tensors), for
+    every k.  ``queries`` None: the cloud's own points."""
+
+    @staticmethod
+    def forward(ctx, points, queries, value, ids, stat, squared):
+        own = queries is None
+        ctx.save_for_backward(points, points if own else queries, ids, value)
+        ctx.own, ctx.stat, ctx.squared = own, stat, squared
+        return value.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        points, qs, ids, value = ctx.saved_tensors
+        own, squared = ctx.own, ctx.squared
+        need_p = ctx.needs_input_grad[0]
+        need_q = own or ctx.needs_input_grad[1]
+        k = ids.shape[1]
+        m = 1 if ctx.stat == "kth" else k                      # "kth": x_(k) alone, the column k - 1
+        # coefficient of (q - x_(i)): grad_out * (1 / f, 0 where f == 0; or 2) / (number of terms of the mean)
+        if squared:
+            coef = grad_out * (2.0 / m)
+        else:
+            coef = torch.where(value > 0, grad_out / (value * m), torch.zeros_like(value))
+        backward = _dtm_backward_hip if points.is_cuda else _dtm_backward_cpu
+        grad_p, grad_q = backward(points.detach(), qs.detach(), ids, k - m, m, coef, own, need_p, need_q)
+        return grad_p, (None if own or not ctx.needs_input_grad[1] else grad_q), None, None, None, None
+
+
+def _dtm_backward_cpu(points, qs, ids, first: int, m: int, coef, own: bool, need_p: bool, need_q: bool):
+    """(grad_points or None, grad_queries or None) over the columns ``first`` .. ``first + m - 1`` of ``ids``: plain torch,
+    ``index_add_`` (sequential on the host: deterministic), in groups of query rows that keep the (rows, m, dim)
+    contributions of a group near 256 MB."""
+    Q, dim = qs.shape
+    grad_q = torch.empty_like(qs) if need_q else None
+    grad_p = torch.zeros_like(points) if need_p else None
+    per_group = max(1, (256 << 20) // (m * dim * points.element_size()))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        nb = ids[a:b, first:first + m]
+        contrib = (qs[a:b].unsqueeze(1) - points[nb]) * coef[a:b].view(-1, 1, 1)      # (rows, m, dim)
+        if need_q:
+            grad_q[a:b] = contrib.sum(dim=1)
+        if need_p:
+            grad_p.index_add_(0, nb.reshape(-1), -contrib.reshape(-1, dim))
+    if need_p and own:
+        grad_p += grad_q
+    return grad_p, grad_q
+
+
+def _dtm_backward_hip(points, qs, ids, first: int, m: int, coef, own: bool, need_p: bool, need_q: bool):
+    """The same on ROCm float32 tensors: ``flooder_dtm_grad_queries_f32`` over all queries, then per group of ascending
+    query rows the (target, query row) pairs as packed int64 keys, sorted (the keys are distinct: one sorted list, however
+    it is sorted), the segment of every row of ``points`` by a binary search, and ``flooder_dtm_grad_points_f32``,
+    which continues the sequential sum per (target, axis) from group to group - the gradient does not depend on
+    ``core.DTM_GRAD_WORKSPACE_BYTES``.  ``queries=None``: one further addition per word, grad_queries onto grad_points."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    pts, q = points.contiguous(), qs.contiguous()
+    coef = coef.to(torch.float32).contiguous()
+    (Q, dim), n, k = q.shape, pts.shape[0], ids.shape[1]
+    grad_q = grad_p = None
+    if need_q:
+        grad_q = torch.empty((Q, dim), dtype=torch.float32, device=dev)
+        _native.check(lib.flooder_dtm_grad_queries_f32(_native.ptr(pts), n, _native.ptr(q), Q, dim,
+                                                       _native.ptr(ids) + 4 * first, k, m, _native.ptr(coef),
+                                                       _native.ptr(grad_q), st), "flooder_dtm_grad_queries_f32")
+    if need_p:
+        grad_p = torch.zeros((n, dim), dtype=torch.float32, device=dev)
+        bounds = torch.arange(n + 1, dtype=torch.int64, device=dev) << 32
+        per_group = max(1, min(Q, int(core.DTM_GRAD_WORKSPACE_BYTES) // (64 * m), ((1 << 31) - 1) // m))
+        for a in range(0, Q, per_group):
+            b = min(Q, a + per_group)
+            rows = torch.arange(b - a, dtype=torch.int64, device=dev).unsqueeze(1)
+            keys = ((ids[a:b, first:first + m].to(torch.int64) << 32) | rows).reshape(-1)
+            keys = torch.sort(keys).values
+            seg_ptr = torch.searchsorted(keys, bounds)
+            _native.check(lib.flooder_dtm_grad_points_f32(_native.ptr(pts), n, _native.ptr(q[a:b]), b - a, dim,
+                                                          _native.ptr(coef[a:b]), _native.ptr(keys), _native.ptr(seg_ptr),
+                                                          None, n, _native.ptr(grad_p), st),
+                          "flooder_dtm_grad_points_f32")
+        if own:
+            grad_p += grad_q
+    return grad_p, grad_q
 
 
 class _PowerDistance(torch.autograd.Function):

@@ -1148,6 +1148,46 @@ int flooder_witness_power(const flooder_witness_search_t* p, const float* w_sort
 int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream);
 int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const float* w_sorted, const float* node_w, void* stream);
 
+/*
+ * ---- Backward of the distance to a measure (csrc/flood_dtm_grad.hip; distance_to_measure(differentiable=True)) -----
+ * Per query q the value of flooder_knn_wide_f32 depends on the m listed neighbours x_(i) = points[ids[q, i]] (m = k for
+ * "dtm"; m = 1, the column k - 1, for "kth") through the differences q - x_(i), each with the coefficient coef[q] the
+ * caller forms (grad_out / (f m), 0 where f = 0; grad_out * 2 / m for the squared value).  points (n_points, dim) and
+ * queries (n_queries, dim) are the caller's contiguous float32 rows in input order: no tree, and no contribution is
+ * ever stored.  No atomics; plain vector loads and stores; every output word is written once per launch.
+ *
+ * flooder_dtm_grad_queries_f32: out_q[q, c] = coef[q] * sum_i (queries[q, c] - points[ids[q * ld_ids + i], c]) over
+ * i = 0 .. m - 1 (ld_ids >= m: the row stride of ids in words; "kth" passes ids + k - 1, ld_ids = k, m = 1).  One wave
+ * per query.  Order of the sum, a function of m and the 64 lanes alone: lane l adds the differences of the positions
+ * l, l + 64, l + 128, ... < m, left to right, to a partial sum that starts as +0; the 64 partial sums a_0 .. a_63 (+0
+ * in the lanes >= m) are added in a butterfly, a_l = a_l + a_(l ^ s) for s = 32, 16, 8, 4, 2, 1 in turn (addition
+ * commutes: every lane holds the same word); the product with coef[q] comes last.  An id outside 0 .. n_points - 1 is
+ * not read and adds nothing.
+ *
+ * flooder_dtm_grad_points_f32: the transpose.  entries: (seg_ptr[n_seg],) int64, the list of all (target, query row)
+ * pairs sorted by target and, inside a target, ascending by query row; of each entry the LOW 32 bits are read, the
+ * query row (so the sorted packed keys (target << 32) | query row serve as they are).  Segment g = the entries
+ * [seg_ptr[g], seg_ptr[g + 1]) and belongs to the row j = seg_target[g] of points (seg_target NULL: j = g; the targets
+ * of one launch are distinct).  Thread (g, c) starts from the word already in out_p[j, c] and takes its entries front
+ * to back: acc = fma(-coef[q], queries[q, c] - points[j, c], acc), one rounding for the difference and one for the
+ * step; then out_p[j, c] = acc.  So launches over consecutive groups of ascending query rows (queries, coef and the
+ * entries' rows relative to the group's first row) continue one sequential sum per (target, axis): the result does not
+ * depend on the groups, bit for bit - the rule of flooder_segment_sum_f32, continued across launches.  Rows of out_p
+ * without a non-empty segment are left as they are; a target outside 0 .. n_points - 1 or a query row >= n_queries is
+ * not read and adds nothing.  A segment may have any length (it is not bounded by FLOODER_KNN_WIDE_MAX: a point can be
+ * a neighbour of every query).
+ *
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a pointer is read: dim outside 2..8; m
+ * outside 1..FLOODER_KNN_WIDE_MAX and ld_ids < m (grad_queries); a negative count; a NULL pointer (seg_target may be).
+ * Then n_queries == 0 or n_seg == 0: FLOODER_OK, nothing is touched.
+ */
+int flooder_dtm_grad_queries_f32(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int dim,
+                                 const int32_t* ids, int64_t ld_ids, int m, const float* coef, float* out_q,
+                                 void* stream);
+int flooder_dtm_grad_points_f32(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int dim,
+                                const float* coef, const int64_t* entries, const int64_t* seg_ptr,
+                                const int32_t* seg_target, int64_t n_seg, float* out_p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
