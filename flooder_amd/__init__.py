@@ -11,8 +11,9 @@ from .core import (flood_complex, generate_landmarks, generate_grid, generate_un
 from .simplex_tree import SimplexTree, DelaunayComplex
 from .io import save_to_disk
 from .grad import FloodFiltration, flood_filtration, power_filtration, dtm_filtration
-from .profile import FloodProfile, flood_profile
-from .neighbors import neighbor_distance, nearest_neighbors, distance_to_measure, power_distance, power_nearest
+from .profile import FloodProfile, flood_profile, power_profile, dtm_profile
+from .neighbors import (neighbor_distance, nearest_neighbors, distance_to_measure, distance_to_measure_profile,
+                        power_distance, power_nearest)
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -33,6 +34,9 @@ __all__ = [
     "neighbor_distance",
     "nearest_neighbors",
     "distance_to_measure",
+    "distance_to_measure_profile",
+    "power_profile",
+    "dtm_profile",
     "power_distance",
     "power_nearest",
     "generate_landmarks",

@@ -151,6 +151,19 @@ class KnnWide(_Block):
         i32 k; i64 n_simplices; i32 stat; i32 reserved; p order; p sample_order; p out_bits; p out_ids; p out_d2""")
 
 
+POWER_COLS_MAX = 8  # FLOODER_POWER_COLS_MAX: weight columns of one power-profile sweep
+
+
+def column_arrays(columns):
+    """(k, stat index) pairs -> (n_cols, col_k, col_stat): the host int32 arrays ``flooder_knn_wide_profile_f32`` reads
+    before its launch (at most ``KNN_COLS_MAX`` columns)."""
+    columns = list(columns)
+    if len(columns) > KNN_COLS_MAX:
+        raise ValueError(f"flooder_knn_wide_profile_f32 takes at most {KNN_COLS_MAX} columns, got {len(columns)}")
+    n = len(columns)
+    return n, (c_int32 * max(n, 1))(*[int(k) for k, _ in columns]), (c_int32 * max(n, 1))(*[int(s) for _, s in columns])
+
+
 # The control words of the fused sweep (include/flooder_hip.h, FLOODER_<name>: int32 word offsets into finish_ctl,
 # defer_ctl and the queue areas); tests/test_host.py compiles the header and compares
 QUEUE_WORDS = 512
@@ -271,10 +284,17 @@ SIGNATURES = {
     "flooder_knn_merge_f32": (c_int, [ctypes.POINTER(KnnMerge), c_void_p]),
     # ... and the k nearest for k up to 1024, one wave per cell (flood_complex(neighbor_mass=m), distance_to_measure)
     "flooder_knn_wide_f32": (c_int, [ctypes.POINTER(KnnWide), c_void_p]),
+    # ... and every (k, stat) column of that list from one walk at the largest k: the same block, then n_cols, the
+    # host arrays col_k and col_stat (int32) and plane_stride (distance_to_measure_profile)
+    "flooder_knn_wide_profile_f32": (c_int, [ctypes.POINTER(KnnWide), c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     # the weighted filtration (flood_complex(point_weights=w)): the minimum of a value per tree row over every node, and
     # the power-distance sweep on the block of the sorted k-nearest sweep (k = 1) plus the weights and their node minima
     "flooder_node_min_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "flooder_sweep_power_f32": (c_int, [ctypes.POINTER(KnnSorted), c_void_p, c_void_p, c_void_p]),
+    # ... for up to 8 interleaved weight columns in one walk of the tree: the same block, then n_cols, w_cols and
+    # node_w_cols (power_profile, dtm_profile)
+    "flooder_node_min_cols_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "flooder_sweep_power_profile_f32": (c_int, [ctypes.POINTER(KnnSorted), c_int, c_void_p, c_void_p, c_void_p]),
     # ... and which point attains a power word: the witness search's block plus the same two pointers (power_filtration)
     "flooder_witness_power": (c_int, [ctypes.POINTER(WitnessSearch), c_void_p, c_void_p, c_void_p]),
     # the backward of the distance to a measure (distance_to_measure(differentiable=True)): per query the sum over its

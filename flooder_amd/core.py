@@ -1705,6 +1705,69 @@ def _power_weights(index: PointIndex, point_weights: torch.Tensor) -> Tuple[torc
     return w_sorted, node_w
 
 
+POWER_COLS_MAX = _native.POWER_COLS_MAX   # FLOODER_POWER_COLS_MAX: weight columns of one flooder_sweep_power_profile_f32
+
+
+def _power_weight_columns(index: PointIndex, point_weights: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The column form of ``_power_weights`` for ``point_weights`` (N, m), 1 <= m <= ``POWER_COLS_MAX``: (``w_cols``
+    (n_pad, NC) = |w| in tree-row order, the m weights of a row contiguous, NC = m rounded up to 1, 2, 4 or 8;
+    ``node_w_cols`` (nodes, NC) = ``flooder_node_min_cols_f32`` of it).  The rows of the padded last leaf and the padding
+    columns hold +inf (the sweep leaves padding columns out of its tests).  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    m = point_weights.shape[1]
+    nc = 1 if m <= 1 else 2 if m <= 2 else 4 if m <= 4 else 8
+    w_cols = torch.full((index.pts.shape[0], nc), float("inf"), dtype=torch.float32, device=dev)
+    w_cols[:index.n, :m] = point_weights.detach().to(torch.float32).abs()[index.order32.long()]
+    node_w_cols = torch.empty((index.nodes.shape[0], nc), dtype=torch.float32, device=dev)
+    _native.check(lib.flooder_node_min_cols_f32(_native.ptr(w_cols), index.n, nc, _native.ptr(node_w_cols),
+                                                _native.current_stream_ptr(dev)), "flooder_node_min_cols_f32")
+    return w_cols, node_w_cols
+
+
+def _sweep_dimension_power_profile(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
+                                   weight_groups, plan: Optional["SamplePlan"] = None,
+                                   stats: Optional[torch.Tensor] = None, timer: Optional[_KernelTimer] = None):
+    """All simplices of one dimension against an indexed point set under SEVERAL weight vectors -> one (S, F) tensor of
+    face maxima per weight column, in column order; tensor c holds the bits ``_sweep_dimension_power`` returns with
+    column c's weights.  ``weight_groups``: ``(m, w_cols, node_w_cols)`` per group of at most ``POWER_COLS_MAX``
+    columns (``_power_weight_columns``, once per call).
+
+    Per column group and per group of consecutive simplices (the (m, S_g, R) plane buffer within
+    ``PROFILE_WORKSPACE_BYTES``; a simplex's words do not depend on which others are swept with it) ONE
+    ``flooder_sweep_power_profile_f32`` - over tiles of the sorted sample order where ``knn_sorts_samples`` says so,
+    as the single sweep - then ``flooder_face_max_f32`` once per plane.  No host synchronisation."""
+    lib = _native.load()
+    dev = index.pts.device
+    st = _native.current_stream_ptr(dev)
+    S, R = verts.shape[0], weights.shape[0]
+    verts = verts.to(torch.float32).contiguous()
+    plan = plan if plan is not None else SamplePlan(weights, faces)
+    n_cols = sum(m for m, _, _ in weight_groups)
+    out_faces = [torch.empty((S, faces.n_faces), dtype=torch.float32, device=dev) for _ in range(n_cols)]
+    first = 0
+    for m, w_cols, node_w_cols in weight_groups:
+        per_group = max(1, min(S, int(PROFILE_WORKSPACE_BYTES) // max(1, 4 * m * R)))
+        for a in range(0, S, per_group):
+            b = min(S, a + per_group)
+            sorted_samples = knn_sorts_samples(index.dim, b - a, R)
+            queue, sort_state = _zeroed_queue(lib, dev, (b - a) * R if sorted_samples else 0)
+            planes = torch.empty((m, b - a, R), dtype=torch.int32, device=dev)
+            with _span(timer, "sweep"):
+                order = (_sorted_sample_order(lib, st, index, verts[a:b], plan.w_perm, sort_state, None,
+                                              int(lib.flooder_sample_key_bits(index.dim))) if sorted_samples else None)
+                blk = _native.KnnSorted(k=1, stat=0, queue=queue, out_bits=planes, stats=stats, sample_order=order,
+                                        **_knn_block_fields(index, verts[a:b], plan.w_perm))
+                _native.check(lib.flooder_sweep_power_profile_f32(ctypes.byref(blk), m, _native.ptr(w_cols),
+                                                                  _native.ptr(node_w_cols), st),
+                              "flooder_sweep_power_profile_f32")
+            with _span(timer, "face_max"):
+                for c in range(m):   # (one span for the planes of a group: the epilogue gets no timer)
+                    _face_epilogue(lib, st, planes[c], faces, plan.rows_perm, out_face=out_faces[first + c][a:b])
+        first += m
+    return out_faces
+
+
 def _sweep_dimension_power(index: PointIndex, verts: torch.Tensor, weights: torch.Tensor, faces: _FaceTable,
                            w_sorted: torch.Tensor, node_w: torch.Tensor,
                            reduce_hook: Optional[Callable[[torch.Tensor], None]] = None,

@@ -33,6 +33,11 @@
 //
 // No atomics, nothing in inline assembly of its own; every output word is written once by plain vector stores.  The
 // rule of the statistic (the strided sum of stat 1) is stated with the entry in include/flooder_hip.h.
+//
+// Profile (flooder_knn_wide_profile_f32; distance_to_measure_profile).  The list a wave ends a cell with holds the k
+// smallest keys ascending, so its first k' entries are the k' smallest keys and wide_statistic over them is the word of
+// the single call at (k', stat'): the epilogue - and nothing else - is a compile-time variant (COLS) that writes one
+// word per listed column, planes plane_stride words apart.  The walk culls against the k-th key of the LARGEST k.
 
 #include "../../include/flooder_hip.h"
 #include "flood_common.hpp"
@@ -117,12 +122,40 @@ __device__ __forceinline__ void merge_buffer(wkey_t* list, wkey_t* buf, int k, i
   lds_handoff();   // (the merged list is in)
 }
 
-template <int DIM, int SLOTS>
+// The columns of the epilogue, a compile-time variant of the ONE kernel: NoCols (flooder_knn_wide_f32) writes the word
+// of (k, stat) to out_bits[g]; WideCols (flooder_knn_wide_profile_f32) a word per listed (k', stat') with k' <= k to
+// out_bits[c * plane_stride + g].  The walk, the insertion and the id / d2 rows do not know which it is.
+struct NoCols {};
+struct WideCols {
+  int64_t plane_stride;
+  int n_cols;
+  int col_k[FLOODER_KNN_COLS_MAX];
+  int col_stat[FLOODER_KNN_COLS_MAX];
+};
+
+// The squared statistic of the first kk keys of the ascending list (wave-uniform kk, stat; the same value in every lane)
+__device__ __forceinline__ float wide_statistic(const wkey_t* list, int kk, int stat, int lane) {
+  if (stat == 0) return __uint_as_float((uint32_t)(list[kk - 1] >> 32));
+  // S_l = w_l + w_(l+64) + w_(l+128) + ... (positions < kk), then S_0 + S_1 + ... + S_(min(kk,64)-1): both sequential
+  // float32 sums in that order; for kk <= 64 the plain ascending sequential sum of the value sweeps
+  float part = 0.f;
+  if (lane < kk) {
+    part = __uint_as_float((uint32_t)(list[lane] >> 32));
+    for (int i = lane + 64; i < kk; i += 64) part = part + __uint_as_float((uint32_t)(list[i] >> 32));
+  }
+  const int L = kk < 64 ? kk : 64;   // the lanes that hold a partial sum
+  float acc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(part), 0));
+  for (int l = 1; l < L; ++l)
+    acc = acc + __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(part), l));
+  return acc / (float)kk;
+}
+
+template <int DIM, int SLOTS, class COLS>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_wide_kernel(
     const float* __restrict__ pts, int64_t n_pts, const float* __restrict__ nodes, Levels lv,
     const int32_t* __restrict__ order, const float* __restrict__ verts, const float* __restrict__ weights, int k1, int R,
     int64_t n_cells, int k, int stat, const int32_t* __restrict__ sample_order, uint32_t* __restrict__ out_bits,
-    int32_t* __restrict__ out_ids, uint32_t* __restrict__ out_d2) {
+    int32_t* __restrict__ out_ids, uint32_t* __restrict__ out_d2, const COLS cols) {
   constexpr int DP = padded_dim(DIM);
   constexpr int CAP = 64 * SLOTS;
   __shared__ wkey_t s_list[WAVES_PER_BLOCK][CAP];
@@ -245,23 +278,16 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_wide_kernel(
       if (out_d2) out_d2[row + i] = (uint32_t)(key >> 32);
     }
     if (out_bits) {
-      float v;
-      if (stat == 0) {
-        v = __uint_as_float((uint32_t)(list[k - 1] >> 32));
+      if constexpr (std::is_same<COLS, NoCols>::value) {
+        const float v = wide_statistic(list, k, stat, lane);
+        if (lane == 0) out_bits[g] = __float_as_uint(v);
       } else {
-        // S_l = w_l + w_(l+64) + w_(l+128) + ... (positions < k), then S_0 + S_1 + ... + S_(min(k,64)-1): both sequential
-        // float32 sums in that order; for k <= 64 the plain ascending sequential sum of the value sweeps
-        float part = 0.f;
-        if (lane < k) {
-          part = __uint_as_float((uint32_t)(list[lane] >> 32));
-          for (int i = lane + 64; i < k; i += 64) part = part + __uint_as_float((uint32_t)(list[i] >> 32));
+        // the first k' keys of the list are the k' smallest: column c is the single call at (col_k[c], col_stat[c])
+        for (int c = 0; c < cols.n_cols; ++c) {
+          const float v = wide_statistic(list, cols.col_k[c], cols.col_stat[c], lane);
+          if (lane == 0) out_bits[(int64_t)c * cols.plane_stride + g] = __float_as_uint(v);
         }
-        float acc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(part), 0));
-        for (int l = 1; l < merge_at; ++l)   // (merge_at = min(k, 64): the lanes that hold a partial sum)
-          acc = acc + __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(part), l));
-        v = acc / (float)k;
       }
-      if (lane == 0) out_bits[g] = __float_as_uint(v);
     }
     lds_handoff();   // (every lane has read the list before the next cell resets it)
   }
@@ -269,33 +295,31 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_wide_kernel(
 
 template <int DIM>
 struct KnnWideOp {
-  template <int SLOTS>
-  static void launch(const flooder_knn_wide_t& a, const Levels& lv, int64_t n_cells, hipStream_t st) {
-    hipLaunchKernelGGL((knn_wide_kernel<DIM, SLOTS>), stack_walk_grid(n_cells), dim3(64 * WAVES_PER_BLOCK), 0, st,
+  template <int SLOTS, class COLS>
+  static void launch(const flooder_knn_wide_t& a, const COLS& cols, const Levels& lv, int64_t n_cells, hipStream_t st) {
+    hipLaunchKernelGGL((knn_wide_kernel<DIM, SLOTS, COLS>), stack_walk_grid(n_cells), dim3(64 * WAVES_PER_BLOCK), 0, st,
                        a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, n_cells, a.k, a.stat,
-                       a.sample_order, a.out_bits, a.out_ids, a.out_d2);
+                       a.sample_order, a.out_bits, a.out_ids, a.out_d2, cols);
   }
-  static int run(const flooder_knn_wide_t& a, const Levels& lv, int64_t n_cells, hipStream_t st) {
+  template <class COLS>
+  static int run(const flooder_knn_wide_t& a, const COLS& cols, const Levels& lv, int64_t n_cells, hipStream_t st) {
     if constexpr (DIM < 2) {
       return fail(FLOODER_E_ARG, "flooder_knn_wide_f32: dim must be in 2..8");
     } else {
       // the list capacity that holds k: 64, 128, 256, 512 or 1024 keys
-      if (a.k <= 64) launch<1>(a, lv, n_cells, st);
-      else if (a.k <= 128) launch<2>(a, lv, n_cells, st);
-      else if (a.k <= 256) launch<4>(a, lv, n_cells, st);
-      else if (a.k <= 512) launch<8>(a, lv, n_cells, st);
-      else launch<16>(a, lv, n_cells, st);
+      if (a.k <= 64) launch<1>(a, cols, lv, n_cells, st);
+      else if (a.k <= 128) launch<2>(a, cols, lv, n_cells, st);
+      else if (a.k <= 256) launch<4>(a, cols, lv, n_cells, st);
+      else if (a.k <= 512) launch<8>(a, cols, lv, n_cells, st);
+      else launch<16>(a, cols, lv, n_cells, st);
       return check_launch("knn_wide");
     }
   }
 };
 
-}  // namespace
-
-extern "C" int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream) {
-  static const char* who = "flooder_knn_wide_f32";
-  flooder_knn_wide_t a;
-  if (int rc = take(p, a, "flooder_knn_wide_f32: bad parameter block (abi / size)")) return rc;
+// The checks of both entries (the profile entry has made its column checks already) and the launch
+template <class COLS>
+int knn_wide(const char* who, const flooder_knn_wide_t& a, const COLS& cols, int64_t plane_stride, void* stream) {
   if (int rc = knn_check_ranges(who, a.k, FLOODER_KNN_WIDE_MAX, a.dim, a.stat, a.n_pts, true, true)) return rc;
   if (a.n_simplices > 0 && a.R > 0 && a.n_simplices > ((1LL << 32) - 3) / a.R)
     return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
@@ -304,8 +328,48 @@ extern "C" int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream) {
   if (!a.out_bits && !a.out_ids && !a.out_d2)
     return failf(FLOODER_E_ARG, "%s: no output (out_bits, out_ids and out_d2 are all NULL)", who);
   if (a.out_ids && !a.order) return failf(FLOODER_E_ARG, "%s: out_ids needs order (tree row -> original id)", who);
+  if (!std::is_same<COLS, NoCols>::value && a.n_simplices > 0 && a.R > 0 && plane_stride < a.n_simplices * (int64_t)a.R)
+    return failf(FLOODER_E_ARG, "%s: plane_stride must be at least n_simplices * R", who);
   if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || a.k1 < 1 || a.R < 0 || a.n_simplices < 0)
     return failf(FLOODER_E_ARG, "%s: bad argument (null pointer, k1, R, n_simplices)", who);
-  return dispatch_dim<KnnWideOp>(a.dim, a, lv, a.n_simplices * (int64_t)a.R, (hipStream_t)stream);
+  return dispatch_dim<KnnWideOp>(a.dim, a, cols, lv, a.n_simplices * (int64_t)a.R, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream) {
+  flooder_knn_wide_t a;
+  if (int rc = take(p, a, "flooder_knn_wide_f32: bad parameter block (abi / size)")) return rc;
+  return knn_wide("flooder_knn_wide_f32", a, NoCols{}, 0, stream);
+}
+
+extern "C" int flooder_knn_wide_profile_f32(const flooder_knn_wide_t* p, int n_cols, const int32_t* col_k,
+                                            const int32_t* col_stat, int64_t plane_stride, void* stream) {
+  static const char* who = "flooder_knn_wide_profile_f32";
+  flooder_knn_wide_t a;   // the walk of the single entry at k = the largest k of the columns
+  if (int rc = take(p, a, "flooder_knn_wide_profile_f32: bad parameter block (abi / size)")) return rc;
+  if (n_cols < 1 || n_cols > FLOODER_KNN_COLS_MAX)
+    return failf(FLOODER_E_ARG, "%s: n_cols must be in 1..%d", who, FLOODER_KNN_COLS_MAX);
+  if (!col_k || !col_stat) return failf(FLOODER_E_ARG, "%s: col_k and col_stat must not be NULL", who);
+  if (a.k < 1 || a.k > FLOODER_KNN_WIDE_MAX)
+    return failf(FLOODER_E_ARG, "%s: k must be in 1..%d", who, FLOODER_KNN_WIDE_MAX);
+  WideCols cols;
+  memset(&cols, 0, sizeof(cols));
+  cols.plane_stride = plane_stride;
+  cols.n_cols = n_cols;
+  int k_max = 0;
+  for (int c = 0; c < n_cols; ++c) {
+    const int k = col_k[c], s = col_stat[c];
+    if (k < 1 || k > a.k) return failf(FLOODER_E_ARG, "%s: col_k must be in 1..k", who);
+    if (s != 0 && s != 1) return failf(FLOODER_E_ARG, "%s: col_stat must be 0 (kth) or 1 (dtm)", who);
+    for (int b = 0; b < c; ++b)
+      if (col_k[b] == k && col_stat[b] == s)
+        return failf(FLOODER_E_ARG, "%s: a (k, stat) column is listed twice", who);
+    cols.col_k[c] = k;
+    cols.col_stat[c] = s;
+    if (k > k_max) k_max = k;
+  }
+  if (a.k != k_max) return failf(FLOODER_E_ARG, "%s: k must equal the largest col_k", who);
+  return knn_wide(who, a, cols, plane_stride, stream);
 }

@@ -271,6 +271,287 @@ struct PowerLaunch {
   }
 };
 
+// ---- several weight vectors in one walk (flooder_sweep_power_profile_f32; power_profile, dtm_profile) -------------
+//
+// node_min_cols: node_min_leaf_kernel / node_min_inner_kernel for nc interleaved columns - a thread (a wave) per
+// (node, column), the same minima, plain stores.
+__global__ __launch_bounds__(256) void node_min_cols_leaf_kernel(const float* __restrict__ vals, int64_t count,
+                                                                 int64_t padded, int nc, float* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= padded * nc) return;
+  const int64_t i = t / nc;
+  const int c = (int)(t - i * nc);
+  float m = __builtin_inff();
+  if (i < count) {
+    const float* v = vals + i * LEAF * nc + c;
+#pragma unroll
+    for (int q = 0; q < LEAF; ++q) m = __builtin_fminf(m, v[(int64_t)q * nc]);
+  }
+  out[t] = m;
+}
+
+__global__ __launch_bounds__(256) void node_min_cols_inner_kernel(const float* __restrict__ child, int64_t count,
+                                                                  int64_t padded, int nc, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= padded * nc) return;
+  const int64_t i = t / nc;
+  const int c = (int)(t - i * nc);
+  float m = __builtin_inff();
+  if (i < count) m = wave_min_f32(child[(i * FAN + lane) * nc + c]);
+  if (lane == 0) out[t] = m;
+}
+
+// sweep_power_profile<DIM, NC>: sweep_power_kernel with NC running minima per lane, NC = n_cols rounded up to 1, 2, 4
+// or 8 = the row length of w_cols and node_w_cols.  Per pair ONE dist2 chain, then fmaf(w_c, w_c, d2) and a min per
+// column: plane c holds the word sweep_power_kernel writes with column c's weights - a minimum does not depend on the
+// order of its elements, nor on further elements that are not below it.
+//
+// Binding rule.  With lb_c = fmaf(nw_c, nw_c, gap2) (nw_c = node_w_cols[node, c]) a child, a leaf or a level is skipped
+// only when !(lb_c * SAFE < bound_c) in EVERY column c < n_cols: bound_c = M[c], the largest running minimum of the
+// tile in column c (children, levels), or the lane's own best[c] (leaves).  What is visited beyond a column's own walk
+// offers it points that are not below its minimum.
+//   - a group of children is tested per lane when it is loaded: a child dead in every column gets gap +inf (the M[c]
+//     only shrink: it stays dead); the others keep their GEOMETRIC gap2, one float per child, in registers (leaf level)
+//     or in the LDS level stack (inner levels) - the stack is not multiplied by NC;
+//   - the walk takes the live child of the smallest gap2 first.  mn = that gap2 is a lower bound of every lb_c of every
+//     child left, so !(mn * SAFE < max_c M[c]) ends the level; else the child's own NC node weights come in by one
+//     scalar load and its columns are tested against the M[c] of NOW before it is opened.
+// Padding columns (n_cols <= c < NC) are LEFT OUT of every test - they never keep a node alive, whatever they hold
+// (flooder_amd fills them with +inf) - their minima are computed and thrown away, and no plane is written for them.
+// A leaf row's NC weights are loaded with the row (never all 16 rows and their weights at once: SGPRs).
+template <int DIM, int NC>
+__global__ __launch_bounds__(256) void sweep_power_profile_kernel(
+    const float* __restrict__ pts, const float* __restrict__ nodes, Levels lv, const float* __restrict__ verts,
+    const float* __restrict__ weights, int k1, int R, int64_t n_simplices, int32_t* __restrict__ queue,
+    uint32_t* __restrict__ out_bits, unsigned long long* __restrict__ stats, const uint32_t* __restrict__ order,
+    const float* __restrict__ w_cols, const float* __restrict__ node_w_cols, int n_cols) {
+  constexpr int DP = padded_dim(DIM);
+  __shared__ float s_lb[4][MAXL][FAN];
+  __shared__ int64_t s_grp[4][MAXL];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int tiles = (R + 63) / 64;
+  const int64_t n_samples = n_simplices * (int64_t)R;
+  const int64_t n_items = order ? (n_samples + 63) / 64 : n_simplices * tiles;
+  const int top = lv.n_levels - 1;
+  unsigned long long n_leaf_eval = 0, n_leaf_test = 0, n_node_test = 0, max_item_tests = 0;
+
+  int q_shard = (int)(((int64_t)blockIdx.x * 4 + wv) % QSHARDS), q_tried = 0;
+  for (;;) {
+    const int64_t g = queue_pop(queue, q_shard, q_tried, n_items, lane);  // sharded heads (flood_common.hpp)
+    if (g < 0) break;
+    const unsigned long long tests_before = n_leaf_test + n_node_test;
+    // ---- this lane's sample (s, r), as sweep_power_kernel takes it
+    int64_t s;
+    int r;
+    bool live;
+    if (order) {
+      const int64_t pos = g * 64 + lane;
+      live = pos < n_samples;
+      const uint32_t id = order[live ? pos : n_samples - 1];  // duplicate of the last entry, never stored
+      const uint32_t si = id / (uint32_t)R;
+      s = (int64_t)si;
+      r = (int)(id - si * (uint32_t)R);
+    } else {
+      s = g / tiles;
+      r = (int)(g - s * tiles) * 64 + lane;
+      live = r < R;
+      if (!live) r = R - 1;  // duplicate of the last sample, never stored
+    }
+    float p[DIM];
+    const float* vs = verts + s * (int64_t)k1 * DIM;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) p[c] = 0.f;
+    for (int j = 0; j < k1; ++j) {
+      const float w = weights[(int64_t)r * k1 + j];
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) p[c] = __builtin_fmaf(w, vs[j * DIM + c], p[c]);
+    }
+    int best[NC];   // (the int32 words of the floats: never negative, never NaN)
+    float M[NC];    // largest running minimum of the tile per column (wave-uniform)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      best[c] = (int)INF_BITS;
+      M[c] = __builtin_inff();
+    }
+    float Mmax = __builtin_inff();   // max over the real columns of M[c]
+
+    float tlo[DIM], thi[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      tlo[c] = wave_min_f32(p[c]);
+      thi[c] = wave_max_f32(p[c]);
+    }
+
+    // child `lane` of group `grp` at level `lvl`: its box (registers) and its geometric gap2 to the tile box, +inf when
+    // no real column can still gain below it (or the lane is past the end of the level)
+    float c_lo[DIM], c_hi[DIM];
+    auto child_gaps = [&](int lvl, int64_t grp) -> float {
+      const float gap2 = child_box_bound<DIM>(nodes, lv, lvl, grp, lane, tlo, thi, c_lo, c_hi);
+      float nw[NC];   // (a slot past the end of the level is padding of the node array: +inf in every column)
+      if constexpr (NC == 1) nw[0] = node_w_cols[lv.off[lvl] + grp * FAN + lane];
+      else load_row<NC>(node_w_cols + (lv.off[lvl] + grp * FAN + lane) * NC, nw);
+      bool alive = false;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < n_cols) alive = alive || __builtin_fmaf(nw[c], nw[c], gap2) * SAFE < M[c];
+      return alive ? gap2 : __builtin_inff();
+    };
+    // the node weights of ONE node (wave-uniform address): does any real column pass with the gap `gap2`?
+    auto node_alive = [&](int64_t node, float gap2) -> bool {
+      const typename RowVec<NC>::type nw = load_uniform_row<NC>(node_w_cols + node * NC);
+      bool alive = false;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < n_cols) alive = alive || __builtin_fmaf(nw[c], nw[c], gap2) * SAFE < M[c];
+      return alive;
+    };
+
+    int lvl = top;
+    float lb0 = child_gaps(top, 0);
+    int64_t grp0 = 0;
+    ++n_node_test;
+    if (top > 0) {
+      s_lb[wv][top][lane] = lb0;
+      if (lane == 0) s_grp[wv][top] = 0;
+    }
+    for (;;) {
+      if (lvl > 0) {
+        const float lbv = s_lb[wv][lvl][lane];
+        const float mn = wave_min_f32(lbv);
+        if (!(mn * SAFE < Mmax)) {  // nothing left at this level can lower a minimum of the tile in any column
+          if (++lvl > top) break;
+          continue;
+        }
+        const int j = __builtin_ctzll(__ballot(lbv == mn));
+        if (lane == j) s_lb[wv][lvl][lane] = __builtin_inff();  // visited
+        const int64_t c = wave_uniform64(s_grp[wv][lvl]) * FAN + j;
+        if (!node_alive(lv.off[lvl] + c, mn)) continue;   // (node c of this level) dead in every column by now
+        --lvl;
+        const float lb = child_gaps(lvl, c);
+        ++n_node_test;
+        if (lvl > 0) {
+          s_lb[wv][lvl][lane] = lb;
+          if (lane == 0) s_grp[wv][lvl] = c;
+        } else {
+          lb0 = lb;
+          grp0 = c;
+        }
+        continue;
+      }
+      // ---- leaf level: nearest unvisited live leaf of the current group
+      const float mn = wave_min_f32(lb0);
+      if (!(mn * SAFE < Mmax)) {
+        if (++lvl > top) break;
+        continue;
+      }
+      const int j = __builtin_ctzll(__ballot(lb0 == mn));
+      if (lane == j) lb0 = __builtin_inff();  // visited
+      const int64_t c = grp0 * FAN + j;
+      // the leaf's NC smallest weights (level 0 starts the node array; wave-uniform: one scalar load)
+      const typename RowVec<NC>::type wl = load_uniform_row<NC>(node_w_cols + c * NC);
+      ++n_leaf_test;
+      float lbp = 0.f;  // gap2 of the lane's own sample to the leaf's box (it comes from lane j)
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const float blo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_lo[a]), j));
+        const float bhi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_hi[a]), j));
+        const float gap = __builtin_fmaxf(__builtin_fmaxf(blo - p[a], p[a] - bhi), 0.f);
+        lbp = __builtin_fmaf(gap, gap, lbp);
+      }
+      bool gain = false;   // can this lane's minimum still drop in some real column?
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc)
+        if (cc < n_cols) gain = gain || __builtin_fmaf(wl[cc], wl[cc], lbp) * SAFE < __int_as_float(best[cc]);
+      if (__ballot(gain) == 0ull) continue;
+      ++n_leaf_eval;
+      const float* cp = pts + c * (int64_t)LEAF * DP;
+      const float* cw = w_cols + c * (int64_t)LEAF * NC;
+      // rows in SGPRs at a time, each with its NC weights: at most 48 scalar registers
+      constexpr int NB = (DP + NC) * 8 <= 48 ? 8 : ((DP + NC) * 4 <= 48 ? 4 : 2);
+      // (not unrolled for 8-float rows, as in sweep_power_kernel, nor for 8 columns: unrolled, <2..4, 8> moved 115 to 220
+      // scalar registers to vector lanes and ran 4 waves per SIMD - profiles/power_profile_kernel_resources.txt)
+      constexpr int UNROLL = DP == 8 || NC == 8 ? 1 : LEAF / NB;
+#pragma unroll UNROLL
+      for (int h = 0; h < LEAF; h += NB) {
+        typename RowVec<DP>::type xr[NB];
+        typename RowVec<NC>::type wr[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          xr[u] = load_uniform_row<DP>(cp + (h + u) * DP);
+          wr[u] = load_uniform_row<NC>(cw + (h + u) * NC);
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          float d;  // (dist2 of flood_bvh.hpp written out, then the weight of every column)
+#pragma unroll
+          for (int a = 0; a < DIM; ++a) {
+            const float t = p[a] - xr[u][a];
+            d = a == 0 ? t * t : __builtin_fmaf(t, t, d);
+          }
+#pragma unroll
+          for (int cc = 0; cc < NC; ++cc) {
+            const int di = __float_as_int(__builtin_fmaf(wr[u][cc], wr[u][cc], d));
+            best[cc] = di < best[cc] ? di : best[cc];
+          }
+        }
+      }
+      Mmax = 0.f;
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) {
+        M[cc] = wave_max_f32(__int_as_float(best[cc]));
+        if (cc < n_cols) Mmax = __builtin_fmaxf(Mmax, M[cc]);
+      }
+    }
+
+    if (live) {
+      const int64_t cell = s * (int64_t)R + r;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < n_cols) out_bits[c * n_samples + cell] = (uint32_t)best[c];
+    }
+    const unsigned long long item_tests = n_leaf_test + n_node_test - tests_before;
+    max_item_tests = item_tests > max_item_tests ? item_tests : max_item_tests;
+  }
+  if (stats && lane == 0 && (n_node_test | n_leaf_test) != 0ull) {
+    atomicMax(&stats[3], max_item_tests);
+    atomicAdd(&stats[0], n_leaf_eval);
+    atomicAdd(&stats[1], n_leaf_test);
+    atomicAdd(&stats[2], n_node_test);
+  }
+}
+
+template <int DIM>
+struct PowerProfileLaunch {
+  template <int NC>
+  static void launch(const flooder_knn_sorted_t& a, int n_cols, const float* w_cols, const float* node_w_cols,
+                     const Levels& lv, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((sweep_power_profile_kernel<DIM, NC>), grid, dim3(256), 0, st, a.pts_sorted, a.nodes, lv, a.verts,
+                       a.weights, a.k1, a.R, a.n_simplices, a.queue, a.out_bits,
+                       reinterpret_cast<unsigned long long*>(a.stats),
+                       reinterpret_cast<const uint32_t*>(a.sample_order), w_cols, node_w_cols, n_cols);
+  }
+  static int run(const flooder_knn_sorted_t& a, int n_cols, const float* w_cols, const float* node_w_cols,
+                 const Levels& lv, hipStream_t st) {
+    if constexpr (DIM < 2) {
+      return fail(FLOODER_E_ARG, "dim must be in 2..8");
+    } else {
+      const int64_t n_items = a.sample_order ? (a.n_simplices * (int64_t)a.R + 63) / 64
+                                             : a.n_simplices * ((a.R + 63) / 64);
+      int64_t grid = g_bvh_grid;  // persistent blocks; 4 independent waves each
+      if (grid > (n_items + 3) / 4) grid = (n_items + 3) / 4;
+      const dim3 gd((unsigned)grid);
+      // the row length of w_cols / node_w_cols: n_cols rounded up to 1, 2, 4 or 8
+      if (n_cols <= 1) launch<1>(a, n_cols, w_cols, node_w_cols, lv, gd, st);
+      else if (n_cols <= 2) launch<2>(a, n_cols, w_cols, node_w_cols, lv, gd, st);
+      else if (n_cols <= 4) launch<4>(a, n_cols, w_cols, node_w_cols, lv, gd, st);
+      else launch<8>(a, n_cols, w_cols, node_w_cols, lv, gd, st);
+      return check_launch("sweep_power_profile");
+    }
+  }
+};
+
 // One wave per query; the stack holds groups of 64 sibling nodes (level, group) as in witness_search_kernel
 // (flood_grad.hip: the pop, the push and the four-leaf step are its steps; keep in step).
 template <int DIM>
@@ -430,6 +711,43 @@ extern "C" int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const floa
   if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
     return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
   return dispatch_dim<PowerLaunch>(a.dim, a, w_sorted, node_w, make_levels(a.n_pts), (hipStream_t)stream);
+}
+
+extern "C" int flooder_node_min_cols_f32(const float* leaf_vals, int64_t n_pts, int nc, float* node_min, void* stream) {
+  if (!leaf_vals || !node_min || n_pts < 1 || nc < 1 || nc > FLOODER_POWER_COLS_MAX)
+    return fail(FLOODER_E_ARG, "flooder_node_min_cols_f32: bad argument (null pointer, n_pts < 1, nc outside 1..8)");
+  const Levels lv = make_levels(n_pts);
+  hipStream_t st = (hipStream_t)stream;
+  for (int l = 0; l < lv.n_levels; ++l) {
+    const int64_t padded = (lv.count[l] + FAN - 1) / FAN * FAN;
+    float* out = node_min + lv.off[l] * nc;
+    if (l == 0)
+      hipLaunchKernelGGL(node_min_cols_leaf_kernel, dim3((unsigned)((padded * nc + 255) / 256)), dim3(256), 0, st,
+                         leaf_vals, lv.count[0], padded, nc, out);
+    else
+      hipLaunchKernelGGL(node_min_cols_inner_kernel, dim3((unsigned)((padded * nc + 3) / 4)), dim3(256), 0, st,
+                         node_min + lv.off[l - 1] * nc, lv.count[l], padded, nc, out);
+  }
+  return check_launch("node_min_cols");
+}
+
+extern "C" int flooder_sweep_power_profile_f32(const flooder_knn_sorted_t* p, int n_cols, const float* w_cols,
+                                               const float* node_w_cols, void* stream) {
+  static const char* who = "flooder_sweep_power_profile_f32";
+  flooder_knn_sorted_t a;
+  if (int rc = take(p, a, "flooder_sweep_power_profile_f32: bad parameter block (abi / size)")) return rc;
+  if (n_cols < 1 || n_cols > FLOODER_POWER_COLS_MAX)
+    return failf(FLOODER_E_ARG, "%s: n_cols must be in 1..%d", who, FLOODER_POWER_COLS_MAX);
+  if (int rc = knn_check_ranges(who, a.k, 1, a.dim, a.stat, a.n_pts, false, false)) return rc;
+  if (a.stat != 0 || a.reserved != 0) return failf(FLOODER_E_ARG, "%s: stat and reserved must be 0", who);
+  if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
+  if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || !a.queue || !a.out_bits || !w_cols || !node_w_cols ||
+      a.n_pts < 1 || a.k1 < 1 || a.k1 > FLOODER_MAX_VERTS || a.R < 0 || a.n_simplices < 0)
+    return failf(FLOODER_E_ARG, "%s: bad argument (null pointer, no points, k1, R)", who);
+  if (a.n_simplices > 0xfffffffeLL || a.n_simplices * (int64_t)a.R > 0xfffffffdLL)   // (ids are 32-bit words)
+    return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
+  return dispatch_dim<PowerProfileLaunch>(a.dim, a, n_cols, w_cols, node_w_cols, make_levels(a.n_pts),
+                                          (hipStream_t)stream);
 }
 
 extern "C" int flooder_witness_power(const flooder_witness_search_t* p, const float* w_sorted, const float* node_w,

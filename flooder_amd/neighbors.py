@@ -182,19 +182,7 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
     on_gpu = _check_points(points, "distance_to_measure")
     if (mass is None) == (neighbors is None):
         raise ValueError("distance_to_measure needs exactly one of mass and neighbors")
-    core._check_neighbor_stat(neighbor_stat)
-    n = points.shape[0]
-    if mass is not None:
-        k, _ = core._check_robust(points, 1, neighbor_stat, mass, None, queries=True)
-    else:
-        if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
-            raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
-        k = int(neighbors)
-        if not 1 <= k <= core.KNN_WIDE_MAX:
-            raise ValueError(f"neighbors must be in 1..{core.KNN_WIDE_MAX} (KNN_WIDE_MAX: the k best of a query live in "
-                             f"the LDS of one wave), got {k}")
-    if k > n:
-        raise ValueError(f"neighbors={k} exceeds the number of points ({n})")
+    k = _measure_neighbors(points, mass, neighbors, neighbor_stat)
     own = queries is None
     queries = _check_queries_and_index(points, queries, index, on_gpu)
     with_grad = bool(differentiable) and torch.is_grad_enabled() and (points.requires_grad or queries.requires_grad)
@@ -215,6 +203,125 @@ def distance_to_measure(points: torch.Tensor, queries: Optional[torch.Tensor] = 
         value = _DistanceToMeasure.apply(grad_points, None if own else grad_queries, value, saved, neighbor_stat,
                                          bool(squared))
     return (value, *_neighbor_pair(points, ids, dist, squared)) if return_neighbors else value
+
+
+def _measure_neighbors(points: torch.Tensor, mass, neighbors, neighbor_stat) -> int:
+    """k of ``distance_to_measure`` from ONE of ``mass`` and ``neighbors`` (the other None), judged in its wording."""
+    core._check_neighbor_stat(neighbor_stat)
+    n = points.shape[0]
+    if mass is not None:
+        k, _ = core._check_robust(points, 1, neighbor_stat, mass, None, queries=True)
+    else:
+        if isinstance(neighbors, bool) or not isinstance(neighbors, Integral):
+            raise TypeError(f"neighbors must be an integer, got {neighbors!r}")
+        k = int(neighbors)
+        if not 1 <= k <= core.KNN_WIDE_MAX:
+            raise ValueError(f"neighbors must be in 1..{core.KNN_WIDE_MAX} (KNN_WIDE_MAX: the k best of a query live in "
+                             f"the LDS of one wave), got {k}")
+    if k > n:
+        raise ValueError(f"neighbors={k} exceeds the number of points ({n})")
+    return k
+
+
+def _measure_columns(points: torch.Tensor, masses, neighbors, neighbor_stat, who: str):
+    """The columns of a mass profile: exactly one of ``masses`` and ``neighbors`` (a value or a non-empty sequence), every
+    entry judged by ``_measure_neighbors`` with every name of ``neighbor_stat`` (a name or a non-empty sequence of
+    distinct names) -> (ks, stats, columns ``[(k, s) for k in ks for s in stats]``, the masses aligned with the columns
+    or None)."""
+    if (masses is None) == (neighbors is None):
+        raise ValueError(f"{who} needs exactly one of masses and neighbors")
+    by_mass = masses is not None
+    given = masses if by_mass else neighbors
+    name = "masses" if by_mass else "neighbors"
+    if isinstance(given, (str, bytes)):
+        raise TypeError(f"{name} must be a number or a sequence of numbers, got {given!r}")
+    entries = list(given) if hasattr(given, "__iter__") else [given]
+    stats = [neighbor_stat] if isinstance(neighbor_stat, str) or not hasattr(neighbor_stat, "__iter__") else list(neighbor_stat)
+    if not entries:
+        raise ValueError(f"{name} must not be empty")
+    if not stats:
+        raise ValueError("neighbor_stat must not be empty")
+    ks = []
+    for e in entries:
+        for stat in stats:
+            k = _measure_neighbors(points, e if by_mass else None, None if by_mass else e, stat)
+        ks.append(k)
+    if len(set(ks)) != len(ks):
+        raise ValueError(f"{name} lists a value twice: {entries!r} gives k = {ks!r}")
+    if len(set(stats)) != len(stats):
+        raise ValueError(f"neighbor_stat lists a name twice: {stats!r}")
+    columns = [(k, s) for k in ks for s in stats]
+    aligned = tuple(float(m) for m in entries for _ in stats) if by_mass else None
+    return ks, stats, columns, aligned
+
+
+def distance_to_measure_profile(points: torch.Tensor, queries: Optional[torch.Tensor] = None, masses=None, *,
+                                neighbors=None, neighbor_stat="dtm", squared: bool = False,
+                                index: Optional[core.PointIndex] = None) -> torch.Tensor:
+    """``distance_to_measure`` for several masses from ONE pass over the queries -> (Q, n_cols) tensor of ``points``'
+    dtype on its device.
+
+    Exactly one of ``masses`` and ``neighbors`` (a value or a non-empty sequence) is given; ``neighbor_stat`` is a name
+    or a sequence of names.  Every entry is judged as ``distance_to_measure`` judges it, in its words, before any work
+    is done; two entries that give the same k are refused ("lists a value twice").  The columns are
+    ``[(k, s) for k in ks for s in stats]`` and column c is ``torch.equal`` to ``distance_to_measure(points, queries,
+    neighbors=k_c, neighbor_stat=s_c, squared=squared)``.  ``queries`` (None: the cloud's own points), ``index`` and the
+    checks on them are those of ``neighbor_distance``; Q = 0 gives an empty (0, n_cols) tensor.  Detached, not
+    differentiable (``distance_to_measure(differentiable=True)`` with one mass is).
+
+    ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_knn_wide_profile_f32``: ONE wide sweep per group of queries
+    at the largest k, no ids - the list a wave ends with holds the k_max smallest keys ascending, its first k' entries
+    are the k' smallest, and both statistics are fixed by the sorted words alone.  The price is that of the one call
+    at the largest k.  At most 64 columns.  CPU tensors (float32, float64; any dimension): one kd-tree query at the
+    largest k, the statistic of the leading k' distances per column."""
+    on_gpu = _check_points(points, "distance_to_measure")
+    ks, stats, columns, _ = _measure_columns(points, masses, neighbors, neighbor_stat, "distance_to_measure_profile")
+    if on_gpu and len(columns) > _native.KNN_COLS_MAX:
+        raise ValueError(f"distance_to_measure_profile on ROCm tensors takes at most {_native.KNN_COLS_MAX} columns, got "
+                         f"{len(columns)}")
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    points, queries = points.detach(), queries.detach()
+    Q, n_cols = queries.shape[0], len(columns)
+    if Q == 0:
+        return torch.empty((0, n_cols), dtype=points.dtype, device=points.device)
+    if on_gpu:
+        bits = _query_profile_hip(points, queries, columns, index)                     # (n_cols, Q) int32
+        value = _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
+        return value.t().contiguous()
+    dist, _ = _kdtree_query(points, queries, max(ks))
+    # (scipy's k' nearest are the first k' of its k_max)
+    return torch.stack([_cpu_statistic(dist[:, :k], k, s, squared).to(points.dtype) for k, s in columns], dim=1)
+
+
+def _query_profile_hip(points: torch.Tensor, queries: torch.Tensor, columns, index: Optional[core.PointIndex]):
+    """``_query_sweep_hip`` in its wide form for every (k, stat) of ``columns`` at once -> (n_cols, Q) int32 words of the
+    squared statistics.  Per group of queries (24 B of keys, orders and sort scratch + 4 B per column each, within
+    ``core.SORTED_WORKSPACE_BYTES``) ONE ``flooder_knn_wide_profile_f32`` at the largest k; a group's slice of a plane
+    is contiguous, its planes are Q words apart: the entry's ``plane_stride``."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    q = queries.detach().contiguous()
+    Q, dim = q.shape
+    cols = [(int(k), core.NEIGHBOR_STATS.index(s)) for k, s in columns]
+    k_max = max(k for k, _ in cols)
+    n_cols, col_k, col_stat = _native.column_arrays(cols)
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    bits = torch.empty((len(cols), Q), dtype=torch.int32, device=dev)
+    key_bits = int(lib.flooder_sample_key_bits(dim))
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // (24 + 4 * len(cols)), (1 << 32) - 3))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
+        _, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnWide(k=k_max, stat=0, sample_order=order, out_bits=_native.ptr(bits) + 4 * a,
+                              **core._knn_block_fields(index, verts, one))
+        _native.check(lib.flooder_knn_wide_profile_f32(ctypes.byref(blk), n_cols, col_k, col_stat, Q, st),
+                      "flooder_knn_wide_profile_f32")
+    return bits
 
 
 def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: Optional[torch.Tensor] = None, *,

@@ -131,6 +131,148 @@ def _check_columns(points: torch.Tensor, neighbors, neighbor_stat, method):
     return checked, stats, columns, knn_method
 
 
+def power_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], point_weights: torch.Tensor,
+                  max_dimension: Optional[int] = None, points_per_edge: Optional[int] = 30,
+                  num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, return_simplex_tree: bool = False,
+                  method: Optional[str] = None, index: Optional["core.PointIndex"] = None) -> FloodProfile:
+    """The weighted Flood filtration for every column of ``point_weights`` (N, M), from one pass: for every c,
+
+        ``prof[c] == flood_complex(points, landmarks, max_dimension, points_per_edge, num_rand, start_idx=start_idx,
+        point_weights=point_weights[:, c], method=method, index=index, return_simplex_tree=return_simplex_tree)``
+
+    exactly - ROCm and CPU tensors; with ``num_rand`` under the same seed of the global CPU generator; with
+    ``return_simplex_tree=True`` the per-dimension simplex and filtration arrays are equal.  ``columns`` is
+    ``((0, "power"), ..., (M - 1, "power"))``; ``prof[i]`` and ``table(d)`` as in ``flood_profile``.
+
+    Every column is judged as ``flood_complex`` judges its ``point_weights``, before any work is done.  One landmark
+    selection, one Delaunay complex, one point index, one sample plan per dimension.  ROCm float32 tensors in 2 to 8
+    dimensions sweep the columns in groups of at most 8 (``flooder_sweep_power_profile_f32``: one walk of the tree, one
+    squared distance per pair, one fma and one minimum per column), the simplices of a dimension in groups within
+    ``core.PROFILE_WORKSPACE_BYTES``; the weights must be finite (not checked).  CPU tensors: one lifted kd-tree per
+    column.  Not differentiable, not sharded, no hooks (``flood_complex`` / ``power_filtration`` with one column)."""
+    if not isinstance(point_weights, torch.Tensor) or point_weights.dim() != 2 or point_weights.shape[1] == 0:
+        got = tuple(point_weights.shape) if isinstance(point_weights, torch.Tensor) else type(point_weights).__name__
+        n = points.shape[0] if isinstance(points, torch.Tensor) and points.dim() == 2 else "N"
+        raise ValueError(f"point_weights must be a ({n}, M) tensor, one column of weights per filtration (M >= 1), got "
+                         f"{got}")
+    n_cols = point_weights.shape[1]
+    for c in range(n_cols):
+        bvh = core._check_point_weights(points, point_weights[:, c], method)
+    columns = [(c, "power") for c in range(n_cols)]
+    return _power_profile(points, landmarks, point_weights, columns, max_dimension, points_per_edge, num_rand, start_idx,
+                          return_simplex_tree, bvh, index)
+
+
+def _power_profile(points, landmarks, point_weights, columns, max_dimension, points_per_edge, num_rand, start_idx,
+                   return_simplex_tree, method, index) -> FloodProfile:
+    """The body of ``power_profile`` and ``dtm_profile`` (checked weights (N, M), ``method`` as
+    ``core._check_point_weights`` returned it); it follows ``flood_profile``."""
+    if method != "bvh":
+        raise ValueError(f"method must be 'cell', 'bvh' or 'ball', got {method!r}")
+    if points.dtype not in core.SUPPORTED_DTYPES:
+        raise TypeError(f"dtype ({points.dtype}) not supported")
+    if points.device.type not in ("cuda", "cpu"):
+        raise RuntimeError("Device not supported.")
+    on_gpu = points.is_cuda
+    n_cols = len(columns)
+    if max_dimension is None:
+        max_dimension = points.shape[1]
+    if index is not None:
+        core._check_index(index, points, on_gpu, "ROCm tensors")
+    if on_gpu:
+        _native.load()   # raises ImportError with the build hint: no fallback
+        torch.cuda.set_device(points.device)
+        if index is None:
+            index = core._recall_index(points)
+            if index is None:
+                index = core.PointIndex(points.to(torch.float32))
+                core._remember_index(points, index)
+    if isinstance(landmarks, Integral):
+        landmarks = core.generate_landmarks(points, min(int(landmarks), points.shape[0]), None, start_idx=start_idx,
+                                            index=index)
+    core._check_landmarks(landmarks, points)
+
+    lm_host = landmarks.detach().cpu().numpy()
+    tree, simplices = core._cell_complex(delaunay_cells(lm_host), lm_host.shape[0], max_dimension)
+    items = [[] for _ in columns]
+    if on_gpu:
+        # the weights in tree-row order and their node minima, once per call: per column, or interleaved per group of 8
+        w = point_weights.detach()
+        single = core._power_weights(index, w[:, 0]) if n_cols == 1 else None
+        groups = [] if n_cols == 1 else [(min(core.POWER_COLS_MAX, n_cols - a),
+                                          *core._power_weight_columns(index, w[:, a:a + core.POWER_COLS_MAX]))
+                                         for a in range(0, n_cols, core.POWER_COLS_MAX)]
+        passes = core._dimension_passes(simplices, landmarks.detach().to(torch.float32), core._widest_axis(points, index.box),
+                                        points_per_edge, num_rand, "tree")
+    else:
+        from scipy.spatial import KDTree
+
+        pts_np = np.asarray(points.detach())
+        w_np = np.asarray(point_weights.detach().abs())
+        # (|p - x|^2 + w_x^2 is the squared distance from (p, 0) to the lifted point (x, |w_x|))
+        kdtrees = [KDTree(np.concatenate([pts_np, w_np[:, c:c + 1]], axis=1)) for c in range(n_cols)]
+        passes = core._dimension_passes(simplices, landmarks.detach(), core._widest_axis(points), points_per_edge,
+                                        num_rand, "ball")
+    for p in passes:
+        if on_gpu and n_cols == 1:
+            face_cols = [core._sweep_dimension_power(index, p.verts, p.weights, p.faces, *single, plan=p.plan)[0]]
+        elif on_gpu:
+            face_cols = core._sweep_dimension_power_profile(index, p.verts, p.weights, p.faces, groups, plan=p.plan)
+        else:
+            samples = p.weights.unsqueeze(0) @ p.verts
+            lifted = np.asarray(torch.cat([samples, samples.new_zeros(samples.shape[:-1] + (1,))], dim=-1))
+            face_cols = [core._face_max_cpu(torch.as_tensor(kd.query(lifted, workers=core.CPU_WORKERS)[0]), p.faces)
+                         for kd in kdtrees]
+        for c, face in enumerate(face_cols):
+            items[c] += core._handoff_items(tree, p, face.cpu().numpy().astype(np.float64))
+    trees = []
+    for c in range(n_cols):
+        trees.append(_clone_tree(tree))
+        core._apply_items(trees[c], items[c])
+        trees[c].make_filtration_non_decreasing()
+    return FloodProfile(columns, trees, None, return_simplex_tree)
+
+
+def dtm_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], masses=None,
+                max_dimension: Optional[int] = None, points_per_edge: Optional[int] = 30,
+                num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, neighbors=None, neighbor_stat="dtm",
+                return_simplex_tree: bool = False, method: Optional[str] = None,
+                index: Optional["core.PointIndex"] = None) -> FloodProfile:
+    """The DTM-weighted Flood filtration for every mass of a list, from one pass: ``power_profile`` with
+    ``distance_to_measure_profile(points, masses=masses, neighbors=neighbors, neighbor_stat=neighbor_stat)`` as its
+    weights.  For every column ``(k, stat)`` of ``prof.columns`` (``[(k, s) for k in ks for s in stats]``, k the
+    neighbours of a mass),
+
+        ``prof[(k, stat)] == flood_complex(points, landmarks, ..., point_weights=distance_to_measure(points,
+        neighbors=k, neighbor_stat=stat))``
+
+    exactly.  ``prof.masses``: the caller's masses aligned with the columns, ``None`` when called with ``neighbors``.
+    Exactly one of ``masses`` and ``neighbors`` is given; every entry is judged as ``distance_to_measure`` judges it.
+    One ``PointIndex`` serves the weights, the landmark selection and the sweep; the weights cost one wide k-nearest
+    sweep at the largest k, the filtrations one weighted sweep per group of 8 columns.  What a scan over the mass is
+    for: choosing it (README, "Choosing the mass")."""
+    from .neighbors import _check_points, _measure_columns, distance_to_measure_profile
+
+    on_gpu = _check_points(points, "distance_to_measure")
+    _, _, columns, aligned = _measure_columns(points, masses, neighbors, neighbor_stat, "dtm_profile")
+    if method in ("cell", "ball"):   # (before the weights are computed; the other refusals of the weighted sweep are
+        raise ValueError(core._POWER_REFUSALS["method"].format(method=method))   # _check_points' for these tensors)
+    bvh = "bvh" if method is None or method == "auto" else method
+    if index is not None:
+        core._check_index(index, points, on_gpu, "ROCm tensors")
+    if on_gpu and index is None:
+        index = core._recall_index(points)
+        if index is None:
+            index = core.PointIndex(points.to(torch.float32))
+            core._remember_index(points, index)
+    weights = distance_to_measure_profile(points, None, masses, neighbors=neighbors, neighbor_stat=neighbor_stat,
+                                          index=index)
+    prof = _power_profile(points, landmarks, weights, columns, max_dimension, points_per_edge, num_rand, start_idx,
+                          return_simplex_tree, bvh, index)
+    prof.masses = aligned
+    return prof
+
+
 def flood_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], max_dimension: Optional[int] = None,
                   points_per_edge: Optional[int] = 30, num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *,
                   neighbors=(1, 2, 4, 8, 16, 32), neighbor_stat="kth", return_simplex_tree: bool = False,

@@ -1102,6 +1102,29 @@ typedef struct flooder_knn_wide_s {         /* flooder_knn_wide_f32 */
 int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream);
 
 /*
+ * flooder_knn_wide_profile_f32: ONE walk of flooder_knn_wide_f32 at k = max(col_k) that writes a plane of its
+ * statistic words for every listed (k, stat) column (flooder_amd.distance_to_measure_profile).  A wave ends a cell with
+ * the k smallest keys ascending in LDS; the first t of them are the t smallest keys, and both statistics are fixed by
+ * the sorted words alone - so
+ *   out_bits[c * plane_stride + g]
+ * equals, word for word, what flooder_knn_wide_f32 with k = col_k[c], stat = col_stat[c] writes to out_bits[g] (stat 1:
+ * the strided sum over the positions < col_k[c] with L = min(col_k[c], 64), then / (float)col_k[c]).  The block is that
+ * of flooder_knn_wide_f32 (the form of flooder_sweep_power_f32: an existing block plus what the entry adds); its k is
+ * max(col_k), its stat is not used (the columns carry theirs) and must still be 0 or 1.  col_k and col_stat are HOST
+ * arrays of n_cols int32 each, read before the launch and not kept.  plane_stride counts words and is at least
+ * n_simplices * R: a driver that works in groups of cells hands over a slice of a (n_cols, Q) buffer, whose planes are
+ * Q words apart; the words between the planes are never touched.  The traversal, the insertion, sample_order, order,
+ * out_ids and out_d2 (rows of k = max(col_k) entries, both optional) are those of flooder_knn_wide_f32; the list
+ * capacity is chosen from k.
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a device pointer is read: what
+ * flooder_knn_wide_f32 refuses (all three outputs NULL included), and: n_cols outside 1..FLOODER_KNN_COLS_MAX; col_k or
+ * col_stat NULL; a col_k outside 1..k; a col_stat that is not 0 or 1; a (k, stat) pair listed twice; k != max(col_k);
+ * plane_stride < n_simplices * R.  Then n_simplices == 0 or R == 0: FLOODER_OK, nothing is touched.
+ */
+int flooder_knn_wide_profile_f32(const flooder_knn_wide_t* p, int n_cols, const int32_t* col_k, const int32_t* col_stat,
+                                 int64_t plane_stride, void* stream);
+
+/*
  * ---- Weighted filtration: the power distance (csrc/flood_power.hip; flood_complex(point_weights=w)) ----------------
  * Every point x carries a weight w_x >= 0 and a sample p is measured by f(p)^2 = min_x ( |p - x|^2 + w_x^2 ).
  *
@@ -1147,6 +1170,38 @@ int flooder_knn_wide_f32(const flooder_knn_wide_t* p, void* stream);
 int flooder_witness_power(const flooder_witness_search_t* p, const float* w_sorted, const float* node_w, void* stream);
 int flooder_node_min_f32(const float* leaf_vals, int64_t n_pts, float* node_min, void* stream);
 int flooder_sweep_power_f32(const flooder_knn_sorted_t* p, const float* w_sorted, const float* node_w, void* stream);
+
+/*
+ * The same sweep for several weight vectors in ONE walk of the tree (flooder_amd.power_profile, dtm_profile).
+ *
+ * flooder_node_min_cols_f32: flooder_node_min_f32 for nc interleaved columns, nc in 1..FLOODER_POWER_COLS_MAX.
+ *   leaf_vals  (n_pad, nc): the nc values of a tree row are contiguous; the rows of the padded last leaf hold +inf.
+ *   node_min   (flooder_bvh_node_count of n_pts, nc): node_min[node * nc + c] is what flooder_node_min_f32 writes to
+ *              node_min[node] for column c, padding slots +inf.
+ * One launch per level, plain vector stores, no atomics.  Refused: a NULL pointer, n_pts < 1, nc out of range.
+ *
+ * flooder_sweep_power_profile_f32: the block is that of flooder_sweep_power_f32 (k 1, stat 0, reserved 0), out_bits
+ * holds n_cols planes (n_cols, n_simplices, R) with 64-bit plane offsets, and out_bits[c, s, r] equals, word for word,
+ * what flooder_sweep_power_f32 writes to out_bits[s, r] with column c of the weights, for any tree, sample order (NULL
+ * and sorted, as there) and tile company.  NC = n_cols rounded up to 1, 2, 4 or 8 is the row length of both arrays:
+ *   w_cols       (n_pad, NC): |w| of column c of tree row i at w_cols[i * NC + c], pad rows +inf;
+ *   node_w_cols  flooder_node_min_cols_f32 of w_cols with nc = NC.
+ * The columns c >= n_cols are padding: they enter no test and no plane is written for them, whatever they hold.  Per
+ * pair one squared distance and per column one fmaf(w_c, w_c, d2) and one minimum; per child and per leaf one gap and
+ * per column one bound fmaf(nw_c, nw_c, gap2).  A child, a leaf or a level is skipped only when the test of
+ * flooder_sweep_power_f32, !(lb_c * SAFE < bound_c), fails in EVERY column c < n_cols - a minimum does not depend on
+ * which further points it was offered, so a column that is shown points it would have culled alone keeps its word.
+ * queue and stats as flooder_sweep_power_f32 (the counters are those of the one walk).
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), before a pointer is read: a bad block size or abi;
+ * n_cols outside 1..FLOODER_POWER_COLS_MAX; k != 1; dim outside 2..8; stat != 0; reserved != 0.  Then n_simplices == 0
+ * or R == 0: FLOODER_OK, nothing is touched.  Then: a NULL pointer (w_cols and node_w_cols included; sample_order and
+ * stats may be NULL), n_pts < 1, k1, n_simplices * R >= 2^32 - 2.
+ */
+#define FLOODER_POWER_COLS_MAX 8
+
+int flooder_node_min_cols_f32(const float* leaf_vals, int64_t n_pts, int nc, float* node_min, void* stream);
+int flooder_sweep_power_profile_f32(const flooder_knn_sorted_t* p, int n_cols, const float* w_cols,
+                                    const float* node_w_cols, void* stream);
 
 /*
  * ---- Backward of the distance to a measure (csrc/flood_dtm_grad.hip; distance_to_measure(differentiable=True)) -----
