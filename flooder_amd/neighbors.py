@@ -15,12 +15,16 @@ the queries.
 ``distance_to_measure`` speaks in MASS (k = mass * N, up to 1024 neighbours): ``flooder_knn_wide_f32``, one wave per query
 with its k best in LDS, values and neighbours; detached by default, with ``differentiable=True`` the closed form of
 ``neighbor_distance`` for every k, its backward two kernels of ``csrc/flood_dtm_grad.hip`` over the sweep's int32 ids.
+
+``distance_to_weighted_measure`` takes SITES WITH MASSES (the coreset of ``voxel_measure``) and a mass that may be far
+more than 1024 points: ``flooder_knn_mass_f32``, the wide kernel's walk up to the site at which the cumulative mass
+reaches the target.
 """
 
 from __future__ import annotations
 
 import ctypes
-from numbers import Integral
+from numbers import Integral, Real
 from typing import Optional, Tuple
 
 import numpy as np
@@ -322,6 +326,227 @@ def _query_profile_hip(points: torch.Tensor, queries: torch.Tensor, columns, ind
         _native.check(lib.flooder_knn_wide_profile_f32(ctypes.byref(blk), n_cols, col_k, col_stat, Q, st),
                       "flooder_knn_wide_profile_f32")
     return bits
+
+
+_CAPACITIES = (64, 128, 256, 512, 1024)   # the list capacities of flooder_knn_mass_f32 (and of the wide kernel)
+
+
+def _list_capacity(max_neighbors) -> int:
+    """``max_neighbors`` (None: ``core.KNN_WIDE_MAX``) rounded up to the capacity ladder 64, 128, 256, 512, 1024."""
+    if max_neighbors is None:
+        return core.KNN_WIDE_MAX
+    if isinstance(max_neighbors, bool) or not isinstance(max_neighbors, Integral):
+        raise TypeError(f"max_neighbors must be an integer, got {max_neighbors!r}")
+    if not 1 <= int(max_neighbors) <= core.KNN_WIDE_MAX:
+        raise ValueError(f"max_neighbors must be in 1..{core.KNN_WIDE_MAX} (KNN_WIDE_MAX: the neighbours of a query live "
+                         f"in the LDS of one wave), got {int(max_neighbors)}")
+    return next(c for c in _CAPACITIES if c >= int(max_neighbors))
+
+
+def _check_point_masses(points: torch.Tensor, point_masses) -> None:
+    n = points.shape[0]
+    if not isinstance(point_masses, torch.Tensor) or tuple(point_masses.shape) != (n,):
+        got = tuple(point_masses.shape) if isinstance(point_masses, torch.Tensor) else type(point_masses).__name__
+        raise ValueError(f"point_masses must be a ({n},) tensor, one mass per point, got {got}")
+    if point_masses.dtype != points.dtype:
+        raise ValueError(f"point_masses.dtype ({point_masses.dtype}) != points.dtype ({points.dtype})")
+    if point_masses.device != points.device:
+        raise ValueError(f"point_masses.device ({point_masses.device}) != points.device ({points.device})")
+    if not points.is_cuda:   # (on ROCm tensors a check would synchronise with the host: the caller's contract)
+        if not bool(torch.isfinite(point_masses).all()) or bool((point_masses < 0).any()):
+            raise ValueError("point_masses must be finite and non-negative")
+        if not float(point_masses.sum(dtype=torch.float64)) > 0.0:
+            raise ValueError("point_masses must have a positive total")
+
+
+def _mass_target(point_masses: torch.Tensor, mass: float) -> torch.Tensor:
+    """tau = mass * sum(point_masses) as a (1,) float64 tensor on the masses' device, without a host synchronisation.
+    A tau within 1e-12 relative of an integer is that integer: (k / N) * N is k, so that unit masses at ``mass=k / N``
+    cross at the k-th neighbour whatever the rounding of the product."""
+    tau = (point_masses.detach().sum(dtype=torch.float64) * float(mass)).reshape(1)
+    near = torch.round(tau)
+    return torch.where((near >= 1) & ((tau - near).abs() <= 1e-12 * tau), near, tau).contiguous()
+
+
+def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tensor, queries: Optional[torch.Tensor] = None,
+                                 mass: Optional[float] = None, *, neighbor_stat: str = "dtm", squared: bool = False,
+                                 max_neighbors: Optional[int] = None, return_neighbors: bool = False,
+                                 index: Optional[core.PointIndex] = None):
+    """Per query the distance to the WEIGHTED measure sum_i mu_i delta_(x_i) (x_i = ``points[i]``, mu_i =
+    ``point_masses[i]`` >= 0) at mass ``mass`` -> (Q,) tensor of ``points``' dtype on its device.
+
+    With T = sum mu_i and the target tau = ``mass`` * T (``mass``: a real number in (0, 1]; a tau within 1e-12 relative
+    of an integer is that integer), the sites are ordered per query by (distance, id); M_j = mu_(0) + ... + mu_(j) is
+    the cumulative mass and j* the first position with M_j* >= tau.  ``neighbor_stat="dtm"``: sqrt(( sum_(i < j*) mu_(i)
+    d_(i)^2 + (tau - M_(j*-1)) d_(j*)^2 ) / tau), the distance to the measure of Chazal, Cohen-Steiner and Merigot;
+    ``"kth"``: d_(j*), the radius at which the ball around the query holds the mass tau.  Sites of mass 0 are listed but
+    add nothing.  With unit masses and ``mass=k / N`` this is ``distance_to_measure(points, queries, neighbors=k)``.
+    ``squared=True`` returns the statistic before the root.
+
+    The number of neighbours j* + 1 differs from query to query and is NOT bounded by k = mass * (number of points the
+    sites stand for): a site of ``voxel_measure`` that stands for 20 points makes its entry count 20-fold, so a mass
+    that is thousands of points - above ``core.KNN_WIDE_MAX``, where ``distance_to_measure`` refuses - is tens of sites.
+    The DTM is stable: |d_(mu,m) - d_(nu,m)| <= W_2(mu, nu) / sqrt(m), and the coreset of cell size c is within
+    W_2 <= c * sqrt(d) of the cloud.  At most L neighbours are looked at, L = ``max_neighbors`` rounded up to 64, 128,
+    256, 512 or 1024 (default ``core.KNN_WIDE_MAX`` = 1024) - and at most the number of sites.  A query whose L nearest
+    sites do not hold the mass tau is NOT REACHED and gets +inf; this is documented, not raised (on ROCm tensors a check
+    would synchronise with the host - the policy of ``point_weights``): coarsen the coreset or lower the mass.
+
+    ``return_neighbors=True`` returns ``(value, ids (Q, L) int64, dist (Q, L), count (Q,) int64)``: per query its
+    first ``count`` = j* + 1 sites ascending by (distance, id) (not reached: all min(L, N) looked at), then -1 / +inf;
+    ``dist`` is squared with ``squared=True``.  ``queries`` (None: the sites themselves), ``index`` and the checks on them
+    are those of ``neighbor_distance``; Q = 0 gives empty results.  ``point_masses``: an (N,) tensor of the points' dtype
+    on their device; CPU tensors refuse non-finite or negative masses and a zero total, ROCm tensors are not checked (it
+    would synchronise): there these are the caller's contract.
+
+    ROCm tensors (float32, 2 to 8 dimensions; float64 is refused) run ``flooder_knn_mass_f32``: one wave per query, the
+    walk of the wide k-nearest kernel whose cull bound is the key at which the cumulative mass (a float64 scan) crosses
+    tau; exact in the sweeps' float32 arithmetic, ``"dtm"`` within (ceil(count / 64) + 67) * 2^-24 relative on the
+    squared value (``include/flooder_hip.h``); tau is formed on the device, only the argument checks synchronise.  With
+    integer masses (the coreset's counts) the crossing is exact.  CPU tensors (float32, float64; any dimension) query
+    scipy's kd-tree at min(L, N) neighbours and evaluate the rule in float64.
+
+    Not differentiable: inputs that require grad are used detached.  Out of scope here: gradients, ``dtm_filtration`` /
+    ``dtm_profile`` and ``flood_complex(neighbor_mass=...)`` over a weighted cloud (pass the result as ``point_weights``
+    instead: ``flood_complex(points, L, point_weights=w)``), sharding, a float64 kernel.
+    """
+    on_gpu = _check_points(points, "distance_to_weighted_measure")
+    core._check_neighbor_stat(neighbor_stat)
+    _check_point_masses(points, point_masses)
+    if mass is None:
+        raise ValueError("distance_to_weighted_measure needs mass (a real number in (0, 1])")
+    core.mass_neighbors(mass, 1)   # (the checks of a mass, in the family's wording)
+    cap = _list_capacity(max_neighbors)
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    points, point_masses, queries = points.detach(), point_masses.detach(), queries.detach()
+    Q = queries.shape[0]
+    if Q == 0:
+        value = torch.empty(0, dtype=points.dtype, device=points.device)
+        if not return_neighbors:
+            return value
+        return (value, *_no_neighbors(points, cap), torch.empty(0, dtype=torch.int64, device=points.device))
+    tau = _mass_target(point_masses, mass)
+    if on_gpu:
+        lib, st = _native.load(), _native.current_stream_ptr(points.device)
+        ids, d2, count, bits = _weighted_sweep_hip(points, point_masses, queries, tau, cap, neighbor_stat, index,
+                                                   return_neighbors)
+        value = _root_of_bits(lib, bits, squared, st)
+        if not return_neighbors:
+            return value
+        return value, ids.long(), _root_of_bits(lib, d2, squared, st), count.long()
+    value, ids, dist, count = _weighted_measure_cpu(points, point_masses, queries, float(tau[0]), cap, neighbor_stat,
+                                                    squared)
+    value = torch.as_tensor(value).to(points.dtype)
+    if not return_neighbors:
+        return value
+    return value, torch.as_tensor(ids), torch.as_tensor(dist).to(points.dtype), torch.as_tensor(count)
+
+
+def _weighted_measure_cpu(points, point_masses, queries, tau: float, cap: int, stat: str, squared: bool):
+    """The rule of ``distance_to_weighted_measure`` in float64 numpy over the kd-tree's min(cap, N) nearest -> (value
+    (Q,), ids (Q, cap) int64 padded with -1, dist (Q, cap) padded with +inf, count (Q,) int64)."""
+    Q, kq = queries.shape[0], min(cap, points.shape[0])
+    dist, ids = _kdtree_query(points, queries, kq)
+    dist = dist.astype(np.float64)
+    d2 = np.square(dist)
+    mu = np.asarray(point_masses, dtype=np.float64)[ids]
+    M = np.cumsum(mu, axis=1)
+    crossed = M >= tau
+    reached = crossed.any(axis=1)
+    j = np.argmax(crossed, axis=1)                                # the first crossing (0 where there is none)
+    rows = np.arange(Q)
+    if stat == "kth":
+        val = d2[rows, j]
+    else:
+        before = np.arange(kq)[None, :] < j[:, None]
+        m_prev = np.where(j > 0, M[rows, np.maximum(j - 1, 0)], 0.0)
+        val = ((mu * d2 * before).sum(axis=1) + (tau - m_prev) * d2[rows, j]) / tau
+    val = np.where(reached, val if squared else np.sqrt(val), np.inf)
+    count = np.where(reached, j + 1, kq).astype(np.int64)
+    listed = np.arange(cap)[None, :] < count[:, None]
+    out_ids = np.full((Q, cap), -1, dtype=np.int64)
+    out_dist = np.full((Q, cap), np.inf)
+    out_ids[:, :kq] = ids
+    out_dist[:, :kq] = d2 if squared else dist
+    out_ids[~listed] = -1
+    out_dist[~listed] = np.inf
+    return val, out_ids, out_dist, count
+
+
+def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: int, stat: str,
+                        index: Optional[core.PointIndex], want_neighbors: bool):
+    """``_query_sweep_hip``'s wide form for ``flooder_knn_mass_f32``: the same ``PointIndex``, the queries sorted by curve
+    key in groups (24 B of keys, orders and sort scratch, 8 B of value and count and, with ``want_neighbors``, 8 * cap
+    bytes of rows per query, within ``core.SORTED_WORKSPACE_BYTES``), one launch per group -> (ids (Q, cap) int32 or
+    None, their d2 words (Q, cap) int32 or None, count (Q,) int32, the words of the squared statistic (Q,) int32)."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    q = queries.contiguous()
+    Q, dim = q.shape
+    masses = point_masses.to(torch.float32).contiguous()
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    ids = torch.empty((Q, cap), dtype=torch.int32, device=dev) if want_neighbors else None
+    d2 = torch.empty((Q, cap), dtype=torch.int32, device=dev) if want_neighbors else None
+    count = torch.empty(Q, dtype=torch.int32, device=dev)
+    bits = torch.empty(Q, dtype=torch.int32, device=dev)
+    key_bits = int(lib.flooder_sample_key_bits(dim))
+    per_query = 24 + 8 + (8 * cap if want_neighbors else 0)
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // per_query, (1 << 32) - 3))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
+        _, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnWide(k=cap, stat=core.NEIGHBOR_STATS.index(stat), order=index.order32, sample_order=order,
+                              out_bits=bits[a:b], out_ids=None if ids is None else ids[a:b],
+                              out_d2=None if d2 is None else d2[a:b], **core._knn_block_fields(index, verts, one))
+        _native.check(lib.flooder_knn_mass_f32(ctypes.byref(blk), _native.ptr(masses), _native.ptr(tau), cap,
+                                               _native.ptr(count[a:b]), st), "flooder_knn_mass_f32")
+    return ids, d2, count, bits
+
+
+def voxel_measure(points: torch.Tensor, cell_size: float):
+    """The coreset of a cloud on a grid of cubes of edge ``cell_size`` -> (``sites`` (M, d), ``masses`` (M,)), both of
+    ``points``' dtype on its device: per occupied cell the centroid of its points and their number - the weighted
+    measure ``distance_to_weighted_measure`` takes, within W_2 <= cell_size * sqrt(d) of the cloud's empirical measure.
+
+    The cell of x is floor((x - min x) * (1 / cell_size)) per axis, in float64 (one multiplication by the reciprocal:
+    the same result on every device).  Rows are ascending by cell, axis 0 most significant.  Deterministic, with no
+    float atomics: the points are sorted by cell, their offsets inside the cell - fixed point, 36 fractional bits, so
+    a centroid is within 2^-37 of a cell of the float64 mean - are summed as INTEGERS (a cumulative sum and differences
+    at the cell boundaries: exact in any order), and the centroid is rounded once to ``points``' dtype.  Two runs, and
+    a CPU and a ROCm run, agree (sites to the last bit of float64 before that rounding).  One host synchronisation (the
+    number M of occupied cells) is taken.  Not differentiable: ``points`` is used detached.  Up to 2^27 points.
+    """
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0 or points.shape[1] == 0:
+        got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
+        raise RuntimeError(f"points must be a non-empty (N, d) tensor, got shape {got}")
+    if points.dtype not in core.SUPPORTED_DTYPES:
+        raise TypeError(f"dtype ({points.dtype}) not supported")
+    if isinstance(cell_size, bool) or not isinstance(cell_size, Real):
+        raise TypeError(f"cell_size must be a positive real number, got {cell_size!r}")
+    cell_size = float(cell_size)
+    if not (np.isfinite(cell_size) and cell_size > 0.0):
+        raise ValueError(f"cell_size must be positive and finite, got {cell_size!r}")
+    if points.shape[0] > 1 << 27:
+        raise ValueError(f"voxel_measure takes at most 2^27 points (the integer sums of a cell), got {points.shape[0]}")
+    x = points.detach().to(torch.float64)
+    lo = x.min(dim=0).values
+    scaled = (x - lo) * (1.0 / cell_size)
+    cell_f = torch.floor(scaled)
+    offs = torch.floor((scaled - cell_f) * float(1 << 36) + 0.5).to(torch.int64)      # 0 .. 2^36
+    cells, inverse, counts = torch.unique(cell_f.to(torch.int64), dim=0, return_inverse=True, return_counts=True)
+    by_cell = torch.sort(inverse.reshape(-1), stable=True).indices
+    sums = torch.cumsum(offs[by_cell], dim=0)                                          # int64: exact
+    ends = torch.cumsum(counts, dim=0)
+    last = sums[ends - 1]
+    total = last - torch.cat([torch.zeros_like(last[:1]), last[:-1]])
+    frac = total.to(torch.float64) / (counts.to(torch.float64).unsqueeze(1) * float(1 << 36))
+    sites = lo + (cells.to(torch.float64) + frac) * cell_size
+    return sites.to(points.dtype).contiguous(), counts.to(points.dtype)
 
 
 def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: Optional[torch.Tensor] = None, *,

@@ -1125,6 +1125,62 @@ int flooder_knn_wide_profile_f32(const flooder_knn_wide_t* p, int n_cols, const 
                                  int64_t plane_stride, void* stream);
 
 /*
+ * flooder_knn_mass_f32 (csrc/flood_knn_mass.hip; flooder_amd.distance_to_weighted_measure): the distance to a WEIGHTED
+ * measure sum_i mu_i delta_(x_i), mu_i = masses[i] >= 0 - the nearest sites of every cell up to the one at which their
+ * cumulative mass reaches tau = *target, however many that are, one WAVE per cell, the list in LDS.  The number of
+ * neighbours differs from cell to cell; a site that stands for 20 points makes its list entry count 20-fold, so a mass
+ * that is thousands of POINTS is tens of SITES.  flooder_knn_wide_f32 and its translation unit are untouched.
+ * Rule.  Per cell g = s * R + r the sample p, the d2 words and the keys (d2 word, id = order[row]) are those of
+ * flooder_knn_wide_f32, ascending: (w_0, id_0) < (w_1, id_1) < ...  M_j = mu_(id_0) + ... + mu_(id_j) in float64 and j*
+ * is the first position with M_j* >= tau (the "crossing"; ">=": a prefix sum that EQUALS tau crosses there).  Sites of
+ * mass 0 are listed and counted but add nothing.  The list has the length L = min(C, n_pts), C = capacity rounded up to
+ * 64, 128, 256, 512 or 1024 (n_pts < C is legal).  If the L smallest keys of the whole cloud do not reach tau the cell
+ * is NOT REACHED.  Unless NULL:
+ *   out_count[g]         j* + 1 (int32); not reached: L;
+ *   out_ids[g, 0..ld_out)  the ids of the first min(count, ld_out) keys, then -1; needs order;
+ *   out_d2[g, 0..ld_out)   their d2 words, then the word of +inf (0x7f800000);
+ *   out_bits[g]          the float32 bits of the SQUARED statistic; not reached: the word of +inf;
+ *     stat 0 ("kth")     w_j*: the squared radius at which the ball around p holds the mass tau;
+ *     stat 1 ("dtm")     ( sum_(i < j*) mu_i w_i + (tau - M_(j*-1)) w_j* ) / tau, computed as: the terms t_i = mu_i * w_i
+ *                        (i < j*) and t_j* = rho * w_j* with rho = (float)(tau - M_(j*-1)) (the subtraction in double,
+ *                        M_(-1) = 0), each ONE float32 product; the terms are added in the strided order of
+ *                        flooder_knn_wide_f32's stat 1 over kk = j* + 1 positions (S_l = t_l + t_(l+64) + ..., then
+ *                        S_0 + S_1 + ... + S_(min(kk,64)-1), both left to right in float32, each starting AS its first
+ *                        term, no fused multiply-add); the word is that sum / (float)tau, correctly rounded.
+ *                        All terms are >= 0, so the roundings add up: one per product, ceil(kk / 64) - 1 + 63 on
+ *                        the longest chain of additions, one for rho, one for (float)tau, one for the division -
+ *                        ceil(kk / 64) + 66 roundings of 2^-24 each; with the second-order terms and the float64
+ *                        roundings of M the word is within (ceil(kk / 64) + 67) * 2^-24 relative of the real-number
+ *                        value of the rule for the float32 masses and d2 words given (83 * 2^-24 at kk = 1024).
+ * With masses all 1.0f and an integer tau = k <= L every product is exact, rho = 1 and (float)tau = (float)k: out_bits,
+ * out_ids[:, :k] and out_d2[:, :k] are those of flooder_knn_wide_f32 at k, word for word, and the count is k.
+ * The crossing position is exact whenever the prefix sums are exactly representable in float64 - for every order of
+ * addition when the masses are integers with a total below 2^53 (a coreset's counts).  For other masses the order of
+ * the float64 additions is fixed (a scan over the 64 positions of a row, plus the carry of the rows before), so the
+ * result is the same run to run; where it is ambiguous which of two neighbouring positions crosses, rho is about 0 and
+ * both readings give the same value up to rounding.  tau is read on the device (one float64): the caller forms
+ * mass * sum(mu) there and nothing synchronises with the host; tau > 0 and finite, masses >= 0 and finite are the
+ * caller's contract (a tau that is not positive crosses at position 0, a NaN is not reached; nothing is read or written
+ * out of bounds either way).  masses is indexed by the key's id: the original id with order, the tree row when order is
+ * NULL.  sample_order, order, the query form (k1 = R = 1) and the walk are those of flooder_knn_wide_f32; the cull bound
+ * is the crossing key while the list has one, else its L-th key (csrc/flood_knn_mass.hip has the exactness argument).
+ * No work queue, no atomics, every output word written once by plain stores.
+ * Arguments: the block of flooder_knn_wide_f32 (the form of flooder_knn_wide_profile_f32 and flooder_sweep_power_f32:
+ * an existing block plus what the entry adds - the header keeps its eleven blocks).  Its k is the CAPACITY, the list
+ * entries wanted, 1..FLOODER_KNN_WIDE_MAX, rounded up to C; its stat, order, sample_order, out_bits, out_ids and out_d2
+ * are as there, rows of out_ids / out_d2 having ld_out entries.  Then: masses ((n_pts,) float32 mu >= 0, indexed by id),
+ * target (DEVICE pointer to one float64, tau), ld_out (entries of a row of out_ids / out_d2, 1..C; not looked at when
+ * both are NULL), out_count ((N,) int32; may be NULL).
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a device pointer is read: a bad block
+ * size or abi; capacity (the block's k) outside 1..FLOODER_KNN_WIDE_MAX; dim outside 2..8; stat not 0 or 1; n_pts < 1; n_pts > 2^31 - 1;
+ * n_simplices * R >= 2^32 - 2; a cloud too large for the stack encoding; all four outputs NULL; out_ids without order;
+ * with out_ids or out_d2, ld_out outside 1..C; masses or target NULL.  Then n_simplices == 0 or R == 0: FLOODER_OK,
+ * nothing is touched.
+ */
+int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* masses, const double* target, int32_t ld_out,
+                         int32_t* out_count, void* stream);
+
+/*
  * ---- Weighted filtration: the power distance (csrc/flood_power.hip; flood_complex(point_weights=w)) ----------------
  * Every point x carries a weight w_x >= 0 and a sample p is measured by f(p)^2 = min_x ( |p - x|^2 + w_x^2 ).
  *
