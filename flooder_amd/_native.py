@@ -306,6 +306,15 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p]),
     "flooder_dtm_grad_points_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_int64, c_void_p, c_void_p]),
+    # ... and of the distance to a WEIGHTED measure (distance_to_weighted_measure(differentiable=True)) over the rows and
+    # counts of flooder_knn_mass_f32: sites are (n, dim + 1) rows (coordinates, then the mass), qrow the (Q, 4) crossing
+    # rows (coefficient in; rho, crossing id, dstar2 out); then the two transposes, into the sites and into the masses
+    "flooder_mass_grad_queries_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "flooder_mass_grad_points_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_void_p, c_void_p]),
+    "flooder_mass_grad_masses_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # The positional forms of the five entry points above: still exported by the library (same symbols as before round 6),

@@ -169,7 +169,11 @@ def build_parser() -> argparse.ArgumentParser:
                           "sqrt(min_x |p - x|^2 + w_x^2) (not together with --neighbors / --neighbor-mass; default: off)")
     wex.add_argument("--dtm-weights", metavar="MASS", type=float, default=None,
                      help="Weighted filtration with weights = distance_to_measure(points, mass=MASS): the DTM "
-                          "filtration (0 < MASS <= 1, at most 1024 neighbours; default: off)")
+                          "filtration (0 < MASS <= 1; at most 1024 neighbours unless --dtm-cell-size is given; "
+                          "default: off)")
+    g.add_argument("--dtm-cell-size", metavar="CELL", type=float, default=None,
+                   help="With --dtm-weights: the weights are distance_to_weighted_measure over the cloud's coreset on a "
+                        "grid of cubes of edge CELL (voxel_measure), for a mass of any number of points (default: off)")
     mex = g.add_mutually_exclusive_group(required=False)
     mex.add_argument("--points-per-edge", metavar="INT", type=int, default=None,
                      help="Points per edge for Flood PH (default: 30 if neither option given)")
@@ -284,6 +288,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parser.parse_args(argv)
     if args.neighbor_mass is not None and args.neighbors != 1:
         parser.error("--neighbor-mass cannot be combined with --neighbors: the mass fixes the number of neighbours")
+    if args.dtm_cell_size is not None and args.dtm_weights is None:
+        parser.error("--dtm-cell-size needs --dtm-weights MASS: it is the cell size of the coreset the weights are taken over")
     if args.verbose:
         print(vars(args))
     device = validate_device(args.device)
@@ -305,9 +311,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if args.point_weights is not None:
             point_weights = load_point_weights(Path(args.point_weights), n_pts).to(device, non_blocking=True)
         elif args.dtm_weights is not None:
-            from . import distance_to_measure
+            from . import distance_to_measure, distance_to_weighted_measure, voxel_measure
 
-            point_weights = distance_to_measure(cloud, mass=args.dtm_weights)
+            if args.dtm_cell_size is not None:
+                sites, site_masses = voxel_measure(cloud, args.dtm_cell_size)
+                point_weights = distance_to_weighted_measure(sites, site_masses, cloud, args.dtm_weights)
+                missed = int((~torch.isfinite(point_weights)).sum())
+                if missed:
+                    raise ValueError(f"--dtm-cell-size: {missed} of {n_pts} points were not reached - their nearest sites "
+                                     f"of the coreset do not hold the mass {args.dtm_weights!r}; coarsen the cell size or "
+                                     "lower the mass")
+            else:
+                point_weights = distance_to_measure(cloud, mass=args.dtm_weights)
         stree = flood_complex(cloud, args.num_landmarks, max_dimension=max_dim, points_per_edge=points_per_edge,
                               point_weights=point_weights,
                               batch_size=args.batch_size, fps_h=args.fps_height,

@@ -185,7 +185,8 @@ def power_filtration(points: torch.Tensor, landmarks, point_weights: torch.Tenso
 def dtm_filtration(points: torch.Tensor, landmarks, mass: Optional[float] = None, max_dimension: Optional[int] = None,
                    points_per_edge: int = 30, num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *,
                    neighbors: Optional[int] = None, neighbor_stat: str = "dtm", method: Optional[str] = None,
-                   index: Optional["core.PointIndex"] = None) -> FloodFiltration:
+                   index: Optional["core.PointIndex"] = None, cell_size: Optional[float] = None,
+                   max_neighbors: Optional[int] = None) -> FloodFiltration:
     """The DTM filtration by mass, differentiable end to end: ``power_filtration(points, landmarks, w, ...)`` with
     ``w = distance_to_measure(points, mass=mass, neighbors=neighbors, neighbor_stat=neighbor_stat, differentiable=True,
     index=index)`` at the cloud's own points - the literature's robust filtration (k = mass * N up to 1024 neighbours)
@@ -197,13 +198,40 @@ def dtm_filtration(points: torch.Tensor, landmarks, mass: Optional[float] = None
     when ``points`` requires it: one backward adds the three gradients of ``power_filtration`` into ``points`` (as
     witness points, as landmarks taken from the cloud, and through the weights, chained through the closed form of
     ``distance_to_measure``).  On ROCm tensors the ``PointIndex`` is built once (or recalled, or ``index``) and serves
-    both steps and the landmark selection; every sum has a fixed order: bit-identical run to run."""
-    from .neighbors import _check_points, _index_of, distance_to_measure
+    both steps and the landmark selection; every sum has a fixed order: bit-identical run to run.
 
-    if _check_points(points, "distance_to_measure") and index is None:
+    ``cell_size=c``: the weights over the cloud's CORESET, for a mass of more than 1024 points - ``w =
+    distance_to_weighted_measure(sites, mu, queries=points, mass=mass, neighbor_stat=neighbor_stat,
+    max_neighbors=max_neighbors, differentiable=True)`` with ``(sites, mu) = voxel_measure(points, c,
+    differentiable=True)``.  The sites get a ``PointIndex`` of their own; the cloud's index serves the landmark selection
+    and ``power_filtration`` as before.  A coreset is addressed by mass: ``neighbors`` together with ``cell_size`` is
+    refused, and so is ``max_neighbors`` (the list capacity of ``distance_to_weighted_measure``) without ``cell_size``.
+    ``power_filtration`` needs finite weights, so a point whose ``max_neighbors`` nearest sites do not hold the mass
+    raises a ``ValueError`` (the function synchronises with the host anyway, for the Delaunay step).  One backward then
+    adds into ``points.grad`` the witness and landmark gradients and the weight gradient, chained through the weighted
+    measure in both roles of the cloud: as its queries, and through the centroids of its cells."""
+    from .neighbors import (_check_points, _index_of, distance_to_measure, distance_to_weighted_measure,
+                            voxel_measure)
+
+    if cell_size is None and max_neighbors is not None:
+        raise ValueError("dtm_filtration: max_neighbors is the list capacity of the coreset's weighted measure and "
+                         "needs cell_size")
+    if cell_size is not None and neighbors is not None:
+        raise ValueError("dtm_filtration: a coreset is addressed by mass - pass mass, not neighbors, with cell_size")
+    on_gpu = _check_points(points, "distance_to_measure")
+    if cell_size is not None:
+        sites, mu = voxel_measure(points, cell_size, differentiable=True)
+        w = distance_to_weighted_measure(sites, mu, points, mass, neighbor_stat=neighbor_stat,
+                                         max_neighbors=max_neighbors, differentiable=True)
+        missed = int((~torch.isfinite(w.detach())).sum())
+        if missed:
+            raise ValueError(f"dtm_filtration: {missed} of {points.shape[0]} points were not reached - their nearest "
+                             f"sites of the coreset do not hold the mass {mass!r}; coarsen cell_size or lower mass")
+    if on_gpu and index is None:
         index = _index_of(points.detach(), None)
-    w = distance_to_measure(points, None, mass, neighbors=neighbors, neighbor_stat=neighbor_stat, differentiable=True,
-                            index=index)
+    if cell_size is None:
+        w = distance_to_measure(points, None, mass, neighbors=neighbors, neighbor_stat=neighbor_stat,
+                                differentiable=True, index=index)
     return power_filtration(points, landmarks, w, max_dimension, points_per_edge, num_rand, start_idx, method=method,
                             index=index)
 

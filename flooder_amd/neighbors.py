@@ -18,7 +18,9 @@ with its k best in LDS, values and neighbours; detached by default, with ``diffe
 
 ``distance_to_weighted_measure`` takes SITES WITH MASSES (the coreset of ``voxel_measure``) and a mass that may be far
 more than 1024 points: ``flooder_knn_mass_f32``, the wide kernel's walk up to the site at which the cumulative mass
-reaches the target.
+reaches the target; detached by default, with ``differentiable=True`` the closed form of the rule in the sites, their
+masses and the queries, its backward two kernels of ``csrc/flood_mass_grad.hip`` over the sweep's int32 rows and counts.
+``voxel_measure(differentiable=True)`` carries the gradient of the sites on to the cloud they are the centroids of.
 """
 
 from __future__ import annotations
@@ -353,6 +355,7 @@ def _check_point_masses(points: torch.Tensor, point_masses) -> None:
     if point_masses.device != points.device:
         raise ValueError(f"point_masses.device ({point_masses.device}) != points.device ({points.device})")
     if not points.is_cuda:   # (on ROCm tensors a check would synchronise with the host: the caller's contract)
+        point_masses = point_masses.detach()
         if not bool(torch.isfinite(point_masses).all()) or bool((point_masses < 0).any()):
             raise ValueError("point_masses must be finite and non-negative")
         if not float(point_masses.sum(dtype=torch.float64)) > 0.0:
@@ -371,7 +374,7 @@ def _mass_target(point_masses: torch.Tensor, mass: float) -> torch.Tensor:
 def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tensor, queries: Optional[torch.Tensor] = None,
                                  mass: Optional[float] = None, *, neighbor_stat: str = "dtm", squared: bool = False,
                                  max_neighbors: Optional[int] = None, return_neighbors: bool = False,
-                                 index: Optional[core.PointIndex] = None):
+                                 index: Optional[core.PointIndex] = None, differentiable: bool = False):
     """Per query the distance to the WEIGHTED measure sum_i mu_i delta_(x_i) (x_i = ``points[i]``, mu_i =
     ``point_masses[i]`` >= 0) at mass ``mass`` -> (Q,) tensor of ``points``' dtype on its device.
 
@@ -406,9 +409,29 @@ def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tenso
     integer masses (the coreset's counts) the crossing is exact.  CPU tensors (float32, float64; any dimension) query
     scipy's kd-tree at min(L, N) neighbours and evaluate the rule in float64.
 
-    Not differentiable: inputs that require grad are used detached.  Out of scope here: gradients, ``dtm_filtration`` /
-    ``dtm_profile`` and ``flood_complex(neighbor_mass=...)`` over a weighted cloud (pass the result as ``point_weights``
-    instead: ``flood_complex(points, L, point_weights=w)``), sharding, a float64 kernel.
+    By default inputs that require grad are used detached.  ``differentiable=True``: when ``points``, ``point_masses``
+    or ``queries`` requires grad (and grad mode is on) the value carries a ``grad_fn`` with the closed form of the rule.
+    Per reached query the listed sites y_(0) .. y_(j*) have the entry coefficients a_t = mu_(t) for t < j* and a_(j*) =
+    rho = tau - M_(j*-1) (they add up to tau).  ``"dtm"``, squared value F = sum_t a_t d_(t)^2 / tau: dF/dq = (2 / tau)
+    sum_t a_t (q - y_(t)), its negative goes entry by entry to the y_(t); dF/dmu_l = (d_(l)^2 - d_(j*)^2) / tau for a site
+    listed before the crossing, and every mass, listed or not, also gets ``mass`` * (d_(j*)^2 - F) / tau (tau depends on
+    every mass).  ``"kth"``, F = d_(j*)^2: dF/dq = 2 (q - y_(j*)), its negative to y_(j*) alone, nothing to the masses
+    (the radius is piecewise constant in them).  The un-squared value f has these times 1 / (2 f), 0 where f = 0.  A
+    query that is not reached (+inf) adds exactly nothing to any gradient, whatever its incoming gradient.  With
+    ``queries=None`` both roles of a site accumulate into ``points.grad``.  The rule is piecewise smooth: this is its
+    gradient wherever the crossing position does not move (almost everywhere); the gradient through the crossing
+    position itself is out of scope.  The values (and ``ids``, ``dist``, ``count`` of ``return_neighbors=True``, which
+    are detached) are bit for bit those of the call without grad; without an input that requires grad the keyword changes
+    nothing.  ROCm tensors keep the sweep's int32 rows and counts and run ``flooder_mass_grad_queries_f32``,
+    ``flooder_mass_grad_points_f32`` and ``flooder_mass_grad_masses_f32`` (csrc/flood_mass_grad.hip; ``"kth"``: ``flooder_dtm_grad_*_f32`` on the column of
+    crossing ids): no (Q, L, dim) tensor, no float atomics, groups of query rows within
+    ``core.DTM_GRAD_WORKSPACE_BYTES`` - the gradient is bit-identical run to run and does not depend on the groups; with
+    unit masses and ``mass=k / N`` it is that of ``distance_to_measure(neighbors=k, differentiable=True)`` bit for bit.
+    CPU tensors: the kd-tree's ids, the closed form in float64 torch and ``index_add_``.
+
+    Out of scope here: ``dtm_profile`` / ``power_profile`` and ``flood_complex(neighbor_mass=...)`` over a weighted cloud
+    (pass the result as ``point_weights`` instead: ``flood_complex(points, L, point_weights=w)``, or use
+    ``dtm_filtration(cell_size=...)``), sharding, a float64 kernel.
     """
     on_gpu = _check_points(points, "distance_to_weighted_measure")
     core._check_neighbor_stat(neighbor_stat)
@@ -417,7 +440,11 @@ def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tenso
         raise ValueError("distance_to_weighted_measure needs mass (a real number in (0, 1])")
     core.mass_neighbors(mass, 1)   # (the checks of a mass, in the family's wording)
     cap = _list_capacity(max_neighbors)
+    own = queries is None
     queries = _check_queries_and_index(points, queries, index, on_gpu)
+    with_grad = bool(differentiable) and torch.is_grad_enabled() and (
+        points.requires_grad or point_masses.requires_grad or queries.requires_grad)
+    grad_points, grad_masses, grad_queries = points, point_masses, queries
     points, point_masses, queries = points.detach(), point_masses.detach(), queries.detach()
     Q = queries.shape[0]
     if Q == 0:
@@ -429,17 +456,25 @@ def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tenso
     if on_gpu:
         lib, st = _native.load(), _native.current_stream_ptr(points.device)
         ids, d2, count, bits = _weighted_sweep_hip(points, point_masses, queries, tau, cap, neighbor_stat, index,
-                                                   return_neighbors)
+                                                   return_neighbors or with_grad, return_neighbors)
         value = _root_of_bits(lib, bits, squared, st)
+        if with_grad:   # (the sweep's int32 rows and counts as they are; the squared words tell reached from not)
+            value = _WeightedMeasure.apply(grad_points, grad_masses, None if own else grad_queries, value,
+                                           bits.view(torch.float32), ids, count, tau, float(mass), neighbor_stat,
+                                           bool(squared))
         if not return_neighbors:
             return value
         return value, ids.long(), _root_of_bits(lib, d2, squared, st), count.long()
     value, ids, dist, count = _weighted_measure_cpu(points, point_masses, queries, float(tau[0]), cap, neighbor_stat,
                                                     squared)
     value = torch.as_tensor(value).to(points.dtype)
+    ids, count = torch.as_tensor(ids), torch.as_tensor(count)
+    if with_grad:
+        value = _WeightedMeasure.apply(grad_points, grad_masses, None if own else grad_queries, value, None, ids, count,
+                                       tau, float(mass), neighbor_stat, bool(squared))
     if not return_neighbors:
         return value
-    return value, torch.as_tensor(ids), torch.as_tensor(dist).to(points.dtype), torch.as_tensor(count)
+    return value, ids, torch.as_tensor(dist).to(points.dtype), count
 
 
 def _weighted_measure_cpu(points, point_masses, queries, tau: float, cap: int, stat: str, squared: bool):
@@ -474,11 +509,13 @@ def _weighted_measure_cpu(points, point_masses, queries, tau: float, cap: int, s
 
 
 def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: int, stat: str,
-                        index: Optional[core.PointIndex], want_neighbors: bool):
+                        index: Optional[core.PointIndex], want_neighbors: bool, want_d2: Optional[bool] = None):
     """``_query_sweep_hip``'s wide form for ``flooder_knn_mass_f32``: the same ``PointIndex``, the queries sorted by curve
     key in groups (24 B of keys, orders and sort scratch, 8 B of value and count and, with ``want_neighbors``, 8 * cap
     bytes of rows per query, within ``core.SORTED_WORKSPACE_BYTES``), one launch per group -> (ids (Q, cap) int32 or
-    None, their d2 words (Q, cap) int32 or None, count (Q,) int32, the words of the squared statistic (Q,) int32)."""
+    None, their d2 words (Q, cap) int32 or None, count (Q,) int32, the words of the squared statistic (Q,) int32).
+    ``want_d2`` (None: as ``want_neighbors``) False: the ids without their d2 words - what a forward with grad keeps."""
+    want_d2 = want_neighbors if want_d2 is None else (want_neighbors and want_d2)
     lib = _native.load()
     dev = points.device
     torch.cuda.set_device(dev)
@@ -489,7 +526,7 @@ def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: i
     masses = point_masses.to(torch.float32).contiguous()
     one = torch.ones((1, 1), dtype=torch.float32, device=dev)
     ids = torch.empty((Q, cap), dtype=torch.int32, device=dev) if want_neighbors else None
-    d2 = torch.empty((Q, cap), dtype=torch.int32, device=dev) if want_neighbors else None
+    d2 = torch.empty((Q, cap), dtype=torch.int32, device=dev) if want_d2 else None
     count = torch.empty(Q, dtype=torch.int32, device=dev)
     bits = torch.empty(Q, dtype=torch.int32, device=dev)
     key_bits = int(lib.flooder_sample_key_bits(dim))
@@ -508,7 +545,7 @@ def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: i
     return ids, d2, count, bits
 
 
-def voxel_measure(points: torch.Tensor, cell_size: float):
+def voxel_measure(points: torch.Tensor, cell_size: float, differentiable: bool = False):
     """The coreset of a cloud on a grid of cubes of edge ``cell_size`` -> (``sites`` (M, d), ``masses`` (M,)), both of
     ``points``' dtype on its device: per occupied cell the centroid of its points and their number - the weighted
     measure ``distance_to_weighted_measure`` takes, within W_2 <= cell_size * sqrt(d) of the cloud's empirical measure.
@@ -519,7 +556,13 @@ def voxel_measure(points: torch.Tensor, cell_size: float):
     a centroid is within 2^-37 of a cell of the float64 mean - are summed as INTEGERS (a cumulative sum and differences
     at the cell boundaries: exact in any order), and the centroid is rounded once to ``points``' dtype.  Two runs, and
     a CPU and a ROCm run, agree (sites to the last bit of float64 before that rounding).  One host synchronisation (the
-    number M of occupied cells) is taken.  Not differentiable: ``points`` is used detached.  Up to 2^27 points.
+    number M of occupied cells) is taken.  Up to 2^27 points.
+
+    By default ``points`` is used detached.  ``differentiable=True``: when ``points`` requires grad (and grad mode is on)
+    ``sites`` carries a ``grad_fn``: a site is the mean of its cell's points, so ``points.grad[i] = sites.grad[cell(i)] /
+    count[cell(i)]`` - one ``index_select`` over the cell of every point, deterministic, no further synchronisation (the
+    assignment of points to cells is piecewise constant).  The masses never carry grad, and the bits of both outputs are
+    those of the plain call.
     """
     if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] == 0 or points.shape[1] == 0:
         got = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
@@ -546,7 +589,26 @@ def voxel_measure(points: torch.Tensor, cell_size: float):
     total = last - torch.cat([torch.zeros_like(last[:1]), last[:-1]])
     frac = total.to(torch.float64) / (counts.to(torch.float64).unsqueeze(1) * float(1 << 36))
     sites = lo + (cells.to(torch.float64) + frac) * cell_size
-    return sites.to(points.dtype).contiguous(), counts.to(points.dtype)
+    sites = sites.to(points.dtype).contiguous()
+    if differentiable and torch.is_grad_enabled() and points.requires_grad:
+        sites = _VoxelSites.apply(points, sites, inverse.reshape(-1), counts)
+    return sites, counts.to(points.dtype)
+
+
+class _VoxelSites(torch.autograd.Function):
+    """``voxel_measure(differentiable=True)``: the computed ``sites`` with the gradient of a mean per cell."""
+
+    @staticmethod
+    def forward(ctx, points, sites, inverse, counts):
+        ctx.save_for_backward(inverse, counts)
+        return sites.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_sites):
+        inverse, counts = ctx.saved_tensors
+        share = grad_sites / counts.to(grad_sites.dtype).unsqueeze(1)
+        return share.index_select(0, inverse), None, None, None
 
 
 def power_distance(points: torch.Tensor, point_weights: torch.Tensor, queries: Optional[torch.Tensor] = None, *,
@@ -899,6 +961,169 @@ def _dtm_backward_hip(points, qs, ids, first: int, m: int, coef, own: bool, need
         if own:
             grad_p += grad_q
     return grad_p, grad_q
+
+
+class _WeightedMeasure(torch.autograd.Function):
+    """``distance_to_weighted_measure(differentiable=True)``: the computed ``value`` with the closed-form backward over
+    the ``ids`` (Q, L) and ``count`` (Q,) the forward found (int32 on ROCm tensors, int64 padded with -1 on CPU tensors).
+    ``value_sq``: the squared statistic (ROCm tensors; None on CPU tensors, which evaluate it again in float64);
+    ``tau``: the (1,) float64 target on the device.  ``queries`` None: the sites themselves."""
+
+    @staticmethod
+    def forward(ctx, points, point_masses, queries, value, value_sq, ids, count, tau, mass, stat, squared):
+        own = queries is None
+        saved = [points, point_masses, points if own else queries, value, ids, count, tau]
+        if value_sq is not None:
+            saved.append(value_sq)
+        ctx.save_for_backward(*saved)
+        ctx.own, ctx.mass, ctx.stat, ctx.squared = own, mass, stat, squared
+        return value.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        points, masses, qs, value, ids, count, tau, *rest = ctx.saved_tensors
+        own = ctx.own
+        need_p, need_m = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_q = own or ctx.needs_input_grad[2]
+        backward = _mass_backward_hip if points.is_cuda else _mass_backward_cpu
+        grad_p, grad_m, grad_q = backward(points.detach(), masses.detach(), qs.detach(), value, rest[0] if rest else None,
+                                          ids, count, tau, ctx.mass, ctx.stat, ctx.squared, grad_out, own, need_p,
+                                          need_m, need_q)
+        return (grad_p, grad_m, (None if own or not ctx.needs_input_grad[2] else grad_q), None, None, None, None, None,
+                None, None, None)
+
+
+def _mass_backward_cpu(points, masses, qs, value, value_sq, ids, count, tau, mass: float, stat: str, squared: bool,
+                       grad_out, own: bool, need_p: bool, need_m: bool, need_q: bool):
+    """(grad_points, grad_masses, grad_queries; None where not needed) of the weighted measure on CPU tensors: the closed
+    form in float64 torch on the kd-tree's ids, ``index_add_`` (sequential on the host: deterministic), in groups of
+    query rows that keep the (rows, columns, dim) contributions of a group near 256 MB.  Rows that were not reached
+    (value +inf) are masked out with ``torch.where``: they add exact zeros."""
+    dt = points.dtype
+    Q, dim = qs.shape
+    n = points.shape[0]
+    reached = torch.isfinite(value)
+    g = torch.where(reached, grad_out.to(torch.float64), torch.zeros((), dtype=torch.float64))
+    t = float(tau[0])
+    x, q, mu = points.to(torch.float64), qs.to(torch.float64), masses.to(torch.float64)
+    cnt = torch.where(reached, count, torch.zeros_like(count))
+    width = max(1, int(cnt.max()))                     # (columns beyond the longest reached list hold nothing)
+    last = (cnt - 1).clamp(min=0)
+    if stat == "kth":                                  # y_(j*) alone: the form of distance_to_measure at m = 1
+        cross = ids.gather(1, last.unsqueeze(1)).clamp(min=0)
+        f = torch.where(reached, value.to(torch.float64), torch.ones((), dtype=torch.float64))
+        coef = g * 2.0 if squared else torch.where(f > 0, g / torch.where(f > 0, f, torch.ones_like(f)), torch.zeros_like(f))
+        grad_p, grad_q = _dtm_backward_cpu(x, q, cross, 0, 1, coef, own, need_p, need_q)
+        return (None if grad_p is None else grad_p.to(dt), torch.zeros_like(masses) if need_m else None,
+                None if grad_q is None else grad_q.to(dt))
+    grad_q = torch.zeros((Q, dim), dtype=torch.float64) if need_q else None
+    grad_p = torch.zeros((n, dim), dtype=torch.float64) if need_p else None
+    grad_m = torch.zeros(n, dtype=torch.float64) if need_m else None
+    dense = torch.zeros((), dtype=torch.float64)
+    cols = torch.arange(width).unsqueeze(0)
+    per_group = max(1, (256 << 20) // (width * dim * 8))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        nb = ids[a:b, :width].clamp(min=0)
+        before = cols < last[a:b].unsqueeze(1)                         # listed before the crossing
+        at = (cols == last[a:b].unsqueeze(1)) & reached[a:b].unsqueeze(1)
+        before = before & reached[a:b].unsqueeze(1)
+        m_nb = torch.where(before, mu[nb], torch.zeros((), dtype=torch.float64))
+        rho = t - m_nb.sum(dim=1)
+        coeffs = m_nb + torch.where(at, rho.unsqueeze(1), torch.zeros((), dtype=torch.float64))      # a_t, 0 elsewhere
+        diff = q[a:b].unsqueeze(1) - x[nb]                             # (rows, width, dim)
+        d2 = diff.square().sum(dim=2)
+        F = (coeffs * d2).sum(dim=1) / t
+        if squared:
+            c = g[a:b] * (2.0 / t)
+        else:
+            f = torch.sqrt(F)
+            c = torch.where(f > 0, g[a:b] / (torch.where(f > 0, f, torch.ones_like(f)) * t), torch.zeros_like(f))
+        contrib = (c.unsqueeze(1) * coeffs).unsqueeze(2) * diff
+        if need_q:
+            grad_q[a:b] = contrib.sum(dim=1)
+        if need_p:
+            grad_p.index_add_(0, nb.reshape(-1), -contrib.reshape(-1, dim))
+        if need_m:
+            h = 0.5 * c
+            dstar2 = d2.gather(1, last[a:b].unsqueeze(1))
+            listed = torch.where(before, h.unsqueeze(1) * (d2 - dstar2), torch.zeros((), dtype=torch.float64))
+            grad_m.index_add_(0, nb.reshape(-1), listed.reshape(-1))
+            dense = dense + (h * (dstar2.squeeze(1) - F)).sum()
+    if need_p and own:
+        grad_p += grad_q
+    if need_m:
+        grad_m += mass * dense
+    return (None if grad_p is None else grad_p.to(dt), None if grad_m is None else grad_m.to(dt),
+            None if grad_q is None else grad_q.to(dt))
+
+
+def _mass_backward_hip(points, masses, qs, value, value_sq, ids, count, tau, mass: float, stat: str, squared: bool,
+                       grad_out, own: bool, need_p: bool, need_m: bool, need_q: bool):
+    """The same on ROCm float32 tensors.  ``"dtm"``: ``flooder_mass_grad_queries_f32`` over all queries (the query
+    gradient and the crossing row - rho, the crossing id, dstar2 - of every query), then per group of ascending query rows
+    the (target, query row) pairs of the PADDED rows as packed int64 keys - rows that were not reached masked to -1, and
+    every negative key sorts in front of ``searchsorted``'s first bound and drops out -, sorted, the segment of every site
+    by a binary search, and ``flooder_mass_grad_points_f32`` and (for the masses) ``flooder_mass_grad_masses_f32``, which
+    continue the sequential sums per word from group to group: the gradient does not depend on ``core.DTM_GRAD_WORKSPACE_BYTES``.  The term every mass gets (tau depends on each) is one float64
+    ``torch.sum``.  ``"kth"``: ``_dtm_backward_hip`` on the (Q, 1) column of crossing ids.  tau stays on the device;
+    nothing here synchronises with the host."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    pts, q = points.contiguous(), qs.contiguous()
+    (Q, dim), n, L = q.shape, pts.shape[0], ids.shape[1]
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    reached = torch.isfinite(value_sq)
+    g = torch.where(reached, grad_out.to(torch.float32), zero)
+    cnt = torch.where(reached, count, torch.zeros_like(count)).contiguous()
+    if stat == "kth":
+        cross = torch.where(reached, ids.gather(1, (cnt.long() - 1).clamp(min=0).unsqueeze(1)).squeeze(1),
+                            torch.full_like(cnt, -1)).reshape(Q, 1).contiguous()
+        coef = g * 2.0 if squared else torch.where(reached & (value > 0), g / value, zero)
+        grad_p, grad_q = _dtm_backward_hip(pts, q, cross, 0, 1, coef, own, need_p, need_q)
+        return grad_p, (torch.zeros_like(masses) if need_m else None), grad_q
+    tau32 = tau.to(torch.float32)
+    # coefficient of a_t (q - y_(t)): with unit masses (tau = k) the words of _DistanceToMeasure
+    if squared:
+        coef = g * (2.0 / tau32)
+    else:
+        coef = torch.where(reached & (value > 0), g / (value * tau32), zero)
+    # the two layouts of csrc/flood_mass_grad.hip: a site's row is its coordinates, then its mass; a query's crossing row
+    # is its coefficient, then what the first kernel writes - rho, the crossing id and dstar2
+    sites = torch.cat([pts, masses.to(torch.float32).unsqueeze(1)], dim=1).contiguous()
+    qrow = torch.empty((Q, 4), dtype=torch.float32, device=dev)
+    qrow[:, 0] = coef
+    grad_q = torch.empty((Q, dim), dtype=torch.float32, device=dev)
+    _native.check(lib.flooder_mass_grad_queries_f32(_native.ptr(sites), n, _native.ptr(q), Q, dim, _native.ptr(ids), L,
+                                                    _native.ptr(cnt), _native.ptr(tau), _native.ptr(qrow),
+                                                    _native.ptr(grad_q), st), "flooder_mass_grad_queries_f32")
+    grad_p = grad_m = None
+    if need_p or need_m:
+        grad_p = torch.zeros((n, dim), dtype=torch.float32, device=dev) if need_p else None
+        grad_m = torch.zeros(n, dtype=torch.float32, device=dev) if need_m else None
+        bounds = torch.arange(n + 1, dtype=torch.int64, device=dev) << 32
+        per_group = max(1, min(Q, int(core.DTM_GRAD_WORKSPACE_BYTES) // (64 * L), ((1 << 31) - 1) // L))
+        for a in range(0, Q, per_group):
+            b = min(Q, a + per_group)
+            rows = torch.arange(b - a, dtype=torch.int64, device=dev).unsqueeze(1)
+            targets = torch.where(reached[a:b].unsqueeze(1), ids[a:b], torch.full_like(ids[a:b], -1)).to(torch.int64)
+            keys = torch.sort(((targets << 32) | rows).reshape(-1)).values
+            seg_ptr = torch.searchsorted(keys, bounds)
+            for out, name in ((grad_p, "flooder_mass_grad_points_f32"), (grad_m, "flooder_mass_grad_masses_f32")):
+                if out is not None:
+                    _native.check(getattr(lib, name)(_native.ptr(sites), n, _native.ptr(q[a:b]), b - a, dim,
+                                                     _native.ptr(qrow[a:b]), _native.ptr(keys), _native.ptr(seg_ptr),
+                                                     None, n, _native.ptr(out), st), name)
+        if need_p and own:
+            grad_p += grad_q
+        if need_m:      # what every mass gets because tau depends on it: mass * sum_q h_q (dstar2_q - F_q)
+            spread = torch.where(reached, (0.5 * coef).double() * (qrow[:, 3].double() - value_sq.double()),
+                                 torch.zeros((), dtype=torch.float64, device=dev))
+            grad_m += (spread.sum() * mass).to(torch.float32)
+    return grad_p, grad_m, (grad_q if need_q else None)
 
 
 class _PowerDistance(torch.autograd.Function):

@@ -1299,6 +1299,64 @@ int flooder_dtm_grad_points_f32(const float* points, int64_t n_points, const flo
                                 const float* coef, const int64_t* entries, const int64_t* seg_ptr,
                                 const int32_t* seg_target, int64_t n_seg, float* out_p, void* stream);
 
+/*
+ * ---- Backward of the distance to a weighted measure (csrc/flood_mass_grad.hip;
+ *      distance_to_weighted_measure(differentiable=True), stat "dtm") -------------------------------------------------
+ * Per reached query q flooder_knn_mass_f32 lists the sites y_(t), t = 0 .. j*, j* = count[q] - 1 the crossing position.
+ * With tau = *tau, M the cumulative mass of the positions before j* and rho = tau - M, the squared value is
+ * F = sum_t a_t |q - y_(t)|^2 / tau with a_t = the mass of y_(t) for t < j* and a_(j*) = rho.  c_q is the coefficient the
+ * caller forms (grad_out / (f tau), 0 where f = 0; grad_out * 2 / tau for the squared value) and h_q = c_q / 2.  No
+ * tree, no contribution is ever stored, no atomics, plain loads and stores, every output word written once per launch.
+ * ("kth" needs none of these entries: it is flooder_dtm_grad_*_f32 on the column of crossing ids with m = 1.)
+ * Two layouts keep every entry at a dozen arguments and every per-entry read of the transposes at one 16-byte load:
+ *   sites  (n_sites, dim + 1) float32, contiguous, input order: the row of a site is its dim coordinates, then its mass;
+ *   qrow   (n_queries, 4) 32-bit words, 16-byte aligned, the crossing row of a query: [0] c_q (float32, the caller's),
+ *          [1] rho (float32), [2] the crossing id (int32; -1 without a list), [3] dstar2 = d2(q, y_(j*)) (float32);
+ *          flooder_mass_grad_queries_f32 reads word 0 and writes words 1 to 3, the transposes read all four.
+ * d2(q, y) is everywhere t_0 * t_0 + t_1 * t_1 + ..., t_a = q[a] - y[a], every product and every sum rounded to float32,
+ * left to right (no fused step).  queries (n_queries, dim) are the caller's contiguous float32 rows.
+ *
+ * flooder_mass_grad_queries_f32: one wave per query.  kk = min(count[q], ld_ids).  kk <= 0: out_q[q, :] = +0,
+ * rho = 0, crossing id = -1, dstar2 = 0.  Else lane l adds (double)mass of the positions l, l + 64, ... < kk - 1 to a
+ * partial sum that starts as +0, left to right; the 64 sums are added in the butterfly of flooder_dtm_grad_queries_f32
+ * (a_l = a_l + a_(l ^ s), s = 32, 16, 8, 4, 2, 1) to M; rho = (float)(tau - M), the subtraction in double; the crossing
+ * id is ids[q, kk - 1] and dstar2 the d2 of q to that site (0 if the id is no site).  Then lane l takes
+ * acc = fmaf(a_t, queries[q, c] - y_(t)[c], acc) over its positions l, l + 64, ... < kk from +0, the sums are added in
+ * the same butterfly and out_q[q, c] = c_q * sum; a c_q that is 0 gives +0 words (nothing is gathered; words 1 to 3 are
+ * written all the same).  An id outside 0 .. n_sites - 1 is not read and adds neither mass nor difference.  With masses
+ * all 1.0f and tau = kk the words of out_q are those of flooder_dtm_grad_queries_f32 at m = kk.
+ * rho is exact, and the rho of flooder_knn_mass_f32 bit for bit, whenever every partial sum of the masses is an exact
+ * float64 number - integer masses with a total below 2^53 (a coreset's counts).  Otherwise M is another fixed order of
+ * the same non-negative float64 terms as the forward's prefix sum: the two differ by at most kk * 2^-52 * M, rho by
+ * that plus its own rounding of 2^-24 relative; the same word run to run.
+ *
+ * flooder_mass_grad_points_f32 and flooder_mass_grad_masses_f32: the transposes.  entries, seg_ptr, seg_target and
+ * n_seg are those of flooder_dtm_grad_points_f32 (the LOW 32 bits of an entry are the query row; segment g belongs to
+ * the site j = seg_target[g], j = g when seg_target is NULL; inside a segment the entries ascend by query row).
+ *   points  thread (g, c) starts from the word in out_p[j, c] ((n_sites, dim) rows) and takes its entries front to back:
+ *           a = rho_q when q's crossing id is j, else the mass of j; e = c_q * a, ONE float32 product;
+ *           acc = fmaf(-e, queries[q, c] - y_j[c], acc); then out_p[j, c] = acc.
+ *   masses  thread (g) starts from out_m[j] ((n_sites,)) and takes the entries whose crossing id is NOT j front to back:
+ *           acc = fmaf(0.5f * c_q, d2(q, y_j) - dstar2_q, acc); then out_m[j] = acc.
+ * Launches over consecutive groups of ascending query rows (queries, qrow and the entries' rows relative to the group's
+ * first row) continue one sequential sum per word: the result does not depend on the groups, bit for bit.  Words without
+ * a non-empty segment are left as they are; a target outside 0 .. n_sites - 1 or a query row >= n_queries is not read
+ * and adds nothing.  With masses all 1.0f and rho 1.0f the words of out_p are those of flooder_dtm_grad_points_f32.
+ *
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a pointer is read: dim outside 2..8;
+ * ld_ids outside 1..FLOODER_KNN_WIDE_MAX (grad_queries); a negative count; a NULL pointer (seg_target may be).  Then
+ * n_queries == 0 or n_seg == 0: FLOODER_OK, nothing is touched.
+ */
+int flooder_mass_grad_queries_f32(const float* sites, int64_t n_sites, const float* queries, int64_t n_queries, int dim,
+                                  const int32_t* ids, int64_t ld_ids, const int32_t* count, const double* tau,
+                                  void* qrow, float* out_q, void* stream);
+int flooder_mass_grad_points_f32(const float* sites, int64_t n_sites, const float* queries, int64_t n_queries, int dim,
+                                 const void* qrow, const int64_t* entries, const int64_t* seg_ptr,
+                                 const int32_t* seg_target, int64_t n_seg, float* out_p, void* stream);
+int flooder_mass_grad_masses_f32(const float* sites, int64_t n_sites, const float* queries, int64_t n_queries, int dim,
+                                 const void* qrow, const int64_t* entries, const int64_t* seg_ptr,
+                                 const int32_t* seg_target, int64_t n_seg, float* out_m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
