@@ -180,7 +180,7 @@ def fps_indices(points: torch.Tensor, n_lms: int, start_idx: int = 0, method: Op
         if method == "bucket" and (FPS_BATCHED or dim > 3) and n > int(lib.flooder_fps_batched_max_points()):
             method = "bucket" if dim <= 3 else "brute"     # (one landmark per launch / brute force beyond 16 M points)
             if dim <= 3:
-                return _fps_bucket_one_per_launch(lib, pts, n, dim, n_lms, start_idx, index, out_idx, points)
+                return _fps_bucket_one_per_launch(lib, pts, n, dim, n_lms, start_idx, index, out_idx, points, _used_index)
         if method == "bucket" and (FPS_BATCHED or dim > 3):
             global LAST_FPS_LAUNCHES
             if index is None:
@@ -726,7 +726,8 @@ class PointIndex:
                           "flooder_index_rows_f32")
 
 
-def index_from_host(points_cpu: torch.Tensor, device, chunk_rows: int = 1 << 21):
+def index_from_host(points_cpu: torch.Tensor, device, chunk_rows: int = 1 << 21, *,
+                    copy_stream: Optional["torch.cuda.Stream"] = None):
     """``PointIndex`` of a cloud that lives in HOST memory, streamed to the GPU in chunks (BASELINE.json configs[4]:
     "chunked point streaming from host pinned memory"; the reference bounds its device working set with
     ``batch_size`` slabs instead, ``core.py:193-217``).  The cloud is copied chunk by chunk from pinned memory on a
@@ -734,7 +735,9 @@ def index_from_host(points_cpu: torch.Tensor, device, chunk_rows: int = 1 << 21)
     the chunks already landed runs on the compute stream; the curve codes need the box of the WHOLE cloud, so the
     sort starts when the last chunk is in.  Returns ``(index, points_dev)``: pass both on -
     ``flood_complex(points_dev, landmarks, index=index)``.  ``h2d_ms_of(index)`` = time from the first copy to
-    the box being known (events on the compute stream)."""
+    the box being known (events on the compute stream).  The compute stream is the CURRENT stream of ``device``;
+    ``copy_stream`` (keyword-only): the stream the chunks are copied on - a prefetch stream of the caller's - instead of
+    one from PyTorch's pool."""
     lib = _native.load()
     dev = torch.device(device)
     src = points_cpu.detach().to(torch.float32).contiguous()
@@ -747,7 +750,11 @@ def index_from_host(points_cpu: torch.Tensor, device, chunk_rows: int = 1 << 21)
         raise RuntimeError("flooder_amd: index_from_host needs 1 <= dim <= 8 and at least one point")
     with torch.cuda.device(dev):
         main = torch.cuda.current_stream(dev)
-        copy = torch.cuda.Stream(dev)
+        if copy_stream is not None and not isinstance(copy_stream, torch.cuda.Stream):
+            raise TypeError(f"index_from_host: copy_stream must be a torch.cuda.Stream, got {type(copy_stream).__name__}")
+        if copy_stream is not None and copy_stream.device.index != torch.cuda.current_device():
+            raise ValueError(f"index_from_host: copy_stream is a stream of {copy_stream.device}, the cloud goes to {dev}")
+        copy = copy_stream if copy_stream is not None else torch.cuda.Stream(dev)
         raw = torch.empty((n, dim), dtype=torch.float32, device=dev)
         n_chunks = (n + chunk_rows - 1) // chunk_rows
         blocks = 64

@@ -279,6 +279,21 @@ def test_sorted_sample_sweep_random_dimensions(dev, monkeypatch):
         assert_tree_matches_kdtree(a, P, L, ppe, 2, f"sorted sweep dim {dim}")
 
 
+def test_index_from_host_on_a_copy_stream_of_the_callers(dev):
+    """``copy_stream=``: the chunks travel on the caller's stream (also when that is the compute stream itself) and the
+    index is the one of the default - a stream of PyTorch's pool -, bit for bit; what is no stream is refused."""
+    P = torch.randn(50_000, 3, generator=torch.Generator().manual_seed(12))
+    want, raw_w = core.index_from_host(P, dev, chunk_rows=20_000)
+    for stream in (torch.cuda.Stream(), torch.cuda.current_stream(dev)):
+        got, raw = core.index_from_host(P, dev, chunk_rows=20_000, copy_stream=stream)
+        torch.cuda.synchronize()
+        assert torch.equal(raw, raw_w) and torch.equal(got.pts, want.pts) and torch.equal(got.order32, want.order32)
+        assert torch.equal(got.nodes, want.nodes) and torch.equal(got.box[:3], want.box[:3])
+        assert core.h2d_ms_of(got) > 0.0
+    with pytest.raises(TypeError, match="copy_stream must be a torch.cuda.Stream"):
+        core.index_from_host(P, dev, copy_stream=0)
+
+
 def test_index_from_host_streams_the_cloud_and_index_kwarg_reuses_it(dev):
     """BASELINE cfg 5's "chunked point streaming from host pinned memory" (``core.index_from_host``): the index built
     from chunked pinned-memory copies equals the index of the resident cloud bit for bit, and
