@@ -161,26 +161,41 @@ extern "C" int64_t flooder_cell_faces(const int32_t* cells, int64_t n_cells, int
     distinct.store(0);
     std::atomic<int> full{0};
     const int64_t limit = (int64_t)(cap / 2);
+    // Every loop here ends.  A thread adds its new keys to `distinct` every `grain` of them (one cell alone can hold
+    // more faces than the first table has slots, and a range of at most 256 cells, or any range on one thread, is a
+    // single chunk), raises `full` once the table is past half and leaves; the others leave at their next `grain`
+    // new keys or their next cell.  grain = max(64, cap / 1024), a power of two: few enough additions to the shared
+    // count, and what 128 threads still insert after the limit fits the free half of a large table.  A probe that
+    // has walked all `cap` slots without finding its key or a free slot has met a (small) table that the other
+    // threads' last keys filled: it raises `full` and leaves too.
+    const int64_t grain = std::max<int64_t>(64, (int64_t)(cap >> 10));
     pool.parallel_for(n_cells, 256, [&](int64_t a, int64_t b, int) {
       int64_t mine = 0;
-      for (int64_t c = a; c < b && !full.load(std::memory_order_relaxed); ++c) {
+      bool leave = false;
+      for (int64_t c = a; c < b && !leave && !full.load(std::memory_order_relaxed); ++c) {
         const int32_t* v = cells + c * width;
-        for (int64_t f = 0; f < ncb; ++f) {
+        for (int64_t f = 0; f < ncb && !leave; ++f) {
           uint64_t key = 0;
           for (int i = 0; i < k; ++i) key = key * base + (uint64_t)(uint32_t)v[cb[(size_t)f][(size_t)i]];
           size_t slot = (size_t)mix64(key) & (cap - 1);
-          for (;;) {
+          for (size_t left = cap;; slot = (slot + 1) & (cap - 1)) {
             uint64_t cur = tab[slot].load(std::memory_order_relaxed);
             if (cur == key + 1) break;
             if (cur == 0) {
-              if (tab[slot].compare_exchange_strong(cur, key + 1, std::memory_order_relaxed)) { ++mine; break; }
+              if (tab[slot].compare_exchange_strong(cur, key + 1, std::memory_order_relaxed)) {
+                if ((++mine & (grain - 1)) == 0 && distinct.fetch_add(grain, std::memory_order_relaxed) + grain > limit)
+                  leave = true;
+                break;
+              }
               if (cur == key + 1) break;
             }
-            slot = (slot + 1) & (cap - 1);
+            if (--left == 0) { leave = true; break; }
           }
         }
       }
-      if (distinct.fetch_add(mine, std::memory_order_relaxed) + mine > limit) full.store(1);
+      const int64_t rest = mine & (grain - 1);
+      if (distinct.fetch_add(rest, std::memory_order_relaxed) + rest > limit || leave)
+        full.store(1, std::memory_order_relaxed);
     });
     if (!full.load()) break;
     cap <<= 1;

@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -17,6 +18,8 @@
 namespace {
 
 // All threads run the same function; the work inside is handed out through atomic counters.
+// An exception thrown by the function on any thread is kept (the first one), every thread still finishes the region,
+// and run() rethrows it on the calling thread once all of them have left: the function refers to the caller's stack.
 struct Pool {
   int nt = 1;
   std::vector<std::thread> th;
@@ -27,10 +30,18 @@ struct Pool {
   alignas(128) std::atomic<int> pending{0};
   alignas(128) std::atomic<int> sleepers{0};
   bool stop = false;
+  std::exception_ptr err;                       // first exception of the current region (guarded by m)
   explicit Pool(int n) : nt(n < 1 ? 1 : n) {
-    for (int t = 1; t < nt; ++t) th.emplace_back([this, t] { loop(t); });
+    try {
+      th.reserve((size_t)(nt - 1));
+      for (int t = 1; t < nt; ++t) th.emplace_back([this, t] { loop(t); });
+    } catch (...) {                             // (no more threads to be had: the ones that started are joinable)
+      shutdown();
+      throw;
+    }
   }
-  ~Pool() {
+  ~Pool() { shutdown(); }
+  void shutdown() {
     {
       std::lock_guard<std::mutex> l(m);
       stop = true;
@@ -38,6 +49,11 @@ struct Pool {
     }
     cv.notify_all();
     for (auto& t : th) t.join();
+    th.clear();
+  }
+  void keep_exception() noexcept {
+    std::lock_guard<std::mutex> l(m);
+    if (!err) err = std::current_exception();
   }
   // The regions of one call follow each other within microseconds (level after level): a thread that finds no work
   // spins on the generation counter for about 100 us before it goes to sleep on the condition variable - waking a
@@ -58,7 +74,11 @@ struct Pool {
       }
       seen = gen.load(std::memory_order_acquire);
       if (stop) return;
-      (*job)(tid);
+      try {
+        (*job)(tid);
+      } catch (...) {
+        keep_exception();
+      }
       if (pending.fetch_sub(1, std::memory_order_acq_rel) == 1) {
         std::lock_guard<std::mutex> l(m);
         cv_done.notify_one();
@@ -74,7 +94,11 @@ struct Pool {
       gen.fetch_add(1, std::memory_order_release);
     }
     if (sleepers.load(std::memory_order_relaxed) > 0) cv.notify_all();
-    f(0);
+    try {
+      f(0);
+    } catch (...) {
+      keep_exception();
+    }
     int spins = 0;
     while (pending.load(std::memory_order_acquire) != 0) {
       if (++spins < 20000) {
@@ -84,6 +108,12 @@ struct Pool {
       std::unique_lock<std::mutex> l(m);
       cv_done.wait(l, [&] { return pending.load(std::memory_order_acquire) == 0; });
     }
+    std::exception_ptr e;
+    {
+      std::lock_guard<std::mutex> l(m);
+      e.swap(err);
+    }
+    if (e) std::rethrow_exception(e);
   }
   // f(i0, i1, tid) over [0, n) in chunks; small ranges run on the calling thread
   template <class F>

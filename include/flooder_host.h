@@ -70,6 +70,9 @@ int flooder_delaunay_nd_isa(int isa);
  *   ascending ids per row, rows in lexicographic order - release with flooder_host_free.
  *   returns the number of distinct faces, or a code below -(1 << 40): bad arguments, or n_points^k >= 2^126 (the packed
  *   keys fit neither 64 nor 128 bits: the caller enumerates with numpy then).
+ *   Returns for every input it accepts at any n_threads (1 included; <= 0: the CPUs of the process, at most 128), with
+ *   the same table: the set of keys it collects in is rebuilt larger whenever a thread finds it more than half taken
+ *   or walks all of its slots in one probe.  Out of memory on any thread comes back as the bad-arguments code.
  */
 int64_t flooder_cell_faces(const int32_t* cells, int64_t n_cells, int width, int k, int64_t n_points, int n_threads,
                            int32_t** out_rows);
