@@ -61,8 +61,9 @@ inline dim3 stack_walk_grid(int64_t n) {   // a wave per query, grid-stride abov
 // arithmetic written out under a comment that names the helper.  Not shared at all, and to be kept in step by hand: the
 // sample as an fmaf chain over the vertices (grep "__builtin_fmaf(w"), the 16-row leaf loop (flood_bvh.hip,
 // flood_finish.hip, flood_sorted.hip, flood_cell.hip), the frontier walk of the six sweeps (sweep_knn_ids_kernel's is a
-// copy of sweep_knn_kernel's with strict culls) and the stack walk of the two witness kernels and of knn_wide_kernel:
-// three copies on the device; the wide entry's HOST side is the family's (above; knn_check_ranges).  For the two sweep_knn
+// copy of sweep_knn_kernel's with strict culls) and the stack walk of the two witness kernels, witness_power_kernel,
+// knn_wide_kernel and knn_mass_kernel: five copies on the device (the last two share their list helpers and ladder,
+// flood_knn_list.hpp); the wide entry's HOST side is the family's (above; knn_check_ranges).  For the two sweep_knn
 // kernels one shared body under an IDS template flag was tried at compile level, in two wordings: it moved the
 // registers of nearly every instantiation of flood_knn.hip, those of the untouched value path included.  No such build
 // has been timed, so the copy stands (the note above sweep_knn_ids_kernel has the figures).  The double sweep of

@@ -7,9 +7,9 @@
 // j* the first position with M_j* >= tau: the CROSSING.  The kernel returns the keys 0 .. j*, their number and the
 // statistic of include/flooder_hip.h.  With unit masses and tau = k it is flooder_knn_wide_f32 at k, word for word.
 //
-// Walk: knn_wide_kernel's (flood_knn_wide.hip, which this file does not touch: lds_handoff, keys_below, merge_buffer
-// and the walk are COPIES, kept in step by hand - a shared header would have had to be included there).  A wave keeps
-// the ascending key list in LDS, the same stack walk, four leaves at a time, the same insertion buffer.  What differs:
+// Walk: knn_wide_kernel's (flood_knn_wide.hip; lds_handoff, keys_below, merge_buffer and the capacity ladder are
+// flood_knn_list.hpp's, shared with it; the walk itself is a COPY, kept in step by hand - that header says why).  A wave
+// keeps the ascending key list in LDS, the same stack walk, four leaves at a time, the same insertion buffer.  What differs:
 //   - the list has L = min(C, n_pts) places: a cloud smaller than the capacity is legal;
 //   - after every merge the wave computes the cumulative masses of the list in float64 (a wave scan per row of 64
 //     positions, carried row to row; masses[id] is GATHERED from global memory, an empty slot has mass 0) and looks for
@@ -46,89 +46,14 @@
 // No atomics, nothing in inline assembly; every output word is written once by plain vector stores.
 
 #include "../../include/flooder_hip.h"
-#include "flood_common.hpp"
-#include "flood_bvh.hpp"
+#include "flood_knn_list.hpp"
 
 using namespace flooder;
 
 namespace {
 
-constexpr int BUF = 128;                 // keys of a wave's insertion buffer (two per lane in a merge)
-constexpr unsigned long long NOKEY = ~0ull;
 constexpr uint32_t INF_WORD = 0x7f800000u;
-typedef unsigned long long wkey_t;
 
-// ---- copies of flood_knn_wide.hip (see the header of this file)
-__device__ __forceinline__ void lds_handoff() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// number of keys of the ascending a[0..n) that are below x
-__device__ __forceinline__ int keys_below(const wkey_t* a, int n, wkey_t x) {
-  int lo = 0;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[lo + half] < x) {
-      lo += half + 1;
-      n -= half + 1;
-    } else {
-      n = half;
-    }
-  }
-  return lo;
-}
-
-// The m <= BUF keys of buf (any order, distinct, none of them in the list) into the ascending list of k keys; what
-// ends up at a place >= k falls off.  Leaves buf free and the list visible to every lane.
-template <int SLOTS>
-__device__ __forceinline__ void merge_buffer(wkey_t* list, wkey_t* buf, int k, int m, int lane) {
-  lds_handoff();   // (the buffer's keys are in)
-  wkey_t b[2];
-  int rank[2], place[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    b[u] = lane + 64 * u < m ? buf[lane + 64 * u] : NOKEY;
-    rank[u] = 0;
-  }
-  for (int j = 0; j < m; ++j) {
-    const wkey_t x = buf[j];   // (one address: broadcast)
-    rank[0] += x < b[0] ? 1 : 0;
-    rank[1] += x < b[1] ? 1 : 0;
-  }
-  lds_handoff();   // (every lane has read the buffer before it is rewritten in order)
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (lane + 64 * u < m) {
-      buf[rank[u]] = b[u];
-      place[u] = rank[u] + keys_below(list, k, b[u]);
-    }
-  lds_handoff();   // (the sorted buffer is in)
-  wkey_t l[SLOTS];
-  int to[SLOTS];
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int i = lane + 64 * s;
-    to[s] = i;
-    if (i < k) {
-      l[s] = list[i];
-      to[s] = i + keys_below(buf, m, l[s]);
-    }
-  }
-  lds_handoff();   // (every lane has read the old list and the buffer)
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int i = lane + 64 * s;
-    if (i < k && to[s] != i && to[s] < k) list[to[s]] = l[s];
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (lane + 64 * u < m && place[u] < k) list[place[u]] = b[u];
-  lds_handoff();   // (the merged list is in)
-}
-
-// ---- what this file adds
 // The crossing of the ascending list[0..len): the first position j with M_j >= tau, or -1 (wave-uniform).  M_j is the
 // float64 sum of masses[id] over the positions 0 .. j, an empty slot counting 0: an inclusive scan over the 64 lanes of
 // a row (position i in lane i % 64), plus the carry of the rows before it.  m_prev: M_(j-1), 0 for j = 0 (it is below
@@ -387,12 +312,7 @@ struct KnnMassOp {
     if constexpr (DIM < 2) {
       return fail(FLOODER_E_ARG, "flooder_knn_mass_f32: dim must be in 2..8");
     } else {
-      // the list capacity that holds k keys: 64, 128, 256, 512 or 1024
-      if (a.k <= 64) launch<1>(a, m, lv, n_cells, st);
-      else if (a.k <= 128) launch<2>(a, m, lv, n_cells, st);
-      else if (a.k <= 256) launch<4>(a, m, lv, n_cells, st);
-      else if (a.k <= 512) launch<8>(a, m, lv, n_cells, st);
-      else launch<16>(a, m, lv, n_cells, st);
+      with_list_slots(a.k, [&](auto slots) { launch<decltype(slots)::value>(a, m, lv, n_cells, st); });
       return check_launch("knn_mass");
     }
   }
@@ -418,7 +338,7 @@ extern "C" int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* ma
   if (!a.out_bits && !out_count && !a.out_ids && !a.out_d2)
     return failf(FLOODER_E_ARG, "%s: no output (out_bits, out_count, out_ids and out_d2 are all NULL)", who);
   if (a.out_ids && !a.order) return failf(FLOODER_E_ARG, "%s: out_ids needs order (tree row -> original id)", who);
-  const int cap = a.k <= 64 ? 64 : a.k <= 128 ? 128 : a.k <= 256 ? 256 : a.k <= 512 ? 512 : 1024;
+  const int cap = list_capacity(a.k);
   if ((a.out_ids || a.out_d2) && (ld_out < 1 || ld_out > cap))
     return failf(FLOODER_E_ARG, "%s: ld_out must be in 1..%d (the list capacity that holds capacity = %d)", who, cap, a.k);
   if (!masses || !target) return failf(FLOODER_E_ARG, "%s: masses and target must not be NULL", who);

@@ -40,87 +40,11 @@
 // word per listed column, planes plane_stride words apart.  The walk culls against the k-th key of the LARGEST k.
 
 #include "../../include/flooder_hip.h"
-#include "flood_common.hpp"
-#include "flood_bvh.hpp"
+#include "flood_knn_list.hpp"
 
 using namespace flooder;
 
 namespace {
-
-constexpr int BUF = 128;                 // keys of a wave's insertion buffer (two per lane in a merge)
-constexpr unsigned long long NOKEY = ~0ull;
-typedef unsigned long long wkey_t;
-
-// Same-wave hand-off through LDS: what the lanes wrote is complete before any lane reads it (the pairing used around
-// s_stack in flood_grad.hip, with the acquire side spelled out).
-__device__ __forceinline__ void lds_handoff() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// number of keys of the ascending a[0..n) that are below x
-__device__ __forceinline__ int keys_below(const wkey_t* a, int n, wkey_t x) {
-  int lo = 0;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[lo + half] < x) {
-      lo += half + 1;
-      n -= half + 1;
-    } else {
-      n = half;
-    }
-  }
-  return lo;
-}
-
-// The m <= BUF keys of buf (any order, distinct, none of them in the list) into the ascending list of k keys; what
-// ends up at a place >= k falls off.  Leaves buf free and the list visible to every lane.
-template <int SLOTS>
-__device__ __forceinline__ void merge_buffer(wkey_t* list, wkey_t* buf, int k, int m, int lane) {
-  lds_handoff();   // (the buffer's keys are in)
-  wkey_t b[2];
-  int rank[2], place[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    b[u] = lane + 64 * u < m ? buf[lane + 64 * u] : NOKEY;
-    rank[u] = 0;
-  }
-  for (int j = 0; j < m; ++j) {
-    const wkey_t x = buf[j];   // (one address: broadcast)
-    rank[0] += x < b[0] ? 1 : 0;
-    rank[1] += x < b[1] ? 1 : 0;
-  }
-  lds_handoff();   // (every lane has read the buffer before it is rewritten in order)
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (lane + 64 * u < m) {
-      buf[rank[u]] = b[u];
-      place[u] = rank[u] + keys_below(list, k, b[u]);
-    }
-  lds_handoff();   // (the sorted buffer is in)
-  wkey_t l[SLOTS];
-  int to[SLOTS];
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int i = lane + 64 * s;
-    to[s] = i;
-    if (i < k) {
-      l[s] = list[i];
-      to[s] = i + keys_below(buf, m, l[s]);
-    }
-  }
-  lds_handoff();   // (every lane has read the old list and the buffer)
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int i = lane + 64 * s;
-    if (i < k && to[s] != i && to[s] < k) list[to[s]] = l[s];
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (lane + 64 * u < m && place[u] < k) list[place[u]] = b[u];
-  lds_handoff();   // (the merged list is in)
-}
 
 // The columns of the epilogue, a compile-time variant of the ONE kernel: NoCols (flooder_knn_wide_f32) writes the word
 // of (k, stat) to out_bits[g]; WideCols (flooder_knn_wide_profile_f32) a word per listed (k', stat') with k' <= k to
@@ -306,12 +230,7 @@ struct KnnWideOp {
     if constexpr (DIM < 2) {
       return fail(FLOODER_E_ARG, "flooder_knn_wide_f32: dim must be in 2..8");
     } else {
-      // the list capacity that holds k: 64, 128, 256, 512 or 1024 keys
-      if (a.k <= 64) launch<1>(a, cols, lv, n_cells, st);
-      else if (a.k <= 128) launch<2>(a, cols, lv, n_cells, st);
-      else if (a.k <= 256) launch<4>(a, cols, lv, n_cells, st);
-      else if (a.k <= 512) launch<8>(a, cols, lv, n_cells, st);
-      else launch<16>(a, cols, lv, n_cells, st);
+      with_list_slots(a.k, [&](auto slots) { launch<decltype(slots)::value>(a, cols, lv, n_cells, st); });
       return check_launch("knn_wide");
     }
   }

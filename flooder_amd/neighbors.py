@@ -330,7 +330,7 @@ def _query_profile_hip(points: torch.Tensor, queries: torch.Tensor, columns, ind
     return bits
 
 
-_CAPACITIES = (64, 128, 256, 512, 1024)   # the list capacities of flooder_knn_mass_f32 (and of the wide kernel)
+_CAPACITIES = (64, 128, 256, 512, 1024)   # mirrors with_list_slots (csrc/flood_knn_list.hpp): the list capacities of the wide and mass entries
 
 
 def _list_capacity(max_neighbors) -> int:

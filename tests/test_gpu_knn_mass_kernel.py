@@ -4,8 +4,10 @@ integer masses (count, ids and ``"kth"`` exact, ``"dtm"`` exact against the floa
 bound), zero masses in front of the crossing, a heavy site, the not-reached rule, general float masses, ``sample_order``
 and the refusals.  The shapes are the smallest that can go wrong: a padded single leaf (15 points), one, two and three
 tree levels, none a multiple of 16; every point doubled in half of the cases (ties decided by id); 1, 63, 65 and 300
-cells; capacities 64, 256 and 1024; rows of the capacity and shorter.  Guard words behind every output; every launch is
-made twice and must write the same words."""
+cells; capacities 64, 256 and 1024; rows of the capacity and shorter.  Two more cases (``WRAP``: 16 684 cells, capacities 64
+and 256) make every wave of the grid-stride loop handle a second cell - a list that shrank to its crossing in one cell
+must start the next at its full length - in the unit, integer and zero mass tests.  Guard words behind every output;
+every launch is made twice and must write the same words."""
 
 import ctypes
 import functools
@@ -31,7 +33,15 @@ NS, DIMS, QS, CAPS = (15, 1000, 1025, 30_001, 70_001), (2, 3, 5, 8), (1, 63, 65,
 CASES = [(n, dim, (i + j) % 2 == 1, QS[(i + j) % 4], CAPS[(i + 2 * j) % 3])
          for i, n in enumerate(NS) for j, dim in enumerate(DIMS)]
 WHOLE_CLOUD = (1000, 3, False, 65, 1024)      # n_pts <= C: the list holds the whole cloud
-IDS = [f"n{n}-d{d}-{'dup' if dup else 'single'}-q{q}-c{c}" for n, d, dup, q, c in CASES]
+# more cells than the grid has waves (4 waves in each of 256 * 16 blocks), no multiple of 3: the query form; SLOTS 1 and 4
+WRAP = [(1025, 3, True, 4 * 256 * 16 + 300, 64), (1025, 3, True, 4 * 256 * 16 + 300, 256)]
+
+
+def case_ids(cases):
+    return [f"n{n}-d{d}-{'dup' if dup else 'single'}-q{q}-c{c}" for n, d, dup, q, c in cases]
+
+
+IDS = case_ids(CASES)
 
 
 def test_cases_cover_what_they_must():
@@ -41,6 +51,8 @@ def test_cases_cover_what_they_must():
     for n in NS:                                   # every size meets a capacity below it (but 15) and doubled points
         assert any(c[0] == n and c[2] for c in CASES) and (n == 15 or any(c[0] == n and c[4] < n for c in CASES))
     assert any(c[0] < c[4] for c in CASES)         # a cloud smaller than the capacity
+    assert any(c[3] > 4 * 256 * 16 for c in WRAP)  # the grid-stride loop wraps ...
+    assert {c[4] for c in WRAP} == {64, 256} and all(c[2] and c[3] % 3 for c in WRAP)   # ... with SLOTS = 1 and above
 
 
 @functools.lru_cache(maxsize=None)
@@ -198,7 +210,7 @@ def check_against_reference(c, masses, tau, got_kth, got_dtm, ld, exact_replay):
     return ref
 
 
-@pytest.mark.parametrize("n,dim,dup,n_cells,cap", CASES, ids=IDS)
+@pytest.mark.parametrize("n,dim,dup,n_cells,cap", CASES + WRAP, ids=IDS + case_ids(WRAP))
 def test_unit_masses_are_the_wide_kernel(n, dim, dup, n_cells, cap):
     c = case(n, dim, dup, n_cells, cap)
     ones = np.ones(n, dtype=np.float32)
@@ -216,7 +228,7 @@ def test_unit_masses_are_the_wide_kernel(n, dim, dup, n_cells, cap):
             assert bool((got["ids"][:, k:] == -1).all()) and bool((got["d2"][:, k:] == km.INF_WORD).all())
 
 
-@pytest.mark.parametrize("n,dim,dup,n_cells,cap", CASES, ids=IDS)
+@pytest.mark.parametrize("n,dim,dup,n_cells,cap", CASES + WRAP, ids=IDS + case_ids(WRAP))
 def test_integer_masses(n, dim, dup, n_cells, cap):
     """Masses in 1..9 and tau <= L = min(C, n): any L sites hold at least L, so every cell is reached."""
     c = case(n, dim, dup, n_cells, cap)
@@ -230,7 +242,8 @@ def test_integer_masses(n, dim, dup, n_cells, cap):
         assert ref["reached"].all()
 
 
-@pytest.mark.parametrize("n,dim,dup,n_cells,cap", [c for c in CASES if c[2]], ids=[i for i, c in zip(IDS, CASES) if c[2]])
+@pytest.mark.parametrize("n,dim,dup,n_cells,cap", [c for c in CASES if c[2]] + WRAP,
+                         ids=[i for i, c in zip(IDS, CASES) if c[2]] + case_ids(WRAP))
 def test_zero_masses_in_front_of_the_crossing(n, dim, dup, n_cells, cap):
     """Doubled points: the even id of a place has mass 0, the odd one a mass in 1..9 (the last point, which has no copy,
     too).  Equal d2 words order by id, so the copies of a place are neighbours in every list and its first L keys hold
