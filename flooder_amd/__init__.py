@@ -13,7 +13,8 @@ from .io import save_to_disk
 from .grad import FloodFiltration, flood_filtration, power_filtration, dtm_filtration
 from .profile import FloodProfile, flood_profile, power_profile, dtm_profile
 from .neighbors import (neighbor_distance, nearest_neighbors, distance_to_measure, distance_to_measure_profile,
-                        power_distance, power_nearest, distance_to_weighted_measure, voxel_measure)
+                        power_distance, power_nearest, distance_to_weighted_measure,
+                        distance_to_weighted_measure_profile, voxel_measure)
 from .synthetic import (
     generate_swiss_cheese_points,
     generate_annulus_points_2d,
@@ -40,6 +41,7 @@ __all__ = [
     "power_distance",
     "power_nearest",
     "distance_to_weighted_measure",
+    "distance_to_weighted_measure_profile",
     "voxel_measure",
     "generate_landmarks",
     "generate_grid",

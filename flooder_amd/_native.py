@@ -290,6 +290,11 @@ SIGNATURES = {
     # ... and the nearest sites of a weighted measure up to a cumulative mass: the same block (its k is the list
     # capacity), then masses, target (a device float64), ld_out and out_count (distance_to_weighted_measure)
     "flooder_knn_mass_f32": (c_int, [ctypes.POINTER(KnnWide), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    # ... and every (target, stat) column of that list from one walk at the largest target: the same block, then masses,
+    # n_cols, targets (a device float64 array), the host array col_stat (int32), plane_stride and the planes of counts
+    # (distance_to_weighted_measure_profile)
+    "flooder_knn_mass_profile_f32": (c_int, [ctypes.POINTER(KnnWide), c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                             c_void_p, c_void_p]),
     # the weighted filtration (flood_complex(point_weights=w)): the minimum of a value per tree row over every node, and
     # the power-distance sweep on the block of the sorted k-nearest sweep (k = 1) plus the weights and their node minima
     "flooder_node_min_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

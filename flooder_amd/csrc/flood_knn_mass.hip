@@ -43,6 +43,24 @@
 // (Hillis-Steele within a row, then + carry), so the result is the same run to run; across an ambiguous crossing the
 // value is continuous, the residual weight on the next key being about 0.
 //
+// Profile (flooder_knn_mass_profile_f32; distance_to_weighted_measure_profile): ONE walk to tau_max, the largest of the
+// columns' targets (formed by every wave from the device array: nothing goes through the host), and an epilogue - it,
+// and nothing else, is a compile-time variant (COLS) - that runs the crossing() scan of the final len places once per
+// column at tau_c and writes the word and the count of (tau_c, stat_c) to plane c.
+//   (5) Column c is the single call at (tau_c, stat_c) and the same capacity, word for word.  By (3) the final list
+//       holds every key of the cloud up to F(tau_max), in order.  F(tau_c) <= F(tau_max) for tau_c <= tau_max: the cloud's
+//       cumulative mass reaches the smaller target no later, and when it reaches neither within L keys both are the L-th
+//       key.  So the list also holds every key of the cloud up to F(tau_c) in order - the places 0 .. j_c of the list the
+//       single call at tau_c ends with.  M_j as crossing() computes it is a function of the places 0 .. j alone: the
+//       Hillis-Steele scan of a row gives lane l the sum of the lanes <= l in an order fixed by l, the carry is the
+//       total of the full rows in front, and places behind j (real keys here, emptied ones in the single call) enter
+//       neither.  So j_c, M_(j_c - 1), rho_c and the strided sum over 0 .. j_c are those of the single call.  If the
+//       walk's cell is not reached the list is the L smallest keys of the cloud, which is also what the single call at
+//       tau_c ends with: it crosses at the same place or, like the walk, nowhere (word +inf, count L).  A column with no
+//       crossing in a list that WAS cut (sums of masses that are no integers rounding to just below tau_c) takes the
+//       last place, the single entry's fallback; there, and only there, the two may read an ambiguous crossing
+//       differently, with a residual weight of about 0.
+//
 // No atomics, nothing in inline assembly; every output word is written once by plain vector stores.
 
 #include "../../include/flooder_hip.h"
@@ -135,12 +153,39 @@ __device__ __forceinline__ int merge_and_cross(wkey_t* list, wkey_t* buf, const 
   return j;
 }
 
-template <int DIM, int SLOTS>
+// The columns of the epilogue, a compile-time variant of the ONE kernel (the form of knn_wide_kernel): NoCols
+// (flooder_knn_mass_f32) walks to tau = *target and writes the word of (tau, stat) to out_bits[g]; MassCols
+// (flooder_knn_mass_profile_f32) walks to the largest of targets[0..n_cols) and writes a word and a count per listed
+// (tau_c, stat_c) to out_bits / out_count[c * plane_stride + g].  The walk and the merges do not know which it is.
+// target_t is what the kernel takes in the place of the target: the single entry's pointer, or the columns by value -
+// so the single entry's kernel keeps its argument list to the byte.
+struct NoCols {
+  typedef const double* __restrict__ target_t;
+};
+struct MassCols {
+  typedef MassCols target_t;
+  int64_t plane_stride;
+  const double* targets;   // DEVICE, n_cols
+  int n_cols;
+  int col_stat[FLOODER_KNN_COLS_MAX];
+};
+
+// The largest target of the columns (wave-uniform; every wave forms it itself: nothing goes through the host)
+__device__ __forceinline__ double walk_target(const MassCols& cols) {
+  double tau = cols.targets[0];
+  for (int c = 1; c < cols.n_cols; ++c) {
+    const double t = cols.targets[c];
+    tau = t > tau ? t : tau;
+  }
+  return tau;
+}
+
+template <int DIM, int SLOTS, class COLS>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_mass_kernel(
     const float* __restrict__ pts, int64_t n_pts, const float* __restrict__ nodes, Levels lv,
     const int32_t* __restrict__ order, const float* __restrict__ verts, const float* __restrict__ weights, int k1, int R,
     int64_t n_cells, int stat, const int32_t* __restrict__ sample_order, const float* __restrict__ masses,
-    const double* __restrict__ target, int ld_out, uint32_t* __restrict__ out_bits, int32_t* __restrict__ out_count,
+    const typename COLS::target_t target, int ld_out, uint32_t* __restrict__ out_bits, int32_t* __restrict__ out_count,
     int32_t* __restrict__ out_ids, uint32_t* __restrict__ out_d2) {
   constexpr int DP = padded_dim(DIM);
   constexpr int CAP = 64 * SLOTS;
@@ -157,7 +202,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_mass_kernel(
   const int top = lv.n_levels - 1;
   const int k = n_pts < CAP ? (int)n_pts : CAP;   // the list's length L: the capacity, or the whole cloud
   const int merge_at = k < 64 ? k : 64;
-  const double tau = *target;
+  double tau;   // the target of the walk
+  if constexpr (std::is_same<COLS, NoCols>::value) tau = *target;
+  else tau = walk_target(target);
   for (int64_t t = wave; t < n_cells; t += n_waves) {
     const int64_t g = sample_order ? (int64_t)(uint32_t)sample_order[t] : t;
     if (g >= n_cells) continue;   // (not a cell: the caller's order is out of bounds there, nothing is written)
@@ -259,72 +306,104 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void knn_mass_kernel(
     lds_handoff();
     // ---- the crossing of the final list (the same scan over the same len places as after the last merge); its keys,
     // their number and the statistic
-    int j = crossing(list, masses, len, tau, lane, m_prev, n_real);
-    if (j < 0 && len < k) {
-      // A crossing existed (len shrank) and the float64 sums of this arrangement round to just below tau - masses that
-      // are no integers only.  The crossing is the last place; its residual is about its whole mass.
-      j = len - 1;
-      m_prev -= (double)masses[(uint32_t)list[j]];
-    }
-    const int count = j >= 0 ? j + 1 : n_real;
-    if (out_ids || out_d2) {
-      const int64_t row = g * (int64_t)ld_out;
-      for (int i = lane; i < ld_out; i += 64) {
-        const wkey_t key = i < count ? list[i] : NOKEY;
-        if (out_ids) out_ids[row + i] = i < count ? (int32_t)(uint32_t)key : -1;
-        if (out_d2) out_d2[row + i] = i < count ? (uint32_t)(key >> 32) : INF_WORD;
+    if constexpr (std::is_same<COLS, NoCols>::value) {
+      int j = crossing(list, masses, len, tau, lane, m_prev, n_real);
+      if (j < 0 && len < k) {
+        // A crossing existed (len shrank) and the float64 sums of this arrangement round to just below tau - masses that
+        // are no integers only.  The crossing is the last place; its residual is about its whole mass.
+        j = len - 1;
+        m_prev -= (double)masses[(uint32_t)list[j]];
       }
-    }
-    if (out_count && lane == 0) out_count[g] = count;
-    if (out_bits) {
-      uint32_t word = INF_WORD;   // not reached
-      if (j >= 0) {
-        if (stat == 0) {
-          word = (uint32_t)(list[j] >> 32);
-        } else {
-          const float rho = (float)(tau - m_prev);
-          word = __float_as_uint(mass_statistic(list, masses, j, rho, (float)tau, lane));
+      const int count = j >= 0 ? j + 1 : n_real;
+      if (out_ids || out_d2) {
+        const int64_t row = g * (int64_t)ld_out;
+        for (int i = lane; i < ld_out; i += 64) {
+          const wkey_t key = i < count ? list[i] : NOKEY;
+          if (out_ids) out_ids[row + i] = i < count ? (int32_t)(uint32_t)key : -1;
+          if (out_d2) out_d2[row + i] = i < count ? (uint32_t)(key >> 32) : INF_WORD;
         }
       }
-      if (lane == 0) out_bits[g] = word;
+      if (out_count && lane == 0) out_count[g] = count;
+      if (out_bits) {
+        uint32_t word = INF_WORD;   // not reached
+        if (j >= 0) {
+          if (stat == 0) {
+            word = (uint32_t)(list[j] >> 32);
+          } else {
+            const float rho = (float)(tau - m_prev);
+            word = __float_as_uint(mass_statistic(list, masses, j, rho, (float)tau, lane));
+          }
+        }
+        if (lane == 0) out_bits[g] = word;
+      }
+    } else {
+      // Column c is the single call at (targets[c], col_stat[c]) - (5) of the header: the same scan over the places
+      // 0 .. j_c of the same keys, the same fallback, the same statistic.  No rows: lists are per target.
+      const MassCols& cols = target;
+      for (int c = 0; c < cols.n_cols; ++c) {
+        const double tau_c = cols.targets[c];
+        int j = crossing(list, masses, len, tau_c, lane, m_prev, n_real);
+        if (j < 0 && len < k) {   // (the list was cut and its sums round to just below tau_c: the last place)
+          j = len - 1;
+          m_prev -= (double)masses[(uint32_t)list[j]];
+        }
+        uint32_t word = INF_WORD;   // not reached
+        if (j >= 0) {
+          if (cols.col_stat[c] == 0) {
+            word = (uint32_t)(list[j] >> 32);
+          } else {
+            const float rho = (float)(tau_c - m_prev);
+            word = __float_as_uint(mass_statistic(list, masses, j, rho, (float)tau_c, lane));
+          }
+        }
+        if (lane == 0) {
+          const int64_t at = (int64_t)c * cols.plane_stride + g;
+          out_bits[at] = word;
+          if (out_count) out_count[at] = j >= 0 ? j + 1 : n_real;
+        }
+      }
     }
     lds_handoff();   // (every lane has read the list before the next cell resets it)
   }
 }
 
-// What the entry adds to the block of flooder_knn_wide_f32 (whose k is the capacity here)
+// What the entries add to the block of flooder_knn_wide_f32 (whose k is the capacity here)
 struct MassArgs {
   const float* masses;
-  const double* target;
+  const double* target;   // the single entry's tau; not used with columns (they carry theirs)
   int ld_out;
   int32_t* out_count;
 };
 
 template <int DIM>
 struct KnnMassOp {
-  template <int SLOTS>
-  static void launch(const flooder_knn_wide_t& a, const MassArgs& m, const Levels& lv, int64_t n_cells, hipStream_t st) {
-    hipLaunchKernelGGL((knn_mass_kernel<DIM, SLOTS>), stack_walk_grid(n_cells), dim3(64 * WAVES_PER_BLOCK), 0, st,
+  template <int SLOTS, class COLS>
+  static void launch(const flooder_knn_wide_t& a, const MassArgs& m, const COLS& cols, const Levels& lv, int64_t n_cells,
+                     hipStream_t st) {
+    typename COLS::target_t target;
+    if constexpr (std::is_same<COLS, NoCols>::value) target = m.target;
+    else target = cols;
+    hipLaunchKernelGGL((knn_mass_kernel<DIM, SLOTS, COLS>), stack_walk_grid(n_cells), dim3(64 * WAVES_PER_BLOCK), 0, st,
                        a.pts_sorted, a.n_pts, a.nodes, lv, a.order, a.verts, a.weights, a.k1, a.R, n_cells, a.stat,
-                       a.sample_order, m.masses, m.target, m.ld_out, a.out_bits, m.out_count, a.out_ids, a.out_d2);
+                       a.sample_order, m.masses, target, m.ld_out, a.out_bits, m.out_count, a.out_ids, a.out_d2);
   }
-  static int run(const flooder_knn_wide_t& a, const MassArgs& m, const Levels& lv, int64_t n_cells, hipStream_t st) {
+  template <class COLS>
+  static int run(const flooder_knn_wide_t& a, const MassArgs& m, const COLS& cols, const Levels& lv, int64_t n_cells,
+                 hipStream_t st) {
     if constexpr (DIM < 2) {
       return fail(FLOODER_E_ARG, "flooder_knn_mass_f32: dim must be in 2..8");
     } else {
-      with_list_slots(a.k, [&](auto slots) { launch<decltype(slots)::value>(a, m, lv, n_cells, st); });
+      with_list_slots(a.k, [&](auto slots) { launch<decltype(slots)::value>(a, m, cols, lv, n_cells, st); });
       return check_launch("knn_mass");
     }
   }
 };
 
-}  // namespace
-
-extern "C" int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* masses, const double* target, int32_t ld_out,
-                                    int32_t* out_count, void* stream) {
-  static const char* who = "flooder_knn_mass_f32";
-  flooder_knn_wide_t a;
-  if (int rc = take(p, a, "flooder_knn_mass_f32: bad parameter block (abi / size)")) return rc;
+// The checks of both entries (the profile entry has made its column checks already) and the launch
+template <class COLS>
+int knn_mass(const char* who, const flooder_knn_wide_t& a, const MassArgs& m, const COLS& cols, int64_t plane_stride,
+             void* stream) {
+  constexpr bool single = std::is_same<COLS, NoCols>::value;
   if (a.k < 1 || a.k > FLOODER_KNN_WIDE_MAX)
     return failf(FLOODER_E_ARG, "%s: capacity (the block's k) must be in 1..%d", who, FLOODER_KNN_WIDE_MAX);
   if (a.dim < 2 || a.dim > FLOODER_MAX_DIM) return failf(FLOODER_E_ARG, "%s: dim must be in 2..8", who);
@@ -335,16 +414,56 @@ extern "C" int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* ma
     return failf(FLOODER_E_ARG, "%s: n_simplices * R must be below 2^32 - 2", who);
   Levels lv;
   if (int rc = stack_walk_levels(who, a.n_pts, lv)) return rc;
-  if (!a.out_bits && !out_count && !a.out_ids && !a.out_d2)
-    return failf(FLOODER_E_ARG, "%s: no output (out_bits, out_count, out_ids and out_d2 are all NULL)", who);
-  if (a.out_ids && !a.order) return failf(FLOODER_E_ARG, "%s: out_ids needs order (tree row -> original id)", who);
-  const int cap = list_capacity(a.k);
-  if ((a.out_ids || a.out_d2) && (ld_out < 1 || ld_out > cap))
-    return failf(FLOODER_E_ARG, "%s: ld_out must be in 1..%d (the list capacity that holds capacity = %d)", who, cap, a.k);
-  if (!masses || !target) return failf(FLOODER_E_ARG, "%s: masses and target must not be NULL", who);
+  if (single) {
+    if (!a.out_bits && !m.out_count && !a.out_ids && !a.out_d2)
+      return failf(FLOODER_E_ARG, "%s: no output (out_bits, out_count, out_ids and out_d2 are all NULL)", who);
+    if (a.out_ids && !a.order) return failf(FLOODER_E_ARG, "%s: out_ids needs order (tree row -> original id)", who);
+    const int cap = list_capacity(a.k);
+    if ((a.out_ids || a.out_d2) && (m.ld_out < 1 || m.ld_out > cap))
+      return failf(FLOODER_E_ARG, "%s: ld_out must be in 1..%d (the list capacity that holds capacity = %d)", who, cap,
+                   a.k);
+    if (!m.masses || !m.target) return failf(FLOODER_E_ARG, "%s: masses and target must not be NULL", who);
+  } else {
+    if (a.out_ids || a.out_d2)
+      return failf(FLOODER_E_ARG, "%s: out_ids and out_d2 must be NULL (lists are per target)", who);
+    if (!a.out_bits) return failf(FLOODER_E_ARG, "%s: out_bits (the planes) must not be NULL", who);
+    if (!m.masses) return failf(FLOODER_E_ARG, "%s: masses must not be NULL", who);
+    if (a.n_simplices > 0 && a.R > 0 && plane_stride < a.n_simplices * (int64_t)a.R)
+      return failf(FLOODER_E_ARG, "%s: plane_stride must be at least n_simplices * R", who);
+  }
   if (a.n_simplices == 0 || a.R == 0) return FLOODER_OK;
   if (!a.pts_sorted || !a.nodes || !a.verts || !a.weights || a.k1 < 1 || a.R < 0 || a.n_simplices < 0)
     return failf(FLOODER_E_ARG, "%s: bad argument (null pointer, k1, R, n_simplices)", who);
-  const MassArgs m{masses, target, ld_out, out_count};
-  return dispatch_dim<KnnMassOp>(a.dim, a, m, lv, a.n_simplices * (int64_t)a.R, (hipStream_t)stream);
+  return dispatch_dim<KnnMassOp>(a.dim, a, m, cols, lv, a.n_simplices * (int64_t)a.R, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* masses, const double* target, int32_t ld_out,
+                                    int32_t* out_count, void* stream) {
+  flooder_knn_wide_t a;
+  if (int rc = take(p, a, "flooder_knn_mass_f32: bad parameter block (abi / size)")) return rc;
+  return knn_mass("flooder_knn_mass_f32", a, MassArgs{masses, target, ld_out, out_count}, NoCols{}, 0, stream);
+}
+
+extern "C" int flooder_knn_mass_profile_f32(const flooder_knn_wide_t* p, const float* masses, int n_cols,
+                                            const double* targets, const int32_t* col_stat, int64_t plane_stride,
+                                            int32_t* out_count, void* stream) {
+  static const char* who = "flooder_knn_mass_profile_f32";
+  flooder_knn_wide_t a;   // the walk of the single entry at the largest target of the columns
+  if (int rc = take(p, a, "flooder_knn_mass_profile_f32: bad parameter block (abi / size)")) return rc;
+  if (n_cols < 1 || n_cols > FLOODER_KNN_COLS_MAX)
+    return failf(FLOODER_E_ARG, "%s: n_cols must be in 1..%d", who, FLOODER_KNN_COLS_MAX);
+  if (!targets || !col_stat) return failf(FLOODER_E_ARG, "%s: targets and col_stat must not be NULL", who);
+  MassCols cols;
+  memset(&cols, 0, sizeof(cols));
+  cols.plane_stride = plane_stride;
+  cols.targets = targets;
+  cols.n_cols = n_cols;
+  for (int c = 0; c < n_cols; ++c) {
+    if (col_stat[c] != 0 && col_stat[c] != 1)
+      return failf(FLOODER_E_ARG, "%s: col_stat must be 0 (kth) or 1 (dtm)", who);
+    cols.col_stat[c] = col_stat[c];
+  }
+  return knn_mass(who, a, MassArgs{masses, nullptr, 0, out_count}, cols, plane_stride, stream);
 }

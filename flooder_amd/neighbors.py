@@ -21,6 +21,8 @@ more than 1024 points: ``flooder_knn_mass_f32``, the wide kernel's walk up to th
 reaches the target; detached by default, with ``differentiable=True`` the closed form of the rule in the sites, their
 masses and the queries, its backward two kernels of ``csrc/flood_mass_grad.hip`` over the sweep's int32 rows and counts.
 ``voxel_measure(differentiable=True)`` carries the gradient of the sites on to the cloud they are the centroids of.
+``distance_to_weighted_measure_profile`` evaluates several masses at once (``flooder_knn_mass_profile_f32``: one walk to
+the largest target, one crossing scan per column), every column equal to the single call.
 """
 
 from __future__ import annotations
@@ -362,11 +364,14 @@ def _check_point_masses(points: torch.Tensor, point_masses) -> None:
             raise ValueError("point_masses must have a positive total")
 
 
-def _mass_target(point_masses: torch.Tensor, mass: float) -> torch.Tensor:
+def _mass_target(point_masses: torch.Tensor, mass: float, total: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tau = mass * sum(point_masses) as a (1,) float64 tensor on the masses' device, without a host synchronisation.
     A tau within 1e-12 relative of an integer is that integer: (k / N) * N is k, so that unit masses at ``mass=k / N``
-    cross at the k-th neighbour whatever the rounding of the product."""
-    tau = (point_masses.detach().sum(dtype=torch.float64) * float(mass)).reshape(1)
+    cross at the k-th neighbour whatever the rounding of the product.  ``total``: that sum, when the caller has it (a
+    profile forms it once for all its masses)."""
+    if total is None:
+        total = point_masses.detach().sum(dtype=torch.float64)
+    tau = (total * float(mass)).reshape(1)
     near = torch.round(tau)
     return torch.where((near >= 1) & ((tau - near).abs() <= 1e-12 * tau), near, tau).contiguous()
 
@@ -429,8 +434,10 @@ def distance_to_weighted_measure(points: torch.Tensor, point_masses: torch.Tenso
     unit masses and ``mass=k / N`` it is that of ``distance_to_measure(neighbors=k, differentiable=True)`` bit for bit.
     CPU tensors: the kd-tree's ids, the closed form in float64 torch and ``index_add_``.
 
-    Out of scope here: ``dtm_profile`` / ``power_profile`` and ``flood_complex(neighbor_mass=...)`` over a weighted cloud
-    (pass the result as ``point_weights`` instead: ``flood_complex(points, L, point_weights=w)``, or use
+    Several masses at once: ``distance_to_weighted_measure_profile`` (one walk of the sites at the largest mass, every
+    column equal to the call here), and over a cloud's coreset ``dtm_profile(cell_size=...)``; ``power_profile`` takes any
+    (N, M) weights, these included.  Out of scope here: ``flood_complex(neighbor_mass=...)`` over a weighted cloud (pass
+    the result as ``point_weights`` instead: ``flood_complex(points, L, point_weights=w)``, or use
     ``dtm_filtration(cell_size=...)``), sharding, a float64 kernel.
     """
     on_gpu = _check_points(points, "distance_to_weighted_measure")
@@ -485,7 +492,23 @@ def _weighted_measure_cpu(points, point_masses, queries, tau: float, cap: int, s
     dist = dist.astype(np.float64)
     d2 = np.square(dist)
     mu = np.asarray(point_masses, dtype=np.float64)[ids]
-    M = np.cumsum(mu, axis=1)
+    val, count = _weighted_rule_cpu(d2, mu, np.cumsum(mu, axis=1), tau, stat, squared)
+    listed = np.arange(cap)[None, :] < count[:, None]
+    out_ids = np.full((Q, cap), -1, dtype=np.int64)
+    out_dist = np.full((Q, cap), np.inf)
+    out_ids[:, :kq] = ids
+    out_dist[:, :kq] = d2 if squared else dist
+    out_ids[~listed] = -1
+    out_dist[~listed] = np.inf
+    return val, out_ids, out_dist, count
+
+
+def _weighted_rule_cpu(d2: np.ndarray, mu: np.ndarray, M: np.ndarray, tau: float, stat: str, squared: bool):
+    """The rule at ONE target over the (Q, kq) squared distances ``d2`` of the nearest sites ascending, their masses
+    ``mu`` and the cumulative masses ``M`` (all float64) -> (value (Q,), +inf where the kq sites do not hold ``tau``;
+    count (Q,) int64: the crossing position + 1, kq where not reached).  ``distance_to_weighted_measure`` and every
+    column of its profile are this function: the same operations on the same numbers."""
+    Q, kq = d2.shape
     crossed = M >= tau
     reached = crossed.any(axis=1)
     j = np.argmax(crossed, axis=1)                                # the first crossing (0 where there is none)
@@ -498,14 +521,7 @@ def _weighted_measure_cpu(points, point_masses, queries, tau: float, cap: int, s
         val = ((mu * d2 * before).sum(axis=1) + (tau - m_prev) * d2[rows, j]) / tau
     val = np.where(reached, val if squared else np.sqrt(val), np.inf)
     count = np.where(reached, j + 1, kq).astype(np.int64)
-    listed = np.arange(cap)[None, :] < count[:, None]
-    out_ids = np.full((Q, cap), -1, dtype=np.int64)
-    out_dist = np.full((Q, cap), np.inf)
-    out_ids[:, :kq] = ids
-    out_dist[:, :kq] = d2 if squared else dist
-    out_ids[~listed] = -1
-    out_dist[~listed] = np.inf
-    return val, out_ids, out_dist, count
+    return val, count
 
 
 def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: int, stat: str,
@@ -543,6 +559,122 @@ def _weighted_sweep_hip(points, point_masses, queries, tau: torch.Tensor, cap: i
         _native.check(lib.flooder_knn_mass_f32(ctypes.byref(blk), _native.ptr(masses), _native.ptr(tau), cap,
                                                _native.ptr(count[a:b]), st), "flooder_knn_mass_f32")
     return ids, d2, count, bits
+
+
+def _weighted_columns(masses, neighbor_stat, who: str):
+    """The columns of a weighted mass profile: ``masses`` (a number or a non-empty sequence, every entry judged as
+    ``distance_to_weighted_measure`` judges ``mass``) x ``neighbor_stat`` (a name or a non-empty sequence of names); an
+    entry listed twice is refused -> (masses as floats, stats, columns ``[(m, s) for m in masses for s in stats]``)."""
+    if masses is None:
+        raise ValueError(f"{who} needs masses (real numbers in (0, 1])")
+    if isinstance(masses, (str, bytes)):
+        raise TypeError(f"masses must be a number or a sequence of numbers, got {masses!r}")
+    entries = list(masses) if hasattr(masses, "__iter__") else [masses]
+    stats = [neighbor_stat] if isinstance(neighbor_stat, str) or not hasattr(neighbor_stat, "__iter__") else list(neighbor_stat)
+    if not entries:
+        raise ValueError("masses must not be empty")
+    if not stats:
+        raise ValueError("neighbor_stat must not be empty")
+    for stat in stats:
+        core._check_neighbor_stat(stat)
+    for m in entries:
+        core.mass_neighbors(m, 1)   # (the checks of a mass, in the family's wording)
+    entries = [float(m) for m in entries]
+    if len(set(entries)) != len(entries):
+        raise ValueError(f"masses lists a value twice: {entries!r}")
+    if len(set(stats)) != len(stats):
+        raise ValueError(f"neighbor_stat lists a name twice: {stats!r}")
+    return entries, stats, [(m, s) for m in entries for s in stats]
+
+
+def distance_to_weighted_measure_profile(points: torch.Tensor, point_masses: torch.Tensor,
+                                         queries: Optional[torch.Tensor] = None, masses=None, *, neighbor_stat="dtm",
+                                         squared: bool = False, max_neighbors: Optional[int] = None,
+                                         return_counts: bool = False, index: Optional[core.PointIndex] = None):
+    """``distance_to_weighted_measure`` for several masses from ONE walk of the sites per query -> (Q, n_cols) tensor of
+    ``points``' dtype on its device; with ``return_counts=True`` ``(values, counts (Q, n_cols) int64)``.
+
+    ``masses`` is a number or a non-empty sequence, ``neighbor_stat`` a name or a sequence of names; every entry is
+    judged as ``distance_to_weighted_measure`` judges it, in its words, before any work is done, and an entry listed
+    twice is refused ("lists a value twice").  The columns are ``[(m, s) for m in masses for s in stats]`` and column c
+    is ``torch.equal`` to ``distance_to_weighted_measure(points, point_masses, queries, mass=m_c, neighbor_stat=s_c,
+    squared=squared, max_neighbors=max_neighbors)``, its count that call's ``count`` - a query that is not reached at a
+    mass (+inf, count min(L, N)) included, whatever the other columns of its row are.  ``points``, ``point_masses``,
+    ``queries`` (None: the sites themselves), ``max_neighbors``, ``index`` and the checks on them are those of
+    ``distance_to_weighted_measure``; Q = 0 gives empty results.  Detached, not differentiable
+    (``distance_to_weighted_measure(differentiable=True)`` with one mass is).
+
+    ROCm tensors (float32, 2 to 8 dimensions) run ``flooder_knn_mass_profile_f32``: one launch per group of queries, the
+    walk of ``flooder_knn_mass_f32`` to the LARGEST target - the list a wave ends with holds every site up to that
+    crossing in order, so the crossing of every smaller target lies in it, and the cumulative mass at a place depends on
+    the places in front of it alone: the epilogue scans the list once per column.  The targets are formed on the device
+    by the single call's rule, each bit for bit its tau; only the argument checks synchronise.  At most 64 columns.  CPU
+    tensors (float32, float64; any dimension): one kd-tree query at min(L, N) neighbours - what the single call queries
+    whatever the mass - and the float64 rule per column."""
+    who = "distance_to_weighted_measure_profile"
+    on_gpu = _check_points(points, "distance_to_weighted_measure")
+    _check_point_masses(points, point_masses)
+    entries, stats, columns = _weighted_columns(masses, neighbor_stat, who)
+    if on_gpu and len(columns) > _native.KNN_COLS_MAX:
+        raise ValueError(f"{who} on ROCm tensors takes at most {_native.KNN_COLS_MAX} columns, got {len(columns)}")
+    cap = _list_capacity(max_neighbors)
+    queries = _check_queries_and_index(points, queries, index, on_gpu)
+    points, point_masses, queries = points.detach(), point_masses.detach(), queries.detach()
+    Q, n_cols = queries.shape[0], len(columns)
+    if Q == 0:
+        value = torch.empty((0, n_cols), dtype=points.dtype, device=points.device)
+        return (value, torch.empty((0, n_cols), dtype=torch.int64, device=points.device)) if return_counts else value
+    total = point_masses.sum(dtype=torch.float64)
+    taus = [_mass_target(point_masses, m, total) for m in entries]          # each the single call's tau, bit for bit
+    if on_gpu:
+        targets = torch.cat([t for t in taus for _ in stats]).contiguous()
+        bits, count = _weighted_profile_hip(points, point_masses, queries, targets,
+                                            [core.NEIGHBOR_STATS.index(s) for _, s in columns], cap, index)
+        value = _root_of_bits(_native.load(), bits, squared, _native.current_stream_ptr(points.device))
+        value = value.t().contiguous()
+        return (value, count.t().contiguous().long()) if return_counts else value
+    kq = min(cap, points.shape[0])
+    dist, ids = _kdtree_query(points, queries, kq)
+    d2 = np.square(dist.astype(np.float64))
+    mu = np.asarray(point_masses, dtype=np.float64)[ids]
+    M = np.cumsum(mu, axis=1)
+    cols = [_weighted_rule_cpu(d2, mu, M, float(tau[0]), s, squared) for tau in taus for s in stats]
+    value = torch.stack([torch.as_tensor(v).to(points.dtype) for v, _ in cols], dim=1)
+    return (value, torch.stack([torch.as_tensor(c) for _, c in cols], dim=1)) if return_counts else value
+
+
+def _weighted_profile_hip(points, point_masses, queries, targets: torch.Tensor, col_stats, cap: int,
+                          index: Optional[core.PointIndex]):
+    """``_weighted_sweep_hip`` for every (target, stat) column at once -> ((n_cols, Q) int32 words of the squared
+    statistics, (n_cols, Q) int32 counts).  Per group of queries (24 B of keys, orders and sort scratch + 8 B per column
+    each, within ``core.SORTED_WORKSPACE_BYTES``) ONE ``flooder_knn_mass_profile_f32``; a group's slice of a plane is
+    contiguous, its planes are Q words apart: the entry's ``plane_stride``."""
+    lib = _native.load()
+    dev = points.device
+    torch.cuda.set_device(dev)
+    st = _native.current_stream_ptr(dev)
+    index = _index_of(points, index)
+    q = queries.contiguous()
+    Q, dim = q.shape
+    n_cols = len(col_stats)
+    col_stat = (ctypes.c_int32 * n_cols)(*[int(s) for s in col_stats])
+    masses = point_masses.to(torch.float32).contiguous()
+    one = torch.ones((1, 1), dtype=torch.float32, device=dev)
+    bits = torch.empty((n_cols, Q), dtype=torch.int32, device=dev)
+    count = torch.empty((n_cols, Q), dtype=torch.int32, device=dev)
+    key_bits = int(lib.flooder_sample_key_bits(dim))
+    per_group = max(1, min(Q, int(core.SORTED_WORKSPACE_BYTES) // (24 + 8 * n_cols), (1 << 32) - 3))
+    for a in range(0, Q, per_group):
+        b = min(Q, a + per_group)
+        verts = q[a:b].unsqueeze(1)                  # (b - a, 1, dim): one vertex per "simplex"
+        _, sort_state = core._zeroed_queue(lib, dev, b - a)
+        order = core._sorted_sample_order(lib, st, index, verts, one, sort_state, None, key_bits)
+        blk = _native.KnnWide(k=cap, stat=0, order=index.order32, sample_order=order, out_bits=_native.ptr(bits) + 4 * a,
+                              **core._knn_block_fields(index, verts, one))
+        _native.check(lib.flooder_knn_mass_profile_f32(ctypes.byref(blk), _native.ptr(masses), n_cols,
+                                                       _native.ptr(targets), col_stat, Q, _native.ptr(count) + 4 * a, st),
+                      "flooder_knn_mass_profile_f32")
+    return bits, count
 
 
 def voxel_measure(points: torch.Tensor, cell_size: float, differentiable: bool = False):

@@ -237,7 +237,8 @@ def dtm_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], masse
                 max_dimension: Optional[int] = None, points_per_edge: Optional[int] = 30,
                 num_rand: Optional[int] = None, start_idx: Optional[int] = 0, *, neighbors=None, neighbor_stat="dtm",
                 return_simplex_tree: bool = False, method: Optional[str] = None,
-                index: Optional["core.PointIndex"] = None) -> FloodProfile:
+                index: Optional["core.PointIndex"] = None, cell_size: Optional[float] = None,
+                max_neighbors: Optional[int] = None) -> FloodProfile:
     """The DTM-weighted Flood filtration for every mass of a list, from one pass: ``power_profile`` with
     ``distance_to_measure_profile(points, masses=masses, neighbors=neighbors, neighbor_stat=neighbor_stat)`` as its
     weights.  For every column ``(k, stat)`` of ``prof.columns`` (``[(k, s) for k in ks for s in stats]``, k the
@@ -250,11 +251,40 @@ def dtm_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], masse
     Exactly one of ``masses`` and ``neighbors`` is given; every entry is judged as ``distance_to_measure`` judges it.
     One ``PointIndex`` serves the weights, the landmark selection and the sweep; the weights cost one wide k-nearest
     sweep at the largest k, the filtrations one weighted sweep per group of 8 columns.  What a scan over the mass is
-    for: choosing it (README, "Choosing the mass")."""
-    from .neighbors import _check_points, _measure_columns, distance_to_measure_profile
+    for: choosing it (README, "Choosing the mass").
 
+    ``cell_size=c``: the weights over the cloud's CORESET, for masses of more than 1024 points - ``(sites, mu) =
+    voxel_measure(points, c)`` once, one index of the sites, and ``distance_to_weighted_measure_profile(sites, mu,
+    points, masses, neighbor_stat=neighbor_stat, max_neighbors=max_neighbors)`` as the weights: one walk of the sites
+    per point at the largest mass.  The columns are still ``(k, stat)`` with k = ``core.mass_neighbors(m, N)``, the number
+    of POINTS the mass stands for (it may be far above 1024; two masses that give the same k are refused), and
+
+        ``prof[(k, stat)] == flood_complex(points, landmarks, ..., point_weights=distance_to_weighted_measure(sites, mu,
+        points, mass=m, neighbor_stat=stat, max_neighbors=max_neighbors))``
+
+    exactly.  A coreset is addressed by mass: ``neighbors`` together with ``cell_size`` is refused, and so is
+    ``max_neighbors`` (the list capacity of ``distance_to_weighted_measure``) without ``cell_size``.  The weighted sweep
+    needs finite weights: a mass at which some point's ``max_neighbors`` nearest sites do not hold it raises a
+    ``ValueError`` that names the mass."""
+    from .neighbors import (_check_points, _measure_columns, _weighted_columns, distance_to_measure_profile,
+                            distance_to_weighted_measure_profile, voxel_measure)
+
+    if cell_size is None and max_neighbors is not None:
+        raise ValueError("dtm_profile: max_neighbors is the list capacity of the coreset's weighted measure and needs "
+                         "cell_size")
+    if cell_size is not None and neighbors is not None:
+        raise ValueError("dtm_profile: a coreset is addressed by mass - pass masses, not neighbors, with cell_size")
     on_gpu = _check_points(points, "distance_to_measure")
-    _, _, columns, aligned = _measure_columns(points, masses, neighbors, neighbor_stat, "dtm_profile")
+    if cell_size is not None:
+        entries, stats, _ = _weighted_columns(masses, neighbor_stat, "dtm_profile")
+        n = points.shape[0]
+        ks = [core.mass_neighbors(m, n) for m in entries]
+        if len(set(ks)) != len(ks):
+            raise ValueError(f"masses lists a value twice: {entries!r} gives k = {ks!r}")
+        columns = [(k, s) for k in ks for s in stats]
+        aligned = tuple(m for m in entries for _ in stats)
+    else:
+        _, _, columns, aligned = _measure_columns(points, masses, neighbors, neighbor_stat, "dtm_profile")
     if method in ("cell", "ball"):   # (before the weights are computed; the other refusals of the weighted sweep are
         raise ValueError(core._POWER_REFUSALS["method"].format(method=method))   # _check_points' for these tensors)
     bvh = "bvh" if method is None or method == "auto" else method
@@ -265,8 +295,18 @@ def dtm_profile(points: torch.Tensor, landmarks: Union[int, torch.Tensor], masse
         if index is None:
             index = core.PointIndex(points.to(torch.float32))
             core._remember_index(points, index)
-    weights = distance_to_measure_profile(points, None, masses, neighbors=neighbors, neighbor_stat=neighbor_stat,
-                                          index=index)
+    if cell_size is not None:
+        sites, mu = voxel_measure(points.detach(), cell_size)
+        weights = distance_to_weighted_measure_profile(sites, mu, points.detach(), entries, neighbor_stat=stats,
+                                                       max_neighbors=max_neighbors)
+        missed = (~torch.isfinite(weights)).sum(dim=0).tolist()
+        for c, m in enumerate(missed):
+            if m:
+                raise ValueError(f"dtm_profile: {m} of {n} points were not reached at mass {aligned[c]!r} - their nearest "
+                                 f"sites of the coreset do not hold it; coarsen cell_size or lower the mass")
+    else:
+        weights = distance_to_measure_profile(points, None, masses, neighbors=neighbors, neighbor_stat=neighbor_stat,
+                                              index=index)
     prof = _power_profile(points, landmarks, weights, columns, max_dimension, points_per_edge, num_rand, start_idx,
                           return_simplex_tree, bvh, index)
     prof.masses = aligned

@@ -1181,6 +1181,37 @@ int flooder_knn_mass_f32(const flooder_knn_wide_t* p, const float* masses, const
                          int32_t* out_count, void* stream);
 
 /*
+ * flooder_knn_mass_profile_f32: ONE walk of flooder_knn_mass_f32 at tau_max = max(targets[0..n_cols)) that writes a
+ * plane of statistic words and a plane of counts for every listed (tau_c, stat_c) column
+ * (flooder_amd.distance_to_weighted_measure_profile).  A wave ends a cell with every key of the cloud up to the
+ * crossing of tau_max, ascending; the crossing of a smaller target lies in that list, and the cumulative mass AT a place
+ * is a function of the places up to it alone (the scan of a row of 64 plus the carry of the rows in front) - so
+ *   out_bits[c * plane_stride + g]   and   out_count[c * plane_stride + g]
+ * equal, word for word, what flooder_knn_mass_f32 with *target = targets[c], stat = col_stat[c] and the same capacity
+ * writes to out_bits[g] and out_count[g] (rho_c = (float)(tau_c - M_(j_c - 1)), the sum divided by (float)tau_c;
+ * csrc/flood_knn_mass.hip, (5), has the argument).  A column that is not reached in a list that was never cut has the
+ * word of +inf and the count L; the smaller columns of such a cell are still those of their single calls.  For masses
+ * that are no integers a column whose prefix sums round to just below tau_c in a list that WAS cut takes the last
+ * place, as the single entry does; such a crossing is ambiguous (rho about 0) and the single call may read it at the
+ * neighbouring place.  tau_max is formed on the device by every wave; nothing is read back to the host.
+ * Arguments: the block of flooder_knn_wide_f32 as flooder_knn_mass_f32 takes it (its k is the CAPACITY; its stat is not
+ * used - the columns carry theirs - and must still be 0 or 1; its out_bits is the plane buffer; out_ids and out_d2 must
+ * be NULL: lists are per target).  Then: masses as there; n_cols in 1..FLOODER_KNN_COLS_MAX; targets, a DEVICE array of
+ * n_cols float64 (tau_c > 0 and finite are the caller's contract); col_stat, a HOST array of n_cols int32 read before
+ * the launch and not kept; plane_stride, in words, at least n_simplices * R (a driver that works in groups of cells
+ * hands over a slice of a (n_cols, Q) buffer: the words between and behind the planes are never touched); out_count, the
+ * planes of counts with the same stride, may be NULL.  Two columns with the same target and stat are legal (the targets
+ * live on the device: the host cannot compare them).
+ * Refused (FLOODER_E_ARG, the message opens with the entry's name), all before a device pointer is read: a bad block
+ * size or abi; n_cols outside 1..FLOODER_KNN_COLS_MAX; targets or col_stat NULL; a col_stat that is not 0 or 1; what
+ * flooder_knn_mass_f32 refuses of capacity, dim, stat, n_pts, n_simplices * R and the stack encoding; out_ids or out_d2
+ * not NULL; out_bits NULL; masses NULL; plane_stride < n_simplices * R.  Then n_simplices == 0 or R == 0: FLOODER_OK,
+ * nothing is touched.
+ */
+int flooder_knn_mass_profile_f32(const flooder_knn_wide_t* p, const float* masses, int n_cols, const double* targets,
+                                 const int32_t* col_stat, int64_t plane_stride, int32_t* out_count, void* stream);
+
+/*
  * ---- Weighted filtration: the power distance (csrc/flood_power.hip; flood_complex(point_weights=w)) ----------------
  * Every point x carries a weight w_x >= 0 and a sample p is measured by f(p)^2 = min_x ( |p - x|^2 + w_x^2 ).
  *
