@@ -2107,6 +2107,8 @@ def _sweep_dimension_cell(index: PointIndex, verts: torch.Tensor, weights: torch
                 blk.planes_ready = 1
             _native.check(lib.flooder_fused_cell(ctypes.byref(blk), st), "flooder_fused_cell")
         with _span(timer, "fallback"):
+            if not CELL_PROBE:   # (the sweeps in front probe when the block names `top`; the finish's own probe pass needs it)
+                blk.top, blk.top_list = ws.top.data_ptr(), ws.top_list.data_ptr()
             _native.check(lib.flooder_fused_finish(ctypes.byref(blk), st), "flooder_fused_finish")
         if stats is not None:  # (diagnostic runs only: a host synchronisation)
             c_d = ws.defer_ctl[:_native.DEFER_CTL_WORDS].tolist()

@@ -7,8 +7,6 @@ wait for the default stream outlasts the hold (``held.query()`` is True when the
 pinned progress words of the batched landmark selection on nine streams past the tag wrap, the module-level tables filled
 on one stream and used on another, and the landmark selection above ``flooder_fps_batched_max_points()``.
 Runs on a real MI355X only (-m gpu)."""
-import warnings
-
 import numpy as np
 import pytest
 import torch
@@ -18,11 +16,16 @@ from flooder_amd import _native, core
 from helpers import get_options, set_options
 from oracle import flood_oracle as fo
 import streams_helper as sh
+import gpu_paths
+from gpu_paths import (DEV, FPS_CASES, INDEX_CASES, N_LMS, NEIGHBOUR_CALLS, check_flood_path, check_neighbour_result, flood,
+                       flood_arguments, flood_cases, grad_calls, grad_clouds, index_parts, profile_arguments, profile_calls,
+                       randn, watch_sweeps, with_grad)
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 N = 20_000
+FLOOD_CASES = flood_cases(N)
+PROFILE_CALLS = profile_calls(N)
 
 
 @pytest.fixture(scope="module")
@@ -80,10 +83,6 @@ def options(lib):
     set_options(lib, keep)
 
 
-def randn(n, dim, seed, scale=1.0):
-    return (scale * torch.randn(n, dim, generator=torch.Generator().manual_seed(seed))).to(DEV)
-
-
 # --------------------------------------------------------------------------------------------------- 1. the premise
 def test_premise_a_side_stream_does_not_wait_for_the_held_default_stream(side):
     x = torch.arange(1 << 16, device=DEV, dtype=torch.float32)
@@ -128,13 +127,7 @@ def test_the_held_call_notices_a_misplaced_launch_and_a_device_wide_wait(side, m
 
 
 # --------------------------------------------------------------------------------------------------- 2. index
-def index_parts(idx):
-    """Rows, box tree, order, density grid, and the lanes of the box that are defined ([0:dim] min, [8:8+dim] max)."""
-    return ([idx.pts, idx.nodes, idx.order32, idx.box[:idx.dim], idx.box[8:8 + idx.dim]]
-            + ([] if idx.dens is None else [idx.dens]))
-
-
-@pytest.mark.parametrize("dim,by_caller", [(2, True), (2, False), (3, True), (3, False), (6, True)])
+@pytest.mark.parametrize("dim,by_caller", INDEX_CASES)
 def test_held_point_index(dim, by_caller, side, monkeypatch):
     monkeypatch.setattr(core, "SORT_STATE_BY_CALLER", by_caller)
     real, decoy = randn(N, dim, 10 + dim), randn(N, dim, 20 + dim)
@@ -168,18 +161,6 @@ def test_held_index_from_host_in_chunks(free_streams):
 
 
 # --------------------------------------------------------------------------------------------------- 2. landmarks
-N_LMS = 300
-FPS_CASES = {
-    # name: (dim, method, FPS_BATCHED, options of the library, launches: None = not the batched entry)
-    "brute": (3, "brute", True, {}, None),
-    "one_per_launch": (3, "bucket", False, {}, None),
-    "batched": (3, "bucket", True, dict(fps_switch=8), "batched"),
-    "batched_rounds": (3, "bucket", True, dict(fps_switch=8, fps_rounds=1), "batched"),
-    "batched_lane_best": (3, "bucket", True, dict(fps_switch=8, fps_lane_best=1), "batched"),
-    "batched_5d": (5, "bucket", True, dict(fps_switch=8), "batched"),
-}
-
-
 @pytest.mark.parametrize("case", list(FPS_CASES))
 def test_held_landmark_selection(case, side, options, monkeypatch):
     dim, method, batched, opts, launches = FPS_CASES[case]
@@ -203,156 +184,43 @@ def test_held_landmark_selection(case, side, options, monkeypatch):
 
 
 # --------------------------------------------------------------------------------------------------- 2. flood_complex
-def flood(p, w=None, n_lms=50, **kw):
-    if kw.get("num_rand") is not None:
-        torch.manual_seed(7)     # (the weights are drawn from the CPU generator)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)   # (float64: the documented warning)
-        return fa.flood_complex(p, n_lms, point_weights=w, **kw)
-
-
-FLOOD_CASES = {
-    # name: (dim, dtype, arguments, the dimension-pass driver of core that must run)
-    "2d": (2, torch.float32, dict(points_per_edge=20), "_sweep_dimension_cell"),
-    "3d": (3, torch.float32, dict(points_per_edge=12), "_sweep_dimension_cell"),
-    "3d_bvh": (3, torch.float32, dict(points_per_edge=12, method="bvh"), "_sweep_dimension_bvh"),
-    "3d_ball": (3, torch.float32, dict(points_per_edge=12, method="ball"), "_sweep_dimension_hip"),
-    "6d": (6, torch.float32, dict(n_lms=24, max_dimension=2, points_per_edge=8), "_sweep_dimension_bvh"),
-    "3d_float64": (3, torch.float64, dict(points_per_edge=10), "_sweep_dimension_f64"),
-    "3d_neighbors_4": (3, torch.float32, dict(points_per_edge=10, neighbors=4, neighbor_stat="kth"), "_sweep_dimension_knn"),
-    "3d_mass_100": (3, torch.float32, dict(points_per_edge=8, neighbor_mass=100 / N, neighbor_stat="dtm"),
-                    "_sweep_dimension_knn"),
-    "3d_power": (3, torch.float32, dict(points_per_edge=12), "_sweep_dimension_power"),
-    "3d_num_rand": (3, torch.float32, dict(points_per_edge=None, num_rand=300), "_sweep_dimension_cell"),
-}
-SWEEP_DRIVERS = ("_sweep_dimension_cell", "_sweep_dimension_bvh", "_sweep_dimension_hip", "_sweep_dimension_f64",
-                 "_sweep_dimension_knn", "_sweep_dimension_power")
-
-
-def watch_sweeps(monkeypatch):
-    """Which dimension-pass drivers of ``core`` run from now on, and with how many neighbours -> (set of names, set of k)."""
-    ran, ks = set(), set()
-    for name in SWEEP_DRIVERS:
-        def watched(*a, _name=name, _f=getattr(core, name), **k):
-            ran.add(_name)
-            if _name == "_sweep_dimension_knn":
-                ks.add(int(a[4]))
-            return _f(*a, **k)
-        monkeypatch.setattr(core, name, watched)
-    return ran, ks
-
-
 @pytest.mark.parametrize("case", list(FLOOD_CASES))
 def test_held_flood_complex(case, side, monkeypatch):
     dim, dtype, kw, driver = FLOOD_CASES[case]
     ran, ks = watch_sweeps(monkeypatch)
-    real, decoy = randn(N, dim, 60 + dim).to(dtype), randn(N, dim, 70 + dim).to(dtype)
     if case == "3d_mass_100":
         assert core.mass_neighbors(kw["neighbor_mass"], N) == 100 > 64
-    args = [(real,), (decoy,)]
-    if case == "3d_power":
-        g = torch.Generator().manual_seed(8)
-        args = [(p, (0.2 * torch.rand(N, generator=g)).to(DEV)) for (p,) in args]
+    args = flood_arguments(case, N, (60, 70))
     ref = sh.held_call(f"flood_complex {case}", lambda *a: flood(*a, **kw), args[0], args[1], side)
     keys, values = ref
     assert max(len(k) for k in keys) == dim + 1 and np.isfinite(values).all() and values.max() > 0
-    # the path: the driver the case is about ran, the default cell sweep only where it is the case; the k-nearest cases
-    # at their k (4: the register ladder; 100 > core.KNN_MAX: flooder_knn_wide_f32)
-    assert driver in ran and (driver == "_sweep_dimension_cell" or "_sweep_dimension_cell" not in ran), sorted(ran)
-    if driver == "_sweep_dimension_knn":
-        assert ks == ({4} if case == "3d_neighbors_4" else {100}) and core.KNN_MAX < 100
+    check_flood_path(case, N, ran, ks)
 
 
 # --------------------------------------------------------------------------------------------------- 2. neighbours
-def weighted_measure(p, q, cell, mass, cap):
-    sites, mu = fa.voxel_measure(p, cell)
-    v, ids, dist, count = fa.distance_to_weighted_measure(sites, mu, q, mass=mass, max_neighbors=cap, return_neighbors=True)
-    return [sites, mu, v, ids, dist, count]
-
-
-NEIGHBOUR_CALLS = {
-    "neighbor_distance k=8 dtm": lambda p, q, w: fa.neighbor_distance(p, q, neighbors=8, neighbor_stat="dtm"),
-    "nearest_neighbors k=8": lambda p, q, w: list(fa.nearest_neighbors(p, q, neighbors=8)),
-    "distance_to_measure k=16": lambda p, q, w: fa.distance_to_measure(p, q, neighbors=16),
-    "distance_to_measure k=100": lambda p, q, w: list(fa.distance_to_measure(p, q, neighbors=100, return_neighbors=True)),
-    "distance_to_measure_profile": lambda p, q, w: fa.distance_to_measure_profile(p, q, neighbors=(4, 32, 100)),
-    "power_distance": lambda p, q, w: fa.power_distance(p, w, q),
-    "power_nearest": lambda p, q, w: list(fa.power_nearest(p, w, q)),
-    "distance_to_weighted_measure": lambda p, q, w: weighted_measure(p, q, 2.0, 0.02, 64),
-}
-
-
 @pytest.fixture(scope="module")
 def neighbour_clouds():
-    """Integer-valued Gaussian clouds (ties are decided by id; dense in the middle, single points far out) and queries
-    that reach beyond them; weights for the power distance."""
-    out = []
-    for seed in (80, 90):
-        g = torch.Generator().manual_seed(seed)
-        p = torch.round(8 * torch.randn(N, 3, generator=g)).to(DEV)
-        q = torch.round(10 * torch.randn(3000, 3, generator=g)).to(DEV)
-        w = torch.randint(0, 6, (N,), generator=g).float().to(DEV)
-        out.append((p, q, w))
-    return out
+    return gpu_paths.neighbour_clouds(N, 3000)
 
 
 @pytest.mark.parametrize("call", list(NEIGHBOUR_CALLS))
 def test_held_neighbour_family(call, side, neighbour_clouds):
     real, decoy = neighbour_clouds
     ref = sh.held_call(call, NEIGHBOUR_CALLS[call], real, decoy, side)
-    if call == "distance_to_weighted_measure":
-        missed = int(np.isinf(ref[2]).sum())
-        assert 0 < missed < ref[2].shape[0], f"{missed} of {ref[2].shape[0]} queries not reached: the case needs both kinds"
+    check_neighbour_result(call, ref)
 
 
 # --------------------------------------------------------------------------------------------------- 2. profiles
-def tables(prof, dim):
-    return [prof.table(d)[1] for d in range(dim + 1)]
-
-
-PROFILE_CALLS = {
-    "flood_profile": lambda p, w: tables(fa.flood_profile(p, 40, points_per_edge=8, neighbors=(1, 4, 16),
-                                                          neighbor_stat=("kth", "dtm")), 3),
-    "power_profile": lambda p, w: tables(fa.power_profile(p, 40, w, points_per_edge=8), 3),
-    "dtm_profile": lambda p, w: tables(fa.dtm_profile(p, 40, masses=(20 / N, 100 / N), points_per_edge=8), 3),
-}
-
-
 @pytest.mark.parametrize("call", list(PROFILE_CALLS))
 def test_held_profiles(call, side):
-    g = torch.Generator().manual_seed(11)
-    args = [(randn(N, 3, 100 + i), (0.2 * torch.rand(N, 3, generator=g)).to(DEV)) for i in range(2)]
+    args = profile_arguments(N)
     ref = sh.held_call(call, PROFILE_CALLS[call], args[0], args[1], side)
     assert all(np.isfinite(t).all() for t in ref) and ref[3].shape[1] >= 2
 
 
 # --------------------------------------------------------------------------------------------------- 2. gradients
-def with_grad(build):
-    """f(points, ...) for the held call: a leaf made on the current stream, ``build(leaf, ...)`` -> differentiable
-    tensors, the gradient of a fixed weighted sum of them; the values and the gradient."""
-    def f(p, *rest):
-        x = p.clone().requires_grad_(True)
-        values = build(x, *rest)
-        loss = sum((torch.linspace(0.5, 1.5, v.numel(), device=v.device) * torch.nan_to_num(v, posinf=0.0).flatten()).sum()
-                   for v in values)
-        (grad,) = torch.autograd.grad(loss, x)
-        return [v.detach() for v in values] + [grad]
-    return f
-
-
 GRAD_N = 8000
-GRAD_KW = dict(points_per_edge=8)
-GRAD_CALLS = {
-    "flood_filtration": lambda x: fa.flood_filtration(x, 40, **GRAD_KW).values,
-    "flood_filtration 2-D": lambda x: fa.flood_filtration(x[:, :2].contiguous(), 40, points_per_edge=12).values,
-    "power_filtration": lambda x: fa.power_filtration(x, 40, 0.1 * x.detach().abs().sum(dim=1), **GRAD_KW).values,
-    "dtm_filtration mass": lambda x: fa.dtm_filtration(x, 40, 100 / GRAD_N, **GRAD_KW).values,
-    "dtm_filtration cell_size": lambda x: fa.dtm_filtration(x, 40, 0.05, cell_size=0.1, max_neighbors=256, **GRAD_KW).values,
-    "distance_to_measure differentiable k=16": lambda x: [fa.distance_to_measure(x, neighbors=16, differentiable=True)],
-    "distance_to_measure differentiable k=100": lambda x: [fa.distance_to_measure(x, neighbors=100, differentiable=True)],
-    "distance_to_weighted_measure differentiable": lambda x: [fa.distance_to_weighted_measure(
-        *fa.voxel_measure(x, 0.1, differentiable=True), x, 0.05, max_neighbors=256, differentiable=True)],
-}
+GRAD_CALLS = grad_calls(GRAD_N)
 # calls whose step 5 (still held when the outputs are on the host) is not asserted, with the reason (none so far)
 GRAD_WITHOUT_STEP_5 = {}
 
@@ -361,7 +229,7 @@ GRAD_WITHOUT_STEP_5 = {}
 def test_held_gradients(call, side):
     """Forward, ``torch.autograd.grad`` and the read of the gradient inside the side-stream context: the backward runs on
     autograd's worker thread, on the stream of its forward."""
-    real, decoy = (torch.rand(GRAD_N, 3, generator=torch.Generator().manual_seed(s)).to(DEV) for s in (120, 130))
+    real, decoy = grad_clouds(GRAD_N)
     ref = sh.held_call(call, with_grad(GRAD_CALLS[call]), (real,), (decoy,), side,
                        check_hold=call not in GRAD_WITHOUT_STEP_5)
     grad = ref[-1]
